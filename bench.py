@@ -6,10 +6,11 @@ pseudo-label mining -> 9 losses -> full backward (backbone from plain3 up, FREEZ
 all-reduce when N > 1) -> SGD-momentum update of all 135.8 M trainable parameters.
 "image" = one view, so value = 4 * N * steps / time.
 
-    python bench.py [--gpus N --steps K --warmup W]        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]     (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 Prints ONE JSON line on rank 0 with the driver's contract plus `roofline` (dominant kernel, timed live with HIP
 events on the launch stream) and `cpu_baseline` (the oracle, timed on this host's cores, rank 0, N == 1 only).
+--dump-outputs DIR: rank 0 writes what the last timed step computed as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import json
@@ -99,6 +100,30 @@ def build(device, dtype, K=None, freeze_at=2):
     return model.to(device)
 
 
+DUMP_SAMPLE = 1 << 16       # --dump-outputs: elements kept of every parameter tensor larger than this
+
+
+def dump_outputs(out_dir, loss_dict, model):
+    """--dump-outputs: what a caller of the timed step holds after its last step, as float32 .npy files — the 9 losses run_step
+    returned (<loss name>.npy, 0-d) and every trainable parameter the step updated (param.<name>.npy, flattened).  A tensor of more
+    than DUMP_SAMPLE elements is represented by DUMP_SAMPLE of them, at sorted indices drawn from a generator seeded by its name
+    (the same indices in every run and every build; ~8 MB in all).  The inputs are seeded too (make_inputs, the sampler, build's
+    manual_seed): two builds run with the same arguments can be compared file by file."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in loss_dict.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v.detach().float().cpu().numpy())
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, f"param.{name}.npy"), flat.float().cpu().numpy())
+
+
 def _cpu_params(K_):
     """random-init parameters of the benchmarked architecture under the reference's state-dict names (numpy, fp32)"""
     from oracle import oicr_oracle as O
@@ -178,6 +203,9 @@ def main():
                     help="skip the short runs of config #3's / #4's / #5's per-GPU shapes (extra keys b2_ms_per_step, coco_ms_per_step, stage3_ms_per_iter)")
     ap.add_argument("--graph", type=int, default=None,
                     help="1: replay the step as a captured hipGraph (default for --gpus 1), 0: eager launches (default under DDP)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's losses and a seeded sample of the parameters it updated "
+                         "as DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -254,10 +282,15 @@ def main():
     phase("model built, graphs captured, warm-up done")
     t0 = time.perf_counter()
     for i in range(args.steps):
-        trainer.run_step(batches[i % 2])
+        last = trainer.run_step(batches[i % 2])
     sync()
     dt = time.perf_counter() - t0
     phase("timed region done")
+    if args.dump_outputs and rank == 0:
+        # now, before the eager / instrumented steps below: they update the parameters again, and a graph replay overwrites the
+        # loss vector (a static output of the captured step) in place
+        dump_outputs(args.dump_outputs, last, model)
+        phase(f"outputs of the last timed step written to {args.dump_outputs}")
     # per-kernel durations need HIP events between launches: a graph replay has no place for them, and in an eager run they are
     # instrumentation (~0.3 ms of stream time per step) — so the same kernels are timed in a few eager steps AFTER the measured
     # region (same shapes, same data, every rank alike so that the collectives stay in step)

@@ -11,14 +11,17 @@ from the reference's source text.
 import os
 import sys
 
-import numpy as np
-import torch
-import torch.nn.functional as F
+os.environ.update({"MKL_CBWR": "COMPATIBLE"})         # = oicr_oracle.REPRODUCIBLE_ENV, before MKL starts
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..", "..")))
 import ref_shim  # noqa: E402
 from oracle import oicr_oracle as O  # noqa: E402
+
+O.reproducible_numerics()               # the fixtures' fp32 numbers are the same bits on every x86-64 host
 
 ns = ref_shim.install()
 Boxes, Instances = ns.boxes.Boxes, ns.instances.Instances
@@ -128,8 +131,6 @@ def run_e2e(case):
         out[f"r{k}/pgt_scores"] = t.gt_scores.numpy(); out[f"r{k}/pgt_boxes"] = t.gt_boxes.tensor.numpy()
         out[f"r{k}/gt_classes"] = l.gt_classes.numpy(); out[f"r{k}/gt_index"] = l.gt_index.numpy()
         out[f"r{k}/gt_weights"] = l.gt_weights.numpy()
-        for v in range(4):
-            out[f"r{k}/logits_v{v}"] = rec["refine"][k][v][0].numpy()
     sd = dict(model.named_parameters())
     for k in GRAD_KEYS_FULL:
         out["grad/" + k] = sd[k].grad.numpy()

@@ -1,24 +1,66 @@
 """CPU: the oracle restatement vs the fixtures generated from the reference's own Python
 (tests/golden/make_golden.py) and vs the known-answer vectors of the reference's unit tests."""
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import oicr_oracle as O
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)                                    # (also as the child process below)
+from oracle import oicr_oracle as O  # noqa: E402
 
 
-@pytest.mark.parametrize("case", ["s0", "s1", "c0"])
-def test_e2e_losses_grads_and_integer_outputs(case, golden_dir):
+def _e2e(golden_dir, case):
     g = np.load(os.path.join(golden_dir, f"e2e_{case}.npz"), allow_pickle=False)
     K, R, H, W = int(g["K"]), int(g["R"]), int(g["H"]), int(g["W"])
     dan = tuple(int(x) for x in g["dan"])
     P = O.make_params(K, dan, tag="p" + case, head_scale=float(g["head_scale"]))
     views, gt = O.make_views(H, W, R, n_gt=int(g["n_gt"]), K=K, tag="v" + case)
     masks = O.make_masks(R, dan, tag="m" + case)
-    assert np.array_equal(gt, g["gt"])
     losses, aux, grads = O.oicr_plus_iteration(P, views, gt, masks, K=K, want_grads=True)
+    out = {"gt": gt, **{"loss/" + k: np.float64(v) for k, v in losses.items()}, **{"grad/" + k: v for k, v in grads.items()}}
+    for k, r in enumerate(aux["rounds"]):
+        out.update({f"r{k}/pgt_index": r["pgt"]["index"], f"r{k}/pgt_classes": r["pgt"]["classes"],
+                    f"r{k}/gt_classes": r["labels"]["gt_classes"], f"r{k}/gt_index": r["labels"]["gt_index"],
+                    f"r{k}/gt_weights": r["labels"]["gt_weights"]})
+    for v in range(4):
+        out[f"wsddn_v{v}"], out[f"fc7_v{v}"], out[f"plain5_v{v}"] = aux["wsddn_scores"][v], aux["fc7"][v], aux["plain5"][v]
+    return out
+
+
+def _infer(golden_dir, case):
+    e = np.load(os.path.join(golden_dir, f"e2e_{case}.npz"))
+    dan = tuple(int(x) for x in e["dan"])
+    P = O.make_params(20, dan, tag="p" + case, head_scale=float(e["head_scale"]))
+    views, _ = O.make_views(int(e["H"]), int(e["W"]), int(e["R"]), n_gt=int(e["n_gt"]), K=20, tag="v" + case)
+    return O.oicr_plus_inference(P, views[0]["image"], views[0]["boxes"], views[0]["obj"], K=20)
+
+
+def _in_reproducible_mode(what, case, golden_dir, tmp_path):
+    """the fixtures hold fp32 numbers of oicr_oracle's reproducible numeric mode (the same bits on every x86-64 host): run the oracle
+    in a child process started in that mode (MKL reads it when it starts, so this process cannot switch to it) and load its outputs"""
+    out = str(tmp_path / f"{what}_{case}.npz")
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), what, case, golden_dir, out],
+                       env=dict(os.environ, **O.REPRODUCIBLE_ENV), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return np.load(out)
+
+
+@pytest.mark.parametrize("case", ["s0", "s1", "c0"])
+def test_e2e_losses_grads_and_integer_outputs(case, golden_dir, tmp_path):
+    g = np.load(os.path.join(golden_dir, f"e2e_{case}.npz"), allow_pickle=False)
+    o = _in_reproducible_mode("e2e", case, golden_dir, tmp_path)
+    assert np.array_equal(o["gt"], g["gt"])
+    losses = {k[5:]: float(o[k]) for k in o.files if k.startswith("loss/")}
+    aux = {"rounds": [{"pgt": {"index": o[f"r{k}/pgt_index"], "classes": o[f"r{k}/pgt_classes"]},
+                       "labels": {n: o[f"r{k}/{n}"] for n in ("gt_classes", "gt_index", "gt_weights")}} for k in range(4)],
+           "wsddn_scores": [o[f"wsddn_v{v}"] for v in range(4)], "fc7": [o[f"fc7_v{v}"] for v in range(4)],
+           "plain5": [o[f"plain5_v{v}"] for v in range(4)]}
+    grads = {k[5:]: o[k] for k in o.files if k.startswith("grad/")}
     for k, v in losses.items():
         ref = float(g["loss/" + k])
         assert abs(v - ref) <= 1e-6 * max(abs(ref), 1e-6), (k, v, ref)      # fp32 losses: 1e-6 rel on CPU
@@ -74,13 +116,9 @@ def test_vector_nms_equals_the_line_by_line_restatement():
         assert np.array_equal(O.nms_keep(b, s, thr), O.nms_keep_scalar(b, s, thr)), (n, thr)
 
 
-def test_inference_matches_reference(golden_dir):
+def test_inference_matches_reference(golden_dir, tmp_path):
     g = np.load(os.path.join(golden_dir, "infer_s0.npz"))
-    e = np.load(os.path.join(golden_dir, "e2e_s0.npz"))
-    dan = tuple(int(x) for x in e["dan"])
-    P = O.make_params(20, dan, tag="ps0", head_scale=float(e["head_scale"]))
-    views, _ = O.make_views(int(e["H"]), int(e["W"]), int(e["R"]), n_gt=int(e["n_gt"]), K=20, tag="vs0")
-    o = O.oicr_plus_inference(P, views[0]["image"], views[0]["boxes"], views[0]["obj"], K=20)
+    o = _in_reproducible_mode("infer", "s0", golden_dir, tmp_path)
     assert np.array_equal(o["classes"], g["pred_classes"])
     np.testing.assert_allclose(o["scores"], g["scores"], rtol=1e-6)
     np.testing.assert_allclose(o["boxes"], g["pred_boxes"], rtol=1e-5, atol=1e-4)
@@ -134,3 +172,9 @@ def test_roipool_c_oracle_edge_cases():
     g = np.ones_like(out)
     gi = O.roi_pool_bwd(g, arg, rois, feat.shape)
     assert gi.sum() == (arg >= 0).sum()
+
+
+if __name__ == "__main__":                 # the child process of _in_reproducible_mode: what case golden_dir out.npz
+    O.reproducible_numerics()
+    what, case, gdir, path = sys.argv[1:5]
+    np.savez(path, **(_e2e if what == "e2e" else _infer)(gdir, case))
