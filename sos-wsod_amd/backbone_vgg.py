@@ -98,7 +98,7 @@ def _wgrad_grouped_target(shapes, bk, n_cu=256, candidates=(40, 48, 56, 64, 72, 
 def _wgrad_direct_covers(probs, dtype):
     """the shape conditions of the direct weight-gradient kernel (csrc/conv_wgrad_direct.hip, sw_conv3x3_wgrad_direct_try): every
     problem (n, H, W, cin, cout, dil) of a grouped launch must meet them, else the whole list runs as implicit GEMMs"""
-    if dtype != torch.bfloat16 or os.environ.get("SW_WGRAD_DIRECT", "1") == "0":
+    if dtype != torch.bfloat16:
         return False
     return all(cout % 64 == 0 and cin % 64 == 0 and dil in (1, 2) and H >= 8 and n * ((W + 31) // 32) * H >= 8
                for n, H, W, cin, cout, dil in probs)
@@ -223,8 +223,7 @@ class _VGGFunction(torch.autograd.Function):
                                           out=torch.empty(n_ * h_ * w_, 6 * cin, device=x.device, dtype=torch.bfloat16))
                     ops.conv3x3(x3.view(n_, h_, w_, 6 * cin), module.staged_weight_x3(w, 0, cin), out, blk.dilation, ep,
                                 tag=f"{blk.tag}.conv{ci + 1}_fwd")
-                elif not (module.winograd_ok(cin, blk.out_channels) and
-                        ops.conv3x3_winograd(cur, module.winograd_weight(w, 0), out, blk.dilation, ep, tag=f"{blk.tag}.conv{ci + 1}_fwd")):
+                else:
                     wk = module.staged_weight(w, 0, cin, dtype)
                     ops.conv3x3(cur, wk, out, blk.dilation, ep, tag=f"{blk.tag}.conv{ci + 1}_fwd")
                 conv_io.append((cur, out))
@@ -402,8 +401,7 @@ class _VGGFunction(torch.autograd.Function):
                                            out=torch.empty(n * H * W, 6 * cout, device=g.device, dtype=torch.bfloat16))
                     ops.conv3x3(dz3.view(n, H, W, 6 * cout), module.staged_weight_x3(w, 1, cin), dx, blk.dilation, epd,
                                 tag=f"{blk.tag}.conv{ci + 1}_dgrad")
-                elif not (module.winograd_ok(blk.out_channels, cin) and
-                        ops.conv3x3_winograd(dz, module.winograd_weight(w, 1), dx, blk.dilation, epd)):
+                else:
                     wkd = module.staged_weight(w, 1, cin, dtype)
                     ops.conv3x3(dz, wkd, dx, blk.dilation, epd, tag=f"{blk.tag}.conv{ci + 1}_dgrad")
                 dz = dx
@@ -432,14 +430,6 @@ class VGG16(nn.Module):
         # fp32x3).  SW_FP32X3_CONV=0 keeps them on the exact-f32 MFMA (A/B timing)
         self.fp32x3 = (compute_dtype == torch.float32 and os.environ.get("SW_FP32X3", "0") == "1"
                        and os.environ.get("SW_FP32X3_CONV", "1") != "0")
-        # Winograd F(2x2, 3x3) for the forward / data gradient of the wide bf16 layers (csrc/conv_winograd.hip): 2.25x fewer MFMA cycles
-        # than the direct kernel — built, bit-validated (relative L2 3.8e-3 against float64, the direct form 2.4e-3) and MEASURED SLOWER
-        # on this part: conv5_3 42.4 vs 38.2 us, conv3_2 49.4 vs 39.3 us (profiles/r05_winograd_experiment.txt: the f32 input transform
-        # and three barriers per 32-channel chunk cost more than the MFMAs saved).  So it is OFF by default; SW_CONV_WINOGRAD=1 routes
-        # the layers with Cin >= SW_WINOGRAD_MIN_CIN (default 256: conv3_2 .. conv5_3) through it.  fp32 mode never uses it.
-        self.winograd = os.environ.get("SW_CONV_WINOGRAD", "0") == "1" and compute_dtype == torch.bfloat16
-        self.winograd_min_cin = int(os.environ.get("SW_WINOGRAD_MIN_CIN", "256"))
-        self._wino_cache = {}
         self._out_feature_strides, self._out_feature_channels = {}, {}
         self.stages_and_names = []
         strides = {"plain1": 2, "plain2": 4, "plain3": 8, "plain4": 8 if conv5_dilation == 2 else 16,
@@ -512,35 +502,6 @@ class VGG16(nn.Module):
         self._wk3_cache[slot] = (key, buf)
         return buf
 
-    def winograd_ok(self, cin, cout):
-        return self.winograd and cin >= self.winograd_min_cin and cin % 32 == 0 and cout % 2 == 0
-
-    def winograd_weight(self, w, mode):
-        """the transformed filters U = G g G^T (bf16, (16, n_out, n_in)) of an OIHW master for the Winograd kernel — mode 0 forward,
-        1 data gradient — current for the parameter's present value (stage_all_weights builds every stale one in ONE launch; a
-        miss here builds its own)"""
-        hit = self._wino_cache.get((id(w), mode))
-        if hit is None or hit[0] != ops.param_key(w):
-            self._winograd_refresh([(w, mode)])
-            hit = self._wino_cache[(id(w), mode)]
-        return hit[1]
-
-    def _winograd_refresh(self, wanted):
-        items = []
-        for w, mode in wanted:
-            key = ops.param_key(w)
-            hit = self._wino_cache.get((id(w), mode))
-            if hit is not None and hit[0] == key:
-                continue
-            cout, cin = w.shape[:2]
-            shape = (16, cout, cin) if mode == 0 else (16, cin, cout)
-            U = hit[1] if (hit is not None and tuple(hit[1].shape) == shape and hit[1].device == w.device) else \
-                torch.empty(shape, device=w.device, dtype=torch.bfloat16)
-            items.append((w.detach(), U, mode))
-            self._wino_cache[(id(w), mode)] = (key, U)
-        if items:
-            ops.winograd_weight_prep(items)
-
     def _register_staging(self, w, dtype):
         cout, cin = w.shape[:2]
         s0, s1 = self._wk_cache.get((id(w), 0)), self._wk_cache.get((id(w), 1))
@@ -561,29 +522,17 @@ class VGG16(nn.Module):
         dtype = self.compute_dtype
         epc = _epc(dtype)
         ft = self.first_trainable_conv()
-        wino = []
         for si, blk in enumerate(self.blocks):
             for ci, c in enumerate(blk.convs()):
                 cout, cin = c.weight.shape[:2]
-                if self.winograd_ok(cin, cout):                      # the Winograd layers take transformed filters instead
-                    wino.append((c.weight, 0))
-                    if with_dgrad and ft is not None and (si, ci) > ft and self.winograd_ok(cout, cin):
-                        wino.append((c.weight, 1))
-                    elif with_dgrad and ft is not None and (si, ci) > ft:
-                        self.staged_weight(c.weight, 1, cin, dtype)
-                    continue
                 cin_pad = (cin + epc - 1) // epc * epc
                 self.staged_weight(c.weight, 0, cin_pad, dtype)
                 if self.x3_layer(dtype, cin_pad, cout):              # the three-piece copies too: both streams read them
                     self.staged_weight_x3(c.weight, 0, cin_pad)
                 if with_dgrad and ft is not None and (si, ci) > ft:
-                    if self.winograd_ok(cout, cin):
-                        wino.append((c.weight, 1))
-                    else:
-                        self.staged_weight(c.weight, 1, cin, dtype)
-                        if self.x3_layer(dtype, cout, cin):
-                            self.staged_weight_x3(c.weight, 1, cin)
-        self._winograd_refresh(wino)
+                    self.staged_weight(c.weight, 1, cin, dtype)
+                    if self.x3_layer(dtype, cout, cin):
+                        self.staged_weight_x3(c.weight, 1, cin)
 
     def first_trainable_conv(self):
         for si, blk in enumerate(self.blocks):

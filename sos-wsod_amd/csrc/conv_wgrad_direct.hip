@@ -26,7 +26,6 @@
 // History of the round (profiles/r06_wgrad_*): one 8-wave workgroup per CU (128 x 64 blocks) ran 0.21-0.29 of peak — the two waves of a SIMD
 // sat in the same phase of the same program; two independent 4-wave workgroups 0.30-0.39; the compiler's s_waitcnt vmcnt(0) in front of the
 // first transposed read after every DMA issue (dma16 below) was the rest: 0.45-0.50 of peak by the layers' true FLOP, MFMA pipe 63 % busy.
-#include <stdlib.h>
 #include "common.h"
 #include "soswsod_hip.h"
 
@@ -248,8 +247,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_direct_kernel(WdArgs wa) {
 // Returns 1 if the direct kernel took the whole problem list, 0 if some problem is not covered (the caller runs the implicit GEMM), < 0 on
 // error.  `eff[i]` = slabs problem i must write (sw_conv3x3_wgrad_workspace_floats / (Cout * 9 * Cin)).
 int sw_conv3x3_wgrad_direct_try(int n_problems, const sw_wgrad_problem* problems, const int* eff, hipStream_t stream) {
-  static const char* sw = getenv("SW_WGRAD_DIRECT");          // development switch: "0" = never
-  if (sw && sw[0] == '0') return 0;
   if (n_problems <= 0) return 1;
   for (int i = 0; i < n_problems; ++i) {
     const sw_wgrad_problem& q = problems[i];
@@ -260,12 +257,7 @@ int sw_conv3x3_wgrad_direct_try(int n_problems, const sw_wgrad_problem* problems
     const long xb = (long)q.nimg * q.H * q.W * q.Cin * 2, db = (long)q.nimg * q.H * q.W * q.Cout * 2;
     if (xb >= 0xFFFFFF00L || db >= 0xFFFFFF00L) return 0;
   }
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ncu = n;
-    else ncu = 256;
-  }
+  const int ncu = sw_cu_count();
   hipError_t e = hipFuncSetAttribute((const void*)conv_wgrad_direct_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WD_LDS);
   if (e != hipSuccess) return -(int)e;
   for (int base = 0; base < n_problems; base += WD_MAX) {

@@ -17,7 +17,6 @@
 // (one barrier per K-tile) and, for 256x256 tiles with a K-contiguous A operand, 8 waves of 128x64 in two staggered groups
 // (ping-pong: one group issues MFMAs while the other loads).  gemm2_grouped_kernel walks a list of conv weight-gradient
 // problems with the same tile code.
-#include <stdlib.h>
 #include "common.h"
 #include "soswsod_hip.h"
 
@@ -60,10 +59,9 @@ __device__ const u32x4 g_zero_chunk = {0u, 0u, 0u, 0u};   // source of zero fill
 
 
 // MFMA shape per dtype.  bf16: v_mfma_f32_16x16x32_bf16 (16 cycles, K = 32) — on MI355X the chip holds a higher clock
-// on this shape than on 32x32x16 at equal cycles per FLOP (MI355X_MICROARCH.md "DVFS give-back" item 7); set
-// -DSW_MFMA32 to build the 32x32x16 variant for A/B runs.  f32: v_mfma_f32_32x32x2_f32 (exact f32).
+// on this shape than on 32x32x16 at equal cycles per FLOP (MI355X_MICROARCH.md "DVFS give-back" item 7).
+// f32: v_mfma_f32_32x32x2_f32 (exact f32).
 template <typename T> struct Mma;
-#ifndef SW_MFMA32
 template <> struct Mma<unsigned short> {
   static constexpr int TS = 16, NSTEP = 2, NACC = 4;         // sub-tile size, K sub-steps per K-tile, acc regs per lane
   typedef f32x4 Acc;
@@ -74,17 +72,6 @@ template <> struct Mma<unsigned short> {
   __device__ static __forceinline__ int row(int lane, int e) { return (lane >> 4) * 4 + e; }
   __device__ static __forceinline__ int col(int lane) { return lane & 15; }
 };
-#else
-template <> struct Mma<unsigned short> {
-  static constexpr int TS = 32, NSTEP = 4, NACC = 16;
-  typedef f32x16 Acc;
-  __device__ static __forceinline__ void mma(Acc& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-  }
-  __device__ static __forceinline__ int row(int lane, int e) { return (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5); }
-  __device__ static __forceinline__ int col(int lane) { return lane & 31; }
-};
-#endif
 template <> struct Mma<float> {
   static constexpr int TS = 32, NSTEP = 4, NACC = 16;
   typedef f32x16 Acc;
@@ -434,9 +421,9 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
   // LDS-DMA schedule (2 buffers): the pieces of tile t+2 go out in phase 3 of tile t (its buffer was last read in phase 2: the
   // second group drains those reads before the barrier) and phases 0-2 of tile t+1; each wave waits for them with a counted
   // vmcnt at the end of tile t+1, one barrier before the first read.
-  constexpr bool PP = (BM == 256 && BN == 256 && WTM == 128 && WTN == 64 && STAGES == 2 && sizeof(T) == 2 && (TS == 16 || TS == 32) &&
-                       AMODE <= OP_KSTRIDED && BMODE <= OP_KSTRIDED);
-  constexpr int QI = 64 / TS, QJ = 32 / TS;             // sub-tiles of a 64x32 quadrant (16x16x32: 4 x 2 x 2 K sub-steps; 32x32x16: 2 x 1 x 4)
+  constexpr bool PP = (BM == 256 && BN == 256 && WTM == 128 && WTN == 64 && STAGES == 2 && sizeof(T) == 2 &&
+                       AMODE == OP_KCONTIG && BMODE <= OP_KSTRIDED);
+  constexpr int QI = 64 / TS, QJ = 32 / TS;             // sub-tiles of a 64x32 quadrant (16x16x32: 4 x 2 x 2 K sub-steps)
   if constexpr (PP) {
     const int grp = wm;                                   // 0: waves 0-3, 1: waves 4-7
     auto dma_pair = [&](int tile, int j) {
@@ -449,9 +436,7 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
     dma_pair(1, 0);
     tile_wait(-1);
     __builtin_amdgcn_s_barrier();
-#ifndef SW_PP_NOSTAGGER
     if (grp == 1) __builtin_amdgcn_s_barrier();           // the stagger: group 1 runs one segment behind
-#endif
     u32x4 fa[QI][NSTEP], fb[2][QJ][NSTEP];
     for (int kt = 0; kt < nt; ++kt) {
       const char* sa = smem + (kt & 1) * STAGE_BYTES;
@@ -481,18 +466,14 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
         __builtin_amdgcn_sched_barrier(0);
         // ---- MFMA segment
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifndef SW_PP_NOPRIO
         __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int st = 0; st < NSTEP; ++st)
 #pragma unroll
           for (int ii = 0; ii < QI; ++ii)
 #pragma unroll
             for (int jj = 0; jj < QJ; ++jj) MM::mma(acc[mq * QI + ii][nq * QJ + jj], fa[ii][st], fb[nq][jj][st]);
-#ifndef SW_PP_NOPRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         if (grp == 0 && p == 3) tile_wait(kt);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -500,9 +481,7 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
       };
       phase(IntC<0>{}); phase(IntC<1>{}); phase(IntC<2>{}); phase(IntC<3>{});
     }
-#ifndef SW_PP_NOSTAGGER
     if (grp == 0) __builtin_amdgcn_s_barrier();           // both groups executed the same number of barriers
-#endif
   } else {
   // prologue: STAGES-1 K-tiles in flight
 #pragma unroll
@@ -661,14 +640,10 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
             } else {                                               // f32 rows (plain or K-split slab)
               float* dst = (float*)g.C + o + (g.slab_stride > 0 ? (long)zsplit * g.slab_stride : 0);
               // nontemporal: the 33-68 MB burst a round of tiles writes retires faster streamed past the write-back L2s, and the next
-              // tiles' loads queue behind it on the in-order vmcnt (fc6 data gradient 1.36 -> 1.25 ms; -D SW_EP_PLAIN_STORES for A/B).
+              // tiles' loads queue behind it on the in-order vmcnt (fc6 data gradient 1.36 -> 1.25 ms).
               // Unconditional on purpose: `if (flag) nontemporal else plain` is merged into one plain store by the optimiser, and
               // arms kept apart by an asm barrier stop the pieces' LDS reads and stores from overlapping (no gain left)
-#ifndef SW_EP_PLAIN_STORES
               if (full && vec_ok) __builtin_nontemporal_store(*(const f32x4*)&v[0], (f32x4*)dst);
-#else
-              if (full && vec_ok) *(f32x4*)dst = *(const f32x4*)&v[0];
-#endif
               else {
 #pragma unroll
                 for (int t = 0; t < 4; ++t) if (nb + t < g.N) dst[t] = v[t];
@@ -680,11 +655,7 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
               u32x4 w;
 #pragma unroll
               for (int t = 0; t < 4; ++t) w[t] = (unsigned)f32_to_bf16_bits(v[2 * t]) | ((unsigned)f32_to_bf16_bits(v[2 * t + 1]) << 16);
-#ifndef SW_EP_PLAIN_STORES
               __builtin_nontemporal_store(w, (u32x4*)dst);
-#else
-              *(u32x4*)dst = w;
-#endif
             } else {
 #pragma unroll
               for (int t = 0; t < CP; ++t) if (nb + t < g.N) dst[t] = f32_to_bf16_bits(v[t]);
@@ -788,17 +759,10 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
         if (staged) { stile[lrow * WTN + j * TS + r] = f32_to_bf16_bits(v); continue; }
         if (!ok) continue;
         const long o = (long)m * g.ldc + n;
-#ifndef SW_EP_PLAIN_STORES
         if (g.slab_stride > 0) __builtin_nontemporal_store(v, (float*)g.C + o + (long)zsplit * g.slab_stride);   // slabs: written once, folded once
         else if (g.atomic) atomicAdd((float*)g.C + o, v);
         else if (g.out_bf16) __builtin_nontemporal_store(f32_to_bf16_bits(v), (unsigned short*)g.C + o);
         else __builtin_nontemporal_store(v, (float*)g.C + o);
-#else
-        if (g.slab_stride > 0) ((float*)g.C)[o + (long)zsplit * g.slab_stride] = v;
-        else if (g.atomic) atomicAdd((float*)g.C + o, v);
-        else if (g.out_bf16) ((unsigned short*)g.C)[o] = f32_to_bf16_bits(v);
-        else ((float*)g.C)[o] = v;
-#endif
       }
     }
   if (staged) {
@@ -809,11 +773,7 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
       const int idx = q * 64 + lane, lrow = idx / CPRW, ch = idx % CPRW;
       const int m = m0 + wm * WTM + lrow, n = n0t + wn * WTN + ch * 8;
       if (m < g.M && n < g.N) {
-#ifndef SW_EP_PLAIN_STORES
         __builtin_nontemporal_store(*(const u32x4*)(stile + lrow * WTN + ch * 8), (u32x4*)((unsigned short*)g.C + (long)m * g.ldc + n));
-#else
-        *(u32x4*)((unsigned short*)g.C + (long)m * g.ldc + n) = *(const u32x4*)(stile + lrow * WTN + ch * 8);
-#endif
       }
     }
   }
@@ -943,17 +903,9 @@ int launch2(GemmArgs& g, int splitk, hipStream_t stream) {
   // Persistent form for the one-workgroup-per-CU tile (256x256, 128 KiB LDS) when there is more than one round of tiles: one
   // workgroup per CU walks the tile list (same XCD: virtual id = resident id + k * CUs keeps id & 7) instead of being
   // re-dispatched per tile — fc6's data gradient (12.25 rounds of 64 K-tiles) -2 %, the step -0.08 ms.
-  {
-    static const char* ps = getenv("SW_GEMM_PERSIST");          // development switch: resident workgroups, "0" = off
-    static int ncu = 0;
-    if (!ncu) {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ncu = n;
-      else ncu = 256;
-    }
-    const int np = ps ? atoi(ps) : ((ncu % 8) == 0 ? ncu : 0);
-    if (np > 0 && splitk == 1 && BM == 256 && BN == 256 && (int)grid.x > np) { g.vgrid = (int)grid.x; grid.x = np; }
-  }
+  // (only on a CU count that is a multiple of 8, for the XCD mapping)
+  const int ncu = sw_cu_count();
+  if ((ncu % 8) == 0 && splitk == 1 && BM == 256 && BN == 256 && (int)grid.x > ncu) { g.vgrid = (int)grid.x; grid.x = ncu; }
   auto kern = gemm2_kernel<T, AMODE, BMODE, BM, BN, STAGES, WTM, WTN>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
   if (e != hipSuccess) return (int)e;
@@ -972,39 +924,27 @@ int launch2(GemmArgs& g, int splitk, hipStream_t stream) {
 //     With ~250 tiles per conv4/conv5 launch, wave-level parallelism beat deeper prefetch: 2 stages == 4 stages in time.
 template <typename T, int AMODE, int BMODE>
 int launch_auto(GemmArgs& g, int splitk, hipStream_t s) {
-  static const char* v = getenv("SW_GEMM_V");               // development switch (tile override)
   const long sk = splitk < 1 ? 1 : splitk;
   auto tiles = [&](int bm, int bn) { return (long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * sk; };
   // the 256x256 tile pays off once the K loop is long enough to hide its prologue / epilogue: the 1x1 convolutions of a ResNet
   // (121 600 pixels x 256 channels, K = 64 .. 256: memory bound) ran 4x slower on it than on the 128x128 tile, two workgroups per
   // CU (244 vs 57 us; tools/probes/gemm_1x1_probe.py).  Every fc / conv shape of the OICR+ step has K >= 1152.
-  const bool big = (v && v[0] == '4') ? true : (v && v[0] == '8') ? false : (g.N > 128 && tiles(256, 256) >= 200 && g.K >= 1024);
-  if (big) {
-#ifdef SW_GEMM_TRY_4WAVE
-    // experiment (tools/build_variant.sh w4 -DSW_GEMM_TRY_4WAVE, SW_GEMM_W4=1): four waves of 128x128, 256 accumulator registers per lane
-    { static const bool w4 = getenv("SW_GEMM_W4") != nullptr;
-      if constexpr (sizeof(T) == 2 && AMODE == OP_KCONTIG && BMODE == OP_KCONTIG)
-        if (w4 && sk == 1) return launch2<T, AMODE, BMODE, 256, 256, 2, 128, 128>(g, splitk, s); }
-#endif
-    static const char* pp = getenv("SW_GEMM_PP");             // development switch: "0" = the 16-wave loop
+  if (g.N > 128 && tiles(256, 256) >= 200 && g.K >= 1024) {
     // ping-pong form (8 waves of 128x64, two staggered groups): forward / data-gradient shapes (A K-contiguous) run 4-6 % faster
     // on it; the weight gradients (both operands transposed on the fly: twice the LDS instructions per fragment in the load
-    // segments) stay on the 16-wave loop, +1 % there.  SW_GEMM_PP=0 / =2: never / also for the weight gradients.
-    if constexpr (sizeof(T) == 2 && AMODE <= OP_KSTRIDED && BMODE <= OP_KSTRIDED) {
-      const bool want = pp ? (pp[0] == '2' || (pp[0] != '0' && AMODE == OP_KCONTIG)) : AMODE == OP_KCONTIG;
-      if (want && (g.K % 64) == 0 && sk == 1) return launch2<T, AMODE, BMODE, 256, 256, 2, 128, 64>(g, splitk, s);
+    // segments) stay on the 16-wave loop, +1 % there.
+    if constexpr (sizeof(T) == 2 && AMODE == OP_KCONTIG && BMODE <= OP_KSTRIDED) {
+      if ((g.K % 64) == 0 && sk == 1) return launch2<T, AMODE, BMODE, 256, 256, 2, 128, 64>(g, splitk, s);
     }
     return launch2<T, AMODE, BMODE, 256, 256, 2>(g, splitk, s);
   }
-  const bool narrow = (v && v[0] == '6') || (!v && g.N <= 64 && sk == 1);     // 64-wide outputs (conv1_x): no half-empty N tile
-  if (narrow) return launch2<T, AMODE, BMODE, 256, 64, 2, 32, 64>(g, splitk, s);
+  // 64-wide outputs (conv1_x): no half-empty N tile
+  if (g.N <= 64 && sk == 1) return launch2<T, AMODE, BMODE, 256, 64, 2, 32, 64>(g, splitk, s);
   // Few tiles and a long K (a ResNet's res4 / res5 1x1 convolutions at batch 1-2: 30-60 tiles x 16-32 K-tiles): one workgroup per
   // CU at most, and its K loop runs at one memory round trip per K-tile (~1 us against 0.15 us of MFMA work) on the 2-buffer ring.
   // A 4-buffer ring keeps three K-tiles in flight (128 KiB of LDS: fine when no second workgroup would share the CU anyway).
   if constexpr (sizeof(T) == 2 && AMODE <= OP_KSTRIDED && BMODE <= OP_KSTRIDED) {
-    static const char* dp = getenv("SW_GEMM_DEEP");           // development switch: "0" = off, else the largest tile count
-    const long lim = dp ? atol(dp) : 256;
-    if (tiles(128, 128) <= lim && g.K >= 512) return launch2<T, AMODE, BMODE, 128, 128, 4, 32, 64>(g, splitk, s);
+    if (tiles(128, 128) <= 256 && g.K >= 512) return launch2<T, AMODE, BMODE, 128, 128, 4, 32, 64>(g, splitk, s);
   }
   return launch2<T, AMODE, BMODE, 128, 128, 2, 32, 64>(g, splitk, s);
 }
@@ -1158,9 +1098,7 @@ int sw_sgd_tile_t_block(int rows, int cols, float* param, const float* grad, flo
 
 // shapes the fused-SGD epilogue covers: launch_auto's ping-pong form (the only epilogue that implements it), whole 16-byte pieces
 static bool sgd_fused_shape_ok(int dtype, int a_kstrided, int b_kstrided, int M, int N, int K) {
-  static const char* pp = getenv("SW_GEMM_PP");
-  static const char* v = getenv("SW_GEMM_V");
-  if (dtype != SW_BF16 || a_kstrided || (pp && pp[0] == '0') || v) return false;
+  if (dtype != SW_BF16 || a_kstrided) return false;
   (void)b_kstrided;
   if ((M % 32) || (N % 64) || (K % 64) || K < 1024 || N <= 128) return false;
   return ((long)((M + 255) / 256) * ((N + 255) / 256)) >= 200;
@@ -1193,11 +1131,10 @@ extern "C" int sw_gemm(int dtype, int a_kstrided, int b_kstrided, int M, int N, 
   const bool has_row_scale = ep && ep->fold_row_scale;
   float* const det_ws = (ep && plain) ? ep->splitk_workspace : nullptr;
   {
-    static const bool no_peel = getenv("SW_GEMM_NO_PEEL") != nullptr;    // development switch
     int r = 0; long sk = 1;
     // (Peeling the bf16-output launches the same way — fc6's data gradient has 32 x 98 tiles = 12.25 rounds — gained 3 % alone
     // and lost 1 % inside the step: the persistent form already spreads its quarter round; not done.)
-    if (!no_peel && plain && !has_row_scale && splitk <= 1 && peel_geometry(M, N, &r, &sk)) {
+    if (plain && !has_row_scale && splitk <= 1 && peel_geometry(M, N, &r, &sk)) {
       const long es = dtype == SW_BF16 ? 2 : 4;
       const long tn = (N + 255) / 256;
       const int N1 = (int)((tn - r) * 256), N2 = N - N1;
@@ -1360,7 +1297,7 @@ extern "C" int sw_conv3x3_igemm(int dtype, int nimg, int H, int W, int Cin, int 
   g.cH = H; g.cW = W; g.cC = Cin; g.cDil = dilation;
   // bf16 only: the fp32 parity mode keeps the natural K order, whose f32 rounding tracks the reference's conv closely enough
   // that ReLU masks / pool argmax of near-zero activations do not flip (test_backbone_backward_matches_autograd)
-  { static const bool no_rot = getenv("SW_CONV_NO_KROT") != nullptr; g.krot = (no_rot || dtype != SW_BF16) ? 0 : 1; }
+  g.krot = dtype == SW_BF16 ? 1 : 0;
   if (ep) {
     g.bias = ep->bias; g.drop = ep->drop_mask; g.ldd = ep->ld_drop; g.drop_scale = ep->drop_scale;
     g.ref = ep->relu_ref; g.ldr = ep->ld_ref; g.ref_scale = ep->ref_scale; g.ref_bf16 = ep->ref_dtype == SW_BF16;
@@ -1530,12 +1467,7 @@ extern "C" int sw_conv3x3_wgrad_grouped(int dtype, int n_problems, const sw_wgra
   }
   const int epc = dtype == SW_BF16 ? 8 : 4, bk = dtype == SW_BF16 ? 64 : 32;
   const long es = dtype == SW_BF16 ? 2 : 4;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ncu = n;
-    else ncu = 256;
-  }
+  const int ncu = sw_cu_count();
   constexpr int LDS = 2 * (Geom2<unsigned short, OP_KSTRIDED, 256>::BYTES + Geom2<unsigned short, OP_CONV_B, 256>::BYTES);
   static_assert(LDS == 2 * (Geom2<float, OP_KSTRIDED, 256>::BYTES + Geom2<float, OP_CONV_B, 256>::BYTES), "one LDS size for both types");
   for (int base = 0; base < n_problems; base += GROUPED_MAX) {
@@ -1589,12 +1521,7 @@ extern "C" int sw_gemm_kk_grouped(int dtype, int n_problems, const sw_gemm_kk_pr
   if (n_problems <= 0) return 0;
   const int epc = dtype == SW_BF16 ? 8 : 4, bk = dtype == SW_BF16 ? 64 : 32;
   const long es = dtype == SW_BF16 ? 2 : 4;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ncu = n;
-    else ncu = 256;
-  }
+  const int ncu = sw_cu_count();
   constexpr int LDS = 4 * Geom2<unsigned short, OP_KSTRIDED, 256>::BYTES;
   static_assert(LDS == 4 * Geom2<float, OP_KSTRIDED, 256>::BYTES, "one LDS size for both types");
   for (int base = 0; base < n_problems; base += GROUPED_MAX) {

@@ -720,12 +720,6 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
   __shared__ unsigned long long s_row[64], s_kept;
   const float off = __fmul_rn((float)c, __fadd_rn(maxcoord[0], 1.0f));
   const bool pos_thresh = nms_thresh >= 0.f;
-#ifdef SW_NMS_TIMING
-  long long tt[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long t0 = wall_clock64();
-#define SW_T(k) { const long long t1 = wall_clock64(); tt[k] += t1 - t0; t0 = t1; }
-#else
-#define SW_T(k)
-#endif
   if (tid == 0) { s_valid = 0; s_nk = 0; }
   __syncthreads();
   for (int i0 = 0; i0 < R; i0 += blockDim.x) {                      // compaction (any order: the keys are unique, the sort orders them)
@@ -743,9 +737,7 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
   const int NPV = next_pow2(nv);
   for (int i = nv + tid; i < NPV; i += blockDim.x) keys[i] = ~0ull;
   __syncthreads();
-  SW_T(0)
   bitonic_sort<true>(keys, NPV);
-  SW_T(1)
   if (nvalid) {
     // mask form on offer (sw_detect_postprocess2): a class with mask_min or more candidates hands its sorted list to det_mask_kernel /
     // det_resolve_kernel (nvalid = count); a smaller one is finished right here (nvalid = -1: the two kernels skip it)
@@ -773,7 +765,6 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
       sup[u] = 0;                                                   // here the flags go by sorted position
     }
     __syncthreads();
-    SW_T(2)
     for (int c0 = 0; c0 < nv; c0 += 64) {
       if (s_nk >= topk) break;                                      // uniform (s_nk is written before the barriers below)
       const int cn = min(64, nv - c0);
@@ -793,7 +784,6 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
         }
       }
       __syncthreads();
-      SW_T(3)
       if (wave == 0) {
         // serial walk over the chunk on wave-uniform 64-bit masks (scalar registers): take the first live candidate, drop what
         // its row suppresses; row i lives in lane i and is fetched by v_readlane
@@ -819,7 +809,6 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
         if (lane == 0) { s_kept = kept; s_nk = nk; }
       }
       __syncthreads();
-      SW_T(4)
       const unsigned long long kept = s_kept;
       if (kept && s_nk < topk) {
         // later candidates against the chunk's kept boxes: a lane holds one candidate (64 per wave and pass), the kept boxes
@@ -849,11 +838,7 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
         }
       }
       __syncthreads();
-      SW_T(5)
     }
-#ifdef SW_NMS_TIMING
-    if (tid == 0 && c == 0) printf("nms level 0 (nv %d, kept %d): compaction %lld sort %lld stage %lld matrix %lld resolve %lld apply %lld  (100 MHz ticks)\n", nv, s_nk, tt[0], tt[1], tt[2], tt[3], tt[4], tt[5]);
-#endif
     if (tid == 0) cls_count[c] = s_nk;
     return;
   }
@@ -1139,10 +1124,8 @@ extern "C" int sw_oicr_mine_label(int R, int ncol, int K, int n_rounds, const fl
   if (R > (1 << 22) || (long)top_k * G > (1 << 22) || top_k > R || G < 1 || n_rounds < 1) return -6;
   if (((uintptr_t)boxes) & 15) return -4;                    // proposal boxes are read as float4
   const int np = mine_np(R, top_k, G);
-  static const bool no_stage = getenv("SW_MINE_NO_STAGE") != nullptr;      // development switch
-  const bool staged = !no_stage && mine_staged(R, top_k, G);
-  const int in_ws = (!staged && (size_t)np * 8 + (size_t)top_k * G > 144 * 1024) ? 1 : 0;
-  if (in_ws && !mine_keys_in_ws(R, top_k, G)) return -6;    // (only with the development switch: the workspace has no key array)
+  const bool staged = mine_staged(R, top_k, G);
+  const int in_ws = mine_keys_in_ws(R, top_k, G) ? 1 : 0;
   const int batch = staged ? mine_class_batch(R, top_k, G) : 1;
   const size_t lds = staged ? mine_staged_lds(R, top_k, G, batch) : (in_ws ? 0 : (size_t)np * 8) + (size_t)top_k * G;
   if (lds > 144 * 1024) return -6;
@@ -1218,10 +1201,9 @@ static int detect_postprocess_impl(int R, int K, const float* all_scores, const 
                      (float)img_h, all_scores, all_boxes, maxcoord);
   SW_CHECK_LAUNCH();
   int np = 64; while (np < R) np <<= 1;
-  static const bool no_mask = getenv("SW_NMS_NO_MASK") != nullptr;            // development switch
-  static const int mask_min = getenv("SW_NMS_MASK_MIN") ? atoi(getenv("SW_NMS_MASK_MIN")) : 256;     // development switch
+  constexpr int mask_min = 256;
   const long base = align256(sw_detect_workspace_bytes(K, topk)), mask_need = detect_mask_bytes(R, K);
-  const bool mask = !no_mask && mask_need > 0 && workspace_bytes >= base + mask_need && R >= mask_min;
+  const bool mask = mask_need > 0 && workspace_bytes >= base + mask_need && R >= mask_min;
   char* m = ws + base;
   int* nvalid = mask ? (int*)m : nullptr; m += align256((long)K * 4);
   unsigned long long* skeys = (unsigned long long*)m; m += align256((long)K * R * 8);

@@ -16,7 +16,6 @@
 // rows, which global float atomics serve ~17x below their peak rate).
 #include <float.h>
 #include <type_traits>
-#include <stdlib.h>
 #include "common.h"
 #include "soswsod_hip.h"
 
@@ -220,7 +219,6 @@ constexpr int FX_CHUNK = 1024;          // ROIs per compaction round of the fixe
 //      lo = rint((t * 2^frac - hi) * 2^bits') with |lo| <= 2^(bits'-1): two v_cvt_i32_f32 + two 32-bit LDS atomics = 2 x (30 - bits) + 1
 //      bits per term (27 at R_image = 2000, 25 at 4000: 2^-26 of the largest term against bf16's 2^-8 outputs), still without the
 //      emulated f32 -> i64 conversion (the kernel is VALU-issue bound: 88 M wave instructions per 4000 ROIs).
-//   1  one 32-bit word (round 2's form, 30 - bits bits per term): kept behind SW_ROI_BWD_ACC32 for A/B timing only.
 template <typename T, typename IT, int ACCMODE>
 __global__ __launch_bounds__(1024) void roi_pool_bwd_fx_kernel(int H, int W, int C, long ld, int nb, int CB,
                                                                const T* __restrict__ dout, const IT* __restrict__ argmax,
@@ -238,7 +236,7 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_fx_kernel(int H, int W, int
   const int px_per = (npix_all + gridDim.z - 1) / gridDim.z;
   const int p0 = blockIdx.z * px_per, p1 = min(npix_all, p0 + px_per);
   typedef typename std::conditional<ACCMODE == 0, unsigned long long, unsigned int>::type ACC;
-  constexpr int ACC_BYTES = ACCMODE == 1 ? 4 : 8;                // per pixel-channel
+  constexpr int ACC_BYTES = 8;                                   // per pixel-channel
   ACC* acc = (ACC*)smem;          // [CB][H*W] two's-complement fixed point: the lanes of a wave
                                                                 // hold bins of ONE channel => neighbouring pixels => distinct banks
                                                                 // (pixel-major [H*W][CB] put them 64 B apart: 8-16-way conflicts)
@@ -316,17 +314,10 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_fx_kernel(int H, int W, int
           const int r = s_r[min(l0 + u, cnt - 1)];
           const long base = (long)r * ld + (long)c0 * nb + (long)j * 4;
           // both streams are read exactly once: nontemporal loads (126 -> 115 us)
-#ifndef SW_ROI_PLAIN_LOADS
           if (sizeof(IT) == 4) av[u] = __builtin_nontemporal_load((const u32x4*)(argmax + base));
           else { const u32x2 t = __builtin_nontemporal_load((const u32x2*)(argmax + base)); av[u][0] = t[0]; av[u][1] = t[1]; }
           if (sizeof(T) == 2) { const u32x2 t = __builtin_nontemporal_load((const u32x2*)(dout + base)); dv[u][0] = t[0]; dv[u][1] = t[1]; }
           else dv[u] = __builtin_nontemporal_load((const u32x4*)(dout + base));
-#else
-          if (sizeof(IT) == 4) av[u] = *(const u32x4*)(argmax + base);
-          else { const u32x2 t = *(const u32x2*)(argmax + base); av[u][0] = t[0]; av[u][1] = t[1]; }
-          if (sizeof(T) == 2) { const u32x2 t = *(const u32x2*)(dout + base); dv[u][0] = t[0]; dv[u][1] = t[1]; }
-          else dv[u] = *(const u32x4*)(dout + base);
-#endif
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -345,9 +336,6 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_fx_kernel(int H, int W, int
               if (ACCMODE == 0) {
                 const long long q = __float2ll_rn(scalbnf(__fmul_rn(d, mul), frac));
                 atomicAdd((unsigned long long*)&acc[crow[e] + (int)rel], (unsigned long long)q);
-              } else if (ACCMODE == 1) {
-                const int q = __float2int_rn(scalbnf(__fmul_rn(d, mul), frac));
-                atomicAdd((unsigned int*)&acc[crow[e] + (int)rel], (unsigned int)q);
               } else {
                 const float t = scalbnf(__fmul_rn(d, mul), frac);            // |t| < 2^term_bits
                 const float hf = rintf(t);                                    // v_rndne_f32; t - hf is exact, |t - hf| <= 0.5
@@ -368,7 +356,6 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_fx_kernel(int H, int W, int
     const int p = i / CB, cc = i - p * CB;
     float v;
     if (ACCMODE == 0) v = scalbnf((float)(long long)acc[cc * npix + p], -frac);
-    else if (ACCMODE == 1) v = scalbnf((float)(int)acc[cc * npix + p], -frac);
     else v = scalbnf((float)(((long long)(int)acc[cc * npix + p] << lo_bits) + (long long)(int)acc[lo_off + cc * npix + p]),
                      -(frac + lo_bits));
     if (rimg && !(Elem<T>::load(rimg + (long)p * C + c0 + cc) > 0.f)) v = 0.f;
@@ -682,18 +669,6 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_plane_kernel(int H, int W, in
 // global memory.
 constexpr int SP_NT = 1024, SP_CH = 128, SP_NLEV = 6, SP_NHC = 7, SP_NCLS = SP_NLEV * SP_NHC;
 
-// development instrumentation (tools/build_variant.sh phases SRC=roipool -DSW_ROI_PHASES; tools/probes/roi_phases.py): shader-clock cycles
-// of workgroup thread 0 per phase, summed over the workgroups.  0 sort, 1 level-0 table, 2 level advances, 3 chunk tables + task list,
-// 4 task scan, 5 wait at the barriers behind a scan (imbalance inside a chunk), 6 whole kernel, 7 workgroups
-#ifdef SW_ROI_PHASES
-__device__ unsigned long long g_roi_phase[8];
-#define SP_T(var) const long long var = (long long)clock64()
-#define SP_ADD(i, a, b) do { if (threadIdx.x == 0) atomicAdd(&g_roi_phase[i], (unsigned long long)((b) - (a))); } while (0)
-#else
-#define SP_T(var) do {} while (0)
-#define SP_ADD(i, a, b) do {} while (0)
-#endif
-
 __device__ __forceinline__ unsigned int key16_of(unsigned int bts) {          // pix_to_keys for one bf16 value
   unsigned int key = (bts & 0x8000u) ? (bts ^ 0xFFFFu) : (bts | 0x8000u);
   if (bts > 0x7F80u && bts < 0x8000u) key = 0;                                // +NaN never wins
@@ -768,7 +743,6 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
       }
     }
   };
-  SP_T(t_begin);
   if (tid <= SP_NCLS) s_start[tid] = 0;
   __syncthreads();
   for_my_rois([&](int r) { atomicAdd(&s_start[roi_class(r) + 1], 1); });
@@ -779,7 +753,6 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
   __syncthreads();
   for_my_rois([&](int r) { s_lvl[atomicAdd(&s_fill[roi_class(r)], 1)] = (unsigned short)r; });
   const int n_rois = s_start[SP_NCLS];
-  SP_T(t_sorted); SP_ADD(0, t_begin, t_sorted); SP_ADD(7, 0, 1);
   if (n_rois == 0) return;                                          // (uniform: s_start is final since the barrier above)
 
   // ---- 2. level 0: candidates of the slab's pixels
@@ -804,13 +777,10 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
     }
   }
   constexpr unsigned KEY_INIT = 0x007FFFFFu;                        // key(-inf) << 16 | 0xFFFF
-  SP_T(t_tab0); SP_ADD(1, t_sorted, t_tab0);
   for (int L = 0; L < SP_NLEV; ++L) {
     const int c_lo = s_start[L * SP_NHC], c_hi = s_start[(L + 1) * SP_NHC];
     if (c_lo >= n_rois) break;                                      // no ROI at this or a higher level
-    SP_T(t_lv0);
     __syncthreads();                                                // level L - 1 fully scanned (L = 0: table and list written)
-    SP_T(t_lv1); SP_ADD(5, t_lv0, t_lv1);
     if (L > 0) {
       // ---- 3. T_L from T_{L-1}, in place: every thread reads its pixels' two spans, barrier, writes
       const int d = 1 << (L - 1);
@@ -840,12 +810,9 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
       __syncthreads();
     }
     const int span = 1 << L;
-    SP_T(t_lv2); SP_ADD(2, t_lv1, t_lv2);
     for (int cs = c_lo; cs < c_hi; cs += SP_CHK) {
       const int cnt = min(SP_CHK, c_hi - cs);
-      SP_T(t_c0);
       __syncthreads();                                              // the previous chunk's tables are no longer read
-      SP_T(t_c1); SP_ADD(5, t_c0, t_c1);
       if (tid == 0) { s_ntask = 0; s_claim = 0; }
       for (int i = tid; i < cnt * (PH + PW); i += NT) {
         const int li = i / (PH + PW), k = i - li * (PH + PW);
@@ -880,7 +847,6 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
         __syncthreads();
         ntask = s_ntask;
       }
-      SP_T(t_c2); SP_ADD(3, t_c1, t_c2);
       const int total = ntask * PW;
       // 64-item units CLAIMED by the waves from an LDS counter (round 6; dealt by position, a wave waited at the chunk's closing barrier
       // for 23 % of the workgroup's cycles on the 63x63 map: 98 units per 128-ROI chunk over 16 waves, and the units differ in length)
@@ -988,10 +954,8 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
           argmax[o + (long)q * nb] = ArgIdx<IT>::enc(mi[q]);
         }
       }
-      SP_T(t_c3); SP_ADD(4, t_c2, t_c3);
     }   // chunks of the level
   }     // levels
-  SP_T(t_end); SP_ADD(6, t_begin, t_end);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -1150,11 +1114,12 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
                                                                 const u32x4* __restrict__ tasks, const int* __restrict__ seg, long cap,
                                                                 unsigned short* __restrict__ out, IT* __restrict__ argmax,
                                                                 int band_S, int band_rows, int n_bands, int n_zsplit) {
+  static_assert(CB == 4 && NT == 1024, "launch_fwd_tasks runs 4 channels per lane, one 1024-thread workgroup per CU");
   const int PH = PFIX ? PFIX : PH_, PW = PFIX ? PFIX : PW_;
-  constexpr int EW = CB == 2 ? 2 : 4;                               // channels per table entry: 8-byte entries for 2-channel slabs, else 16
+  constexpr int EW = 4;                                             // channels per table entry (16 bytes)
   constexpr int NPL = CB / EW;                                      // planes of entries
-  typedef typename std::conditional<CB == 2, u32x2, u32x4>::type TE;
-  constexpr int PXT = (CB == 8 ? 5 : CB == 4 ? 10 : 20) * (1024 / NT);   // table pixels per thread (host: rows * W <= PXT * NT)
+  typedef u32x4 TE;
+  constexpr int PXT = 10;                                           // table pixels per thread (host: rows * W <= PXT * NT)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int s_seg[TK_SEG], s_next[SP_NLEV];                  // s_next[L]: units of level L claimed so far
   // (band = blockIdx.z % n_bands keeps the 8 slabs of a 64-channel group, which write neighbouring runs of every ROI row, in the same
@@ -1169,7 +1134,6 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
   const int tid = threadIdx.x;
   const int nb = PH * PW;
   const unsigned short* fimg = feat + (long)img * H * W * C + c0;
-  SP_T(t_begin);
   if (tid < TK_SEG) s_seg[tid] = seg[((long)img * n_bands + band) * TK_SEG + tid];
   if (tid < SP_NLEV) s_next[tid] = 0;
   __syncthreads();
@@ -1189,9 +1153,7 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
     for (int j = 0; j < CB / 2; ++j) raw[k][j] = 0u;
     if (px < npx_t) {
       const unsigned short* src = fimg + (long)(y0 * W + px) * C;
-      if constexpr (CB == 8) { const u32x4 w = *(const u32x4*)src; raw[k][0] = w[0]; raw[k][1] = w[1]; raw[k][2] = w[2]; raw[k][3] = w[3]; }
-      else if constexpr (CB == 4) { const u32x2 w = *(const u32x2*)src; raw[k][0] = w[0]; raw[k][1] = w[1]; }
-      else raw[k][0] = *(const unsigned int*)src;
+      const u32x2 w = *(const u32x2*)src; raw[k][0] = w[0]; raw[k][1] = w[1];
     }
   }
 #pragma unroll
@@ -1217,15 +1179,10 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
   // the units' lengths, see the claims below; the stores' share is what this form removes)
   auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   constexpr unsigned KEY_INIT = 0x007FFFFFu;                        // key(-inf) << 16 | 0xFFFF
-  // (development instrumentation as in the sparse kernel, -DSW_ROI_PHASES: 0 -, 1 level-0 table, 2 level advances, 3 first records of
-  // a level, 4 item loop, 5 barrier at a level's start, 6 whole kernel, 7 workgroups)
-  SP_T(t_tab0); SP_ADD(1, t_begin, t_tab0); SP_ADD(7, 0, 1);
   for (int L = 0; L < SP_NLEV; ++L) {
     const int t_lo = s_seg[L * SP_NHC], t_hi = s_seg[(L + 1) * SP_NHC];
     if (t_lo >= n_tasks_end) break;                                 // no task at this or a higher level
-    SP_T(t_lv0);
     lds_barrier();                                                // level L - 1 fully scanned (L = 0: table written)
-    SP_T(t_lv1); SP_ADD(L == 0 ? 0 : 5, t_lv0, t_lv1);
     if (L > 0) {
       const int d = 1 << (L - 1);
       TE nv[PXT][NPL];
@@ -1255,7 +1212,6 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
       lds_barrier();
     }
     const int span = 1 << L;
-    SP_T(t_lv2); SP_ADD(2, t_lv1, t_lv2);
     const int n_lvl = t_hi - t_lo, total = n_lvl * PW;
     // Items (task, bin column) of the level, in units of 64 consecutive ones per wave and iteration.
     // The <= 10 records (7 bin columns) a wave's 64 items touch are consecutive in the list; 20 lanes fetch them (16 bytes each) THREE
@@ -1289,7 +1245,6 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
     int un0 = claim(), un1 = claim(), un2 = claim(), un3 = claim();      // first items of the claimed units
     u32x4 r1 = u32x4{0u, 0u, 0u, 0u}, r2 = r1;
     if (lane < 2 * n_rec) { const u32x4 r0 = fetch(un0); r1 = fetch(un1); r2 = fetch(un2); *(u32x4*)(wbuf + lane * 16) = r0; }
-    SP_T(t_lv3); SP_ADD(3, t_lv2, t_lv3);
     for (int k = 0; un0 >= 0; ++k) {
       u32x4 r3 = r2;
       if (lane < 2 * n_rec) r3 = fetch(un3);
@@ -1308,11 +1263,7 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
       unsigned int best[CB];
 #pragma unroll
       for (int q = 0; q < CB; ++q) best[q] = KEY_INIT;
-#ifdef SW_TK_NOSCAN                     // development ablation (tools/build_variant.sh): no window scan
-      if (!empty && hs == 250) {
-#else
       if (!empty) {
-#endif
         const int bw = we - ws;
         const int he_lds = min(he, y1);
         int cold_from = max(hs, y1);                                // first window row read from global memory
@@ -1364,9 +1315,7 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
             const int gi = hh * W + x;
             const unsigned int inv0 = 0xFFFEu - (unsigned)gi;
             unsigned int u[CB / 2];
-            if constexpr (CB == 8) { const u32x4 w = *(const u32x4*)(fimg + (long)gi * C); u[0] = w[0]; u[1] = w[1]; u[2] = w[2]; u[3] = w[3]; }
-            else if constexpr (CB == 4) { const u32x2 w = *(const u32x2*)(fimg + (long)gi * C); u[0] = w[0]; u[1] = w[1]; }
-            else u[0] = *(const unsigned int*)(fimg + (long)gi * C);
+            const u32x2 w = *(const u32x2*)(fimg + (long)gi * C); u[0] = w[0]; u[1] = w[1];
 #pragma unroll
             for (int k = 0; k < CB / 2; ++k) {
               best[2 * k] = max(best[2 * k], (key16_of(u[k] & 0xFFFFu) << 16) | inv0);
@@ -1390,9 +1339,6 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
       }
       const float mul = __uint_as_float(q0[2]);
       const long o = (long)r * ld + (long)c0 * nb + b;
-#ifdef SW_TK_NOSTORE                    // development ablation: the 2 x CB stores only for a value that does not occur
-      if (lowest == 0x12345u)
-#endif
 #pragma unroll
       for (int q = 0; q < CB; ++q) {
         Elem<unsigned short>::store(out + o + (long)q * nb, __fmul_rn(mv[q], mul));
@@ -1402,10 +1348,8 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
       r1 = r2; r2 = r3;
       un0 = un1; un1 = un2; un2 = un3; un3 = un4;
     }
-    SP_T(t_lv4); SP_ADD(4, t_lv3, t_lv4);
     }
   }     // levels
-  SP_T(t_end); SP_ADD(6, t_begin, t_end);
 }
 
 // max |x| over n elements -> out[0] (f32; caller zero-fills).  |x| as IEEE bits is monotone => integer atomicMax; a NaN in x
@@ -1444,10 +1388,9 @@ namespace {
 // workgroups per (slab, image, band) = how many ways the ROI chunks are dealt out: enough workgroups to fill the chip a few times
 // over (the chunks differ in work), no more (each one fetches its slab of the map)
 inline int fwd_zsplit(int wg_per_z, int n_chunks, size_t lds) {
-  // measured (tools/roi_bench_voc.py, SW_ROI_FWD_WGS sweep): one-workgroup-per-CU slabs 512-1024 workgroups (150x200 map: 1.36 ms
+  // measured (tools/roi_bench_voc.py, workgroup target sweep): one-workgroup-per-CU slabs 512-1024 workgroups (150x200 map: 1.36 ms
   // at 1024, 1.52 at 4096), two-per-CU slabs flat from 512 to 4096
-  static const int forced = getenv("SW_ROI_FWD_WGS") ? atoi(getenv("SW_ROI_FWD_WGS")) : 0;      // development switch
-  const int target = forced ? forced : (lds > 80 * 1024 ? 768 : 2048);
+  const int target = lds > 80 * 1024 ? 768 : 2048;
   int nz = (target + wg_per_z - 1) / wg_per_z;
   nz = nz < 1 ? 1 : nz;
   return nz > n_chunks ? n_chunks : nz;
@@ -1527,55 +1470,42 @@ int launch_fwd_sparse(int nimg, int H, int W, int C, long ld, int PH, int PW, fl
   constexpr size_t LDS_MAX = 160 * 1024 - 1536;                     // the kernel's static LDS (class tables) + alignment
   const int n_blocks = (R + 127) / 128;                             // row blocks of 128 ROIs are dealt to the workgroups of a (slab, image)
   // workgroups: ONE per CU (every form here holds most of a CU's LDS, and a workgroup's fixed work — its share of the ROI sort, the
-  // slab fetch, the level advances — is paid per workgroup: 63x63 / 4000 ROIs 156 us at 256 workgroups, 188 at 768, 226 at 1536);
-  // SW_ROI_FWD_WGS overrides the target
-  static const int forced = getenv("SW_ROI_FWD_WGS") ? atoi(getenv("SW_ROI_FWD_WGS")) : 0;      // development switch
+  // slab fetch, the level advances — is paid per workgroup: 63x63 / 4000 ROIs 156 us at 256 workgroups, 188 at 768, 226 at 1536)
   auto zsplit = [&](int wg_per_z) {
-    const int target = forced ? forced : 256;
-    int nz = (target + wg_per_z / 2) / wg_per_z;
+    int nz = (256 + wg_per_z / 2) / wg_per_z;
     nz = nz < 1 ? 1 : nz;
     return nz > n_blocks ? n_blocks : nz;
   };
-  static const bool force_cb4 = getenv("SW_ROI_SPARSE_CB4") != nullptr;                // development switch: 4 channels per lane everywhere
-  // ROIs per chunk: a run-time kernel argument since round 6 (SW_ROI_SPARSE_CHUNK, development switch).  The phase clocks of the band form
-  // (99x165 map: 29 % of a workgroup's cycles in chunk set-up, 21 % at the barrier behind a scan; profiles/r06_roi_phases.txt) suggested
-  // larger chunks; measured, they are slower on every map (99x165 / 8000 ROIs: 672 us at 128, 684 at 256, 792 at 512, 1041 at 1024 —
-  // their tables take LDS from the band's rows; profiles/r06_roi_chunk_sweep.txt): 128 stays
-  static const int chunk_env = getenv("SW_ROI_SPARSE_CHUNK") ? atoi(getenv("SW_ROI_SPARSE_CHUNK")) : 0;
-  const int chunk_plane = chunk_env > 0 ? chunk_env : SP_CH, chunk_band = chunk_env > 0 ? chunk_env : SP_CH;
-  const size_t plane8 = (size_t)H * W * 32 + sparse_tables_bytes(R, PH, PW, false, chunk_plane);
-  if (!force_cb4 && plane8 <= LDS_MAX && (long)H * W <= 5 * SP_NT) {
+  // ROIs per chunk: SP_CH.  The phase clocks of the band form (99x165 map: 29 % of a workgroup's cycles in chunk set-up, 21 % at the
+  // barrier behind a scan; profiles/r06_roi_phases.txt) suggested larger chunks; measured, they are slower on every map (99x165 / 8000
+  // ROIs: 672 us at 128, 684 at 256, 792 at 512, 1041 at 1024 — their tables take LDS from the band's rows;
+  // profiles/r06_roi_chunk_sweep.txt)
+  const size_t plane8 = (size_t)H * W * 32 + sparse_tables_bytes(R, PH, PW, false, SP_CH);
+  if (plane8 <= LDS_MAX && (long)H * W <= 5 * SP_NT) {
     const int nz = zsplit((C / 8) * nimg);
     return launch_sparse_kernel<IT, 8, false>(dim3(C / 8, nimg, nz), plane8, H, W, C, ld, PH, PW, scale, feat, rois, R, row_scale,
-                                              row_scale_add, out, argmax, H, H, 1, nz, chunk_plane, stream);
+                                              row_scale_add, out, argmax, H, H, 1, nz, SP_CH, stream);
   }
   // row bands: 4 channels per lane (16 B per pixel).  8 channels (32 B per pixel: a third of the rows per band) measured slower on
   // every banded map (99x165 / 8000 ROIs: 956 vs 669 us with 9 vs 3 bands; 125x167: 525 vs 383; 76x114: 245 vs 219) — the bands'
-  // redundant ROI tables and slab fetches outweigh the halved task count; SW_ROI_SPARSE_CB8BAND=1 tries it first (A/B timing)
-  static const bool try_cb8_band = getenv("SW_ROI_SPARSE_CB8BAND") != nullptr;          // development switch
-  const size_t tb = sparse_tables_bytes(R, PH, PW, true, chunk_band);
+  // redundant ROI tables and slab fetches outweigh the halved task count
+  const size_t tb = sparse_tables_bytes(R, PH, PW, true, SP_CH);
   if (PH > 255) return -100;
   const int halo = (H + PH - 1) / PH + 1;
-  for (int cb = (try_cb8_band && !force_cb4) ? 8 : 4; cb >= 4; cb >>= 1) {
-    const int pxb = cb * 4, pxt = cb == 8 ? 5 : 10;
-    if (tb + (size_t)W * pxb * 8 > LDS_MAX) continue;
-    int fit = (int)((LDS_MAX - tb) / ((size_t)W * pxb));
-    if ((long)fit * W > (long)pxt * SP_NT) fit = pxt * SP_NT / W;
-    int S, rows;
-    if (fit >= H) { S = H; rows = H; }                              // the whole map fits: one band
-    else { if (fit - halo < 8) continue; S = fit - halo; rows = fit; }
-    const int n_bands = (H + S - 1) / S;
-    const size_t lds = (size_t)rows * W * pxb + tb;
-    const int nz = zsplit((C / cb) * nimg * n_bands);
-    if ((long)n_bands * nz > 65535) continue;
-    dim3 grid(C / cb, nimg, n_bands * nz);
-    if (cb == 8)
-      return launch_sparse_kernel<IT, 8, true>(grid, lds, H, W, C, ld, PH, PW, scale, feat, rois, R, row_scale, row_scale_add, out, argmax,
-                                               S, rows, n_bands, nz, chunk_band, stream);
-    return launch_sparse_kernel<IT, 4, true>(grid, lds, H, W, C, ld, PH, PW, scale, feat, rois, R, row_scale, row_scale_add, out, argmax,
-                                             S, rows, n_bands, nz, chunk_band, stream);
-  }
-  return -100;
+  constexpr int cb = 4, pxb = 16, pxt = 10;
+  if (tb + (size_t)W * pxb * 8 > LDS_MAX) return -100;
+  int fit = (int)((LDS_MAX - tb) / ((size_t)W * pxb));
+  if ((long)fit * W > (long)pxt * SP_NT) fit = pxt * SP_NT / W;
+  int S, rows;
+  if (fit >= H) { S = H; rows = H; }                                // the whole map fits: one band
+  else { if (fit - halo < 8) return -100; S = fit - halo; rows = fit; }
+  const int n_bands = (H + S - 1) / S;
+  const size_t lds = (size_t)rows * W * pxb + tb;
+  const int nz = zsplit((C / cb) * nimg * n_bands);
+  if ((long)n_bands * nz > 65535) return -100;
+  dim3 grid(C / cb, nimg, n_bands * nz);
+  return launch_sparse_kernel<IT, cb, true>(grid, lds, H, W, C, ld, PH, PW, scale, feat, rois, R, row_scale, row_scale_add, out, argmax,
+                                            S, rows, n_bands, nz, SP_CH, stream);
 }
 
 // prepared-task form (sw_roi_pool_fwd_ws): workspace = [nimg][TK_MAXB][TK_SEG] ints, then [nimg][R * PH] task records of 32 bytes
@@ -1604,52 +1534,31 @@ int launch_tasks_kernel(dim3 grid, size_t lds, int H, int W, int C, long ld, int
 template <typename IT>
 int launch_fwd_tasks(int nimg, int H, int W, int C, long ld, int PH, int PW, float scale, const void* feat, const float* rois, int R,
                      const float* row_scale, float row_scale_add, void* out, void* argmax, void* workspace, hipStream_t stream) {
-  // development switches: SW_ROI_TASKS_CB (4 / 8 channels per lane on banded maps), SW_ROI_TASKS_NT (1024 / 512 threads: one / two
-  // workgroups per CU), SW_ROI_TASKS_HALO (rows of overlap between bands; anything below ceil(H / PH) + 1 sends the tallest windows
-  // to the global-memory loop), SW_ROI_FWD_WGS (workgroup target)
-  static const int env_cb = getenv("SW_ROI_TASKS_CB") ? atoi(getenv("SW_ROI_TASKS_CB")) : 0;
-  static const int env_nt = getenv("SW_ROI_TASKS_NT") ? atoi(getenv("SW_ROI_TASKS_NT")) : 0;
-  static const int env_halo = getenv("SW_ROI_TASKS_HALO") ? atoi(getenv("SW_ROI_TASKS_HALO")) : 0;
-  static const int env_wgs = getenv("SW_ROI_FWD_WGS") ? atoi(getenv("SW_ROI_FWD_WGS")) : 0;
+  constexpr int CB = 4, NT = 1024;                                  // 4 channels per lane, one workgroup per CU
   constexpr size_t LDS_ALL = 160 * 1024 - 1024;                     // the kernel's static LDS + alignment
   int* seg = (int*)workspace;
   RoiGeo* geo = (RoiGeo*)((char*)workspace + tasks_seg_bytes(nimg));
   int* hist = (int*)((char*)geo + tasks_geo_bytes(R));
   u32x4* tasks = (u32x4*)((char*)hist + tasks_hist_bytes(nimg, R));
   const long cap = (long)R * PH;
-  // whole map at 32 B per pixel (8 channels per lane) where it fits, else row bands
-  int cb, nt, S, rows, n_bands;
   if (PW < 3) return -100;                                          // a wave's 64 items then span more records than it has lanes to fetch
-  auto ring_bytes = [&](int nthreads) { return (size_t)(nthreads / 64) * 2 * (size_t)(((62 + PW) / PW + 1) * 32); };   // per-wave record ring
-  const bool plane8 = (size_t)H * W * 32 + ring_bytes(1024) <= LDS_ALL && (long)H * W <= 5 * 1024;
+  const size_t ring = (size_t)(NT / 64) * 2 * (size_t)(((62 + PW) / PW + 1) * 32);   // the waves' record rings
   // maps that fit LDS whole at 8 channels per lane: the sparse kernel's per-chunk work is small there (63x63 / 4000 ROIs: 151 us against
-  // 155 + 18 us of list building), so they stay with it; SW_ROI_TASKS_PLANE=1 sends them here (A/B timing)
-  static const bool env_plane = getenv("SW_ROI_TASKS_PLANE") != nullptr;
-  if (plane8 && (env_cb == 0 || env_cb == 8)) {
-    if (!env_plane) return -100;
-    cb = 8; nt = 1024; S = H; rows = H; n_bands = 1;
-  }
+  // 155 + 18 us of list building), so they stay with it
+  if ((size_t)H * W * 32 + ring <= LDS_ALL && (long)H * W <= 5 * 1024) return -100;
+  // row bands of 16-byte pixels
+  int fit = (int)((LDS_ALL - ring) / ((size_t)W * CB * 4));
+  if ((long)fit * W > 10L * NT) fit = 10 * NT / W;
+  int S, rows, n_bands;
+  if (fit >= H) { S = H; rows = H; n_bands = 1; }
   else {
-    cb = env_cb == 8 ? 8 : env_cb == 2 ? 2 : 4;
-    nt = env_nt == 512 ? 512 : 1024;
-    const size_t budget = (nt == 512 ? LDS_ALL / 2 : LDS_ALL) - ring_bytes(nt);
-    const int pxb = cb * 4, pxt = (cb == 8 ? 5 : cb == 4 ? 10 : 20) * (1024 / nt);
-    int fit = (int)(budget / ((size_t)W * pxb));
-    if ((long)fit * W > (long)pxt * nt) fit = pxt * nt / W;
-    if (fit >= H) { S = H; rows = H; n_bands = 1; }
-    else {
-      const int halo = env_halo > 0 ? env_halo : (H + PH - 1) / PH + 1;
-      if (fit - halo < 4) return -100;
-      n_bands = (H + (fit - halo) - 1) / (fit - halo);
-      static const int env_bands = getenv("SW_ROI_TASKS_BANDS") ? atoi(getenv("SW_ROI_TASKS_BANDS")) : 0;   // development switch: more, overlapping bands
-      if (env_bands > n_bands) n_bands = env_bands;
-      S = (H + n_bands - 1) / n_bands;                              // equal bands
-      n_bands = (H + S - 1) / S;
-      static const bool tight = getenv("SW_ROI_TASKS_TIGHT") != nullptr;           // development switch: rows = S + halo as the sparse kernel
-      rows = tight ? S + halo : fit;                                // all the rows LDS holds: more ROIs lie inside one band
-      if (rows > H) rows = H;
-      if (n_bands > TK_MAXB) return -100;
-    }
+    const int halo = (H + PH - 1) / PH + 1;
+    if (fit - halo < 4) return -100;
+    n_bands = (H + (fit - halo) - 1) / (fit - halo);
+    S = (H + n_bands - 1) / n_bands;                                // equal bands
+    n_bands = (H + S - 1) / S;
+    rows = fit;                                                     // all the rows LDS holds: more ROIs lie inside one band
+    if (n_bands > TK_MAXB) return -100;
   }
   if (nimg * n_bands > 64) return -100;
   const int prep_wgs = (R + TK_PREP_NT - 1) / TK_PREP_NT;
@@ -1658,20 +1567,13 @@ int launch_fwd_tasks(int nimg, int H, int W, int C, long ld, int PH, int PW, flo
   hipLaunchKernelGGL(roi_pool_tasks_kernel, dim3(prep_wgs), dim3(TK_PREP_NT), 0, stream, nimg, PH, R, n_bands, (const RoiGeo*)geo,
                      (const int*)hist, tasks, seg, cap);
   SW_CHECK_LAUNCH();
-  const size_t lds = ((((size_t)rows * W * cb * 4) + 15) & ~(size_t)15) + ring_bytes(nt);
-  const int slabs = (C / cb) * nimg * n_bands;
-  const int target = env_wgs ? env_wgs : (nt == 512 ? 512 : 256);
-  int nz = (target + slabs / 2) / slabs;
+  const size_t lds = ((((size_t)rows * W * CB * 4) + 15) & ~(size_t)15) + ring;
+  const int slabs = (C / CB) * nimg * n_bands;
+  int nz = (256 + slabs / 2) / slabs;                               // 256 workgroups
   nz = nz < 1 ? 1 : nz;
   if ((long)n_bands * nz > 65535) return -6;
-  dim3 grid(C / cb, nimg, n_bands * nz);
-#define SW_TK(CBV, NTV) return launch_tasks_kernel<IT, CBV, NTV>(grid, lds, H, W, C, ld, PH, PW, feat, tasks, seg, cap, out, argmax, S, rows, \
-                                                                 n_bands, nz, stream)
-  if (cb == 8) { if (nt == 512) SW_TK(8, 512); SW_TK(8, 1024); }
-  if (cb == 2) { if (nt == 512) SW_TK(2, 512); SW_TK(2, 1024); }
-  if (nt == 512) SW_TK(4, 512);
-  SW_TK(4, 1024);
-#undef SW_TK
+  dim3 grid(C / CB, nimg, n_bands * nz);
+  return launch_tasks_kernel<IT, CB, NT>(grid, lds, H, W, C, ld, PH, PW, feat, tasks, seg, cap, out, argmax, S, rows, n_bands, nz, stream);
 }
 
 template <typename IT>
@@ -1683,28 +1585,19 @@ int roi_fwd_dispatch(int dtype, int nimg, int H, int W, int C, long ld, int PH, 
   // per lane at 16 waves per CU beat 4 channels at 32 (76x114 map, 4000 ROIs: 393 vs 439 us; 86x115: 560 vs 657 with 8- vs
   // 4-byte slabs), and on maps too large for any two-workgroup slab (125x167, 150x200) the 4-byte slab still beats the
   // ROI-stationary gather kernel below (1368 vs 1479, 1762 vs 2072 us) since the per-task overhead was cut (tools/roi_bench_voc.py)
-  static const bool force_gather = getenv("SW_ROI_FWD_GATHER") != nullptr;    // development switch
   const size_t es = dtype == SW_BF16 ? 2 : 4;
-  if (!force_gather && nimg > 0 && (((uintptr_t)feat) & 15) == 0 && H <= 255 && W <= 255) {      // 8-bit bin tables
+  if (nimg > 0 && (((uintptr_t)feat) & 15) == 0 && H <= 255 && W <= 255) {      // 8-bit bin tables
     int pxb = 0;
     for (int cand = 16; cand >= 4 && !pxb; cand >>= 1)
       if ((C % (cand / (int)es)) == 0 && (size_t)H * W * cand <= 150 * 1024) pxb = cand;
-    static const char* force_pxb = getenv("SW_ROI_FWD_PXB");                      // development switch: 16 / 8 / 4, 0 = gather form
-    if (force_pxb) {
-      const int want = atoi(force_pxb);
-      pxb = (want && (C % (want / (int)es)) == 0 && (size_t)H * W * want <= 150 * 1024) ? want : 0;
-    }
     // row sparse table form (bf16, packed candidates): the whole map at 32 B per pixel (8 channels per lane), else row bands at 16 B
-    // per pixel (4 channels per lane); SW_ROI_FWD_SPARSE=0 keeps the scan forms below (A/B timing)
-    static const char* sparse_sw = getenv("SW_ROI_FWD_SPARSE");                       // development switch
-    if (!(sparse_sw && sparse_sw[0] == '0') && !force_pxb && dtype == SW_BF16 && (C % 8) == 0 && (long)H * W < 65535 && R <= 16384 &&
-        PH <= 8 && PW <= 8) {
+    // per pixel (4 channels per lane)
+    if (dtype == SW_BF16 && (C % 8) == 0 && (long)H * W < 65535 && R <= 16384 && PH <= 8 && PW <= 8) {
       const int rc = launch_fwd_sparse<IT>(nimg, H, W, C, ld, PH, PW, spatial_scale, feat, rois, R, row_scale, row_scale_add, out, argmax, stream);
       if (rc != -100) return rc;                                                   // -100: shape not covered, use the forms below
     }
-    static const bool no_band = getenv("SW_ROI_FWD_NO_BAND") != nullptr;            // development switch
     int bS = 0, brows = 0;
-    if (!no_band && !force_pxb && dtype == SW_BF16 && pxb < 16 && (C % 8) == 0 && (long)H * W < 65535 &&
+    if (dtype == SW_BF16 && pxb < 16 && (C % 8) == 0 && (long)H * W < 65535 &&
         band_geometry(H, W, PH, PW, &bS, &brows))
       return launch_fwd_band<IT>(nimg, H, W, C, ld, PH, PW, spatial_scale, feat, rois, R, row_scale, row_scale_add, out, argmax,
                                  bS, brows, stream);
@@ -1744,15 +1637,12 @@ int roi_bwd_dispatch(int nimg, int H, int W, int C, long ld, int PH, int PW, con
                      int R, const float* row_scale, float row_scale_add, const void* relu_ref, const float* dout_absmax,
                      void* dfeat, float spatial_scale, hipStream_t stream) {
   // fixed-point path: CB in {8, 4} with H*W*CB*8 bytes of LDS; needs max|dout| (device scalar)
-  static const bool float_atomics = getenv("SW_ROI_FLOAT_ATOMICS") != nullptr;    // development switch
   // bf16: a hi/lo pair of 32-bit accumulators (see the kernel) when PH*PW*R terms (every bin of every ROI on one pixel: the worst
-  // case) leave >= 8 bits per word; fp32: one 64-bit word.  SW_ROI_BWD_ACC32: round 2's single 32-bit word (A/B timing only)
-  static const bool acc32_single = getenv("SW_ROI_BWD_ACC32") != nullptr;          // development switch
+  // case) leave >= 8 bits per word; fp32: one 64-bit word
   const bool small_terms = sizeof(T) == 2 && R > 0 && (long)PH * PW * R < (1L << 30) &&
                            (30 - (32 - __builtin_clz((unsigned)(PH * PW * R)))) >= 8;
-  static const bool acc64 = getenv("SW_ROI_BWD_ACC64") != nullptr;                 // development switch: the fp32 form for bf16 too
-  const int accmode = (!small_terms || acc64) ? 0 : (acc32_single ? 1 : 2);
-  const size_t ab = accmode == 1 ? 4 : 8;
+  const int accmode = small_terms ? 2 : 0;
+  constexpr size_t ab = 8;
   int cbx = 8;
   constexpr size_t ACC_BUDGET = 150 * 1024;        // of the CU's 160 KiB: + 8 KiB ROI list + the static reduction scratch
   while (cbx > 4 && ((size_t)H * W * cbx * ab > ACC_BUDGET || (C % cbx) || (C / cbx) * nimg < 256)) cbx >>= 1;
@@ -1760,8 +1650,7 @@ int roi_bwd_dispatch(int nimg, int H, int W, int C, long ld, int PH, int PW, con
   // (2-channel slabs on maps that need >= 3 pixel ranges at 4 channels — half the ranges, fewer ROIs straddling a range boundary and
   // streamed twice — measured slower, round 6: 99x165 / 8000 ROIs 459 -> 486 us, 150x200 398 -> 458: twice the workgroups' fixed work)
   const int nsplit = cbx ? (int)(((size_t)H * W * cbx * ab + ACC_BUDGET - 1) / ACC_BUDGET) : 1;   // pixel ranges per plane
-  if (cbx >= 4 && nsplit <= 16 && dout_absmax != nullptr && (((uintptr_t)dout & 7) == 0) && (((uintptr_t)argmax & 15) == 0) && (ld % 4) == 0 &&
-      !float_atomics) {
+  if (cbx >= 4 && nsplit <= 16 && dout_absmax != nullptr && (((uintptr_t)dout & 7) == 0) && (((uintptr_t)argmax & 15) == 0) && (ld % 4) == 0) {
     const int px_per = (H * W + nsplit - 1) / nsplit;
     const size_t ldsx = (size_t)px_per * cbx * ab + FX_CHUNK * 8;
     dim3 gridx(C / cbx, nimg, nsplit), blockx(1024);
@@ -1774,7 +1663,7 @@ int roi_bwd_dispatch(int nimg, int H, int W, int C, long ld, int PH, int PW, con
       hipLaunchKernelGGL(k, gridx, blockx, ldsx, stream, H, W, C, ld, PH * PW, cbx, (const T*)dout, (const IT*)argmax, rois, R, \
                          row_scale, row_scale_add, dout_absmax, (const T*)relu_ref, (T*)dfeat, spatial_scale);                  \
     }
-    if (accmode == 2) SW_BWD_FX(2) else if (accmode == 1) SW_BWD_FX(1) else SW_BWD_FX(0)
+    if (accmode == 2) SW_BWD_FX(2) else SW_BWD_FX(0)
 #undef SW_BWD_FX
     SW_CHECK_LAUNCH();
     return 0;
@@ -1818,8 +1707,7 @@ extern "C" int sw_roi_pool_fwd_ws(int dtype, int nimg, int H, int W, int C, int 
   const long ld = ld_out > 0 ? ld_out : (long)C * PH * PW;
   if (ld < (long)C * PH * PW) return -5;
   if (dtype != SW_BF16 && dtype != SW_F32) return -1;
-  static const bool no_tasks = getenv("SW_ROI_FWD_TASKS") && getenv("SW_ROI_FWD_TASKS")[0] == '0';      // development switch (A/B timing)
-  if (workspace && !no_tasks && (argmax_bits == 32 || argmax_bits == 16) && tasks_shape_ok(dtype, nimg, H, W, C, PH, PW, R, feat)) {
+  if (workspace && (argmax_bits == 32 || argmax_bits == 16) && tasks_shape_ok(dtype, nimg, H, W, C, PH, PW, R, feat)) {
     if ((((uintptr_t)workspace) & 15) || workspace_bytes < sw_roi_pool_fwd_workspace_bytes(nimg, R, PH, PW)) return -5;
     const int rc = argmax_bits == 32
         ? launch_fwd_tasks<int>(nimg, H, W, C, ld, PH, PW, spatial_scale, feat, rois, R, row_scale, row_scale_add, out, argmax, workspace, stream)
@@ -1870,11 +1758,3 @@ extern "C" int sw_absmax(int dtype, long n, const void* x, float* out, hipStream
   return 0;
 }
 
-#ifdef SW_ROI_PHASES
-extern "C" int sw_debug_roi_phases(unsigned long long* out8, int reset) {
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess && out8) e = hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_roi_phase), 64);
-  if (e == hipSuccess && reset) { unsigned long long z[8] = {}; e = hipMemcpyToSymbol(HIP_SYMBOL(g_roi_phase), z, 64); }
-  return e == hipSuccess ? 0 : -(int)e;
-}
-#endif

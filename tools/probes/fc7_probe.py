@@ -1,5 +1,4 @@
-"""fc7-sized GEMMs (8000 x 4096 x 4096: 2 rounds of 256x256 tiles with only 64 K-steps each) under the tile / loop variants the
-development switches select (run one process per variant: SW_GEMM_V, SW_GEMM_PP are read once)."""
+"""fc7-sized GEMMs (8000 x 4096 x 4096: 2 rounds of 256x256 tiles with only 64 K-steps each) and the cost of each epilogue."""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import sos_wsod_amd.ops as ops
@@ -14,7 +13,7 @@ y = torch.empty(M, N, device=dev, dtype=dt)
 wt = torch.randn(K, N, device=dev).to(dt)
 fwd = t(lambda: ops.gemm(x, w, y, M, N, K, ep=ops.make_epilogue(bias=b, relu=True, out_dtype=dt)))
 dg = t(lambda: ops.gemm(x, w, y, M, N, K, ep=ops.make_epilogue(out_dtype=dt)))
-print(f"V={os.environ.get('SW_GEMM_V','-')} PP={os.environ.get('SW_GEMM_PP','-')} PERSIST={os.environ.get('SW_GEMM_PERSIST','-')}: fc7 fwd (bias+relu) {fwd:.0f} us = {2.0*M*N*K/fwd/1e6:.0f} TF/s; plain bf16 out {dg:.0f} us")
+print(f"fc7 fwd (bias+relu) {fwd:.0f} us = {2.0*M*N*K/fwd/1e6:.0f} TF/s; plain bf16 out {dg:.0f} us")
 for name, ep in [("plain", dict()), ("bias", dict(bias=b)), ("relu", dict(relu=True)), ("bias+relu", dict(bias=b, relu=True)),
                  ("bias+relu+hash-dropout", dict(bias=b, relu=True, drop_hash=(123, 0, 0.5))), ("relu_ref mask", dict(relu_ref=x[:, :N].contiguous() if K >= N else None))]:
     us = t(lambda: ops.gemm(x, w, y, M, N, K, ep=ops.make_epilogue(out_dtype=dt, **ep)))

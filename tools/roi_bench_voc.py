@@ -1,5 +1,4 @@
-"""ROIPool forward / backward at a given map size (env RH, RW, RR; default the VOC-sized 76 x 114 map, 4000 ROIs on 2 images): which
-slab width is faster when the plane exceeds 76 KiB?  SW_ROI_FWD_PXB=16|8|4|0 forces the forward's slab bytes per pixel (0 = gather)."""
+"""ROIPool forward / backward at a given map size (env RH, RW, RR; default the VOC-sized 76 x 114 map, 4000 ROIs on 2 images)."""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import sos_wsod_amd.ops as ops
@@ -19,4 +18,4 @@ def t(fn, n=10):
 tf = t(lambda: ops.roi_pool_fwd(feat, rois, out, arg, 0.125, 7, 7, row_scale=obj, row_scale_add=1.0))
 amax = ops.absmax(dout)
 tb = t(lambda: ops.roi_pool_bwd(dout, arg, rois, dfeat, 7, 7, row_scale=obj, row_scale_add=1.0, relu_ref=feat, dout_absmax=amax, spatial_scale=0.0 if os.environ.get('NOSCALE') else 0.125))
-print(f"{H}x{W} map, {R} ROIs, pxb={os.environ.get('SW_ROI_FWD_PXB', 'auto')}: roi_pool fwd {tf*1e3:.0f} us   bwd {tb*1e3:.0f} us")
+print(f"{H}x{W} map, {R} ROIs: roi_pool fwd {tf*1e3:.0f} us   bwd {tb*1e3:.0f} us")

@@ -1,8 +1,6 @@
-"""ROIPool forward: the prepared-task form (sw_roi_pool_fwd_ws) against the form without workspace, and its development switches.
-    python tools/roi_tasks_forms.py                     # all shapes: no workspace | prepared tasks (default geometry)
-    python tools/roi_tasks_forms.py sweep               # + SW_ROI_TASKS_CB / _NT / _HALO / SW_ROI_FWD_WGS variants on the large maps
-Each variant runs in its own child process (the switches are read once per process); prints the time and checks that values and
-argmax equal the no-workspace form's bit for bit."""
+"""ROIPool forward: the prepared-task form (sw_roi_pool_fwd_ws) against the form without workspace.
+    python tools/roi_tasks_forms.py                     # all shapes: no workspace | prepared tasks
+Each shape runs in its own child process; prints the time and checks that values and argmax equal the no-workspace form's bit for bit."""
 import os, subprocess, sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 SHAPES = [(63, 63, 4000), (76, 114, 4000), (99, 165, 8000), (104, 139, 4000), (125, 167, 4000), (150, 200, 4000), (47, 62, 4000)]
@@ -33,8 +31,7 @@ def one(H, W, R):
         res.append(a.elapsed_time(b) / 20 * 1e3)
     same = torch.equal(out.view(torch.int16), out0.view(torch.int16)) and torch.equal(arg, arg0)
     alg = R * 25088 * 4 + 2 * H * W * C * 2
-    sw = " ".join(f"{k[7:]}={v}" for k, v in os.environ.items() if k.startswith("SW_ROI_"))
-    print(f"{H}x{W} map, {R} ROIs [{sw}]: no workspace {res[0]:7.1f} us | prepared tasks {res[1]:7.1f} us = {alg / res[1] / 1e6 / 8:.3f} of 8 TB/s"
+    print(f"{H}x{W} map, {R} ROIs: no workspace {res[0]:7.1f} us | prepared tasks {res[1]:7.1f} us = {alg / res[1] / 1e6 / 8:.3f} of 8 TB/s"
           f"  {'identical' if same else 'DIFFERENT'}", flush=True)
 
 
@@ -42,11 +39,5 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "one":
         one(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
     else:
-        sweep = len(sys.argv) > 1 and sys.argv[1] == "sweep"
-        variants = [{}]
-        if sweep:
-            variants += [{"SW_ROI_TASKS_CB": "2"}, {"SW_ROI_TASKS_CB": "4"}, {"SW_ROI_TASKS_CB": "8"}, {"SW_ROI_TASKS_CB": "2", "SW_ROI_TASKS_NT": "512"},
-                         {"SW_ROI_TASKS_CB": "2", "SW_ROI_FWD_WGS": "512"}]
         for H, W, R in SHAPES:
-            for v in variants:
-                subprocess.run([sys.executable, os.path.abspath(__file__), "one", str(H), str(W), str(R)], env=dict(os.environ, **v))
+            subprocess.run([sys.executable, os.path.abspath(__file__), "one", str(H), str(W), str(R)])

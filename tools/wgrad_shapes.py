@@ -1,10 +1,10 @@
 """Every conv weight gradient of one backward pass (7 trainable layers x 2 view batches) as the grouped launch + folds, ALONE, at the
 headline (512x512), recipe-mean (832x1109 + 864x1152) and COCO (800x1333) view sizes:   python tools/wgrad_shapes.py
-SW_WGRAD_DIRECT=0 selects the implicit-GEMM path; TS=... lists K-tile targets per item (default: the backbone's own choice)."""
+TS=... lists K-tile targets per item (default: the backbone's own split plan)."""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import sos_wsod_amd.ops as ops
-from sos_wsod_amd.backbone_vgg import _wgrad_grouped_splits, _wgrad_grouped_target, _wgrad_direct_splits
+from sos_wsod_amd.backbone_vgg import _wgrad_grouped_splits, _wgrad_direct_splits
 dt, dev = torch.bfloat16, "cuda"
 
 
@@ -30,10 +30,8 @@ for name, views in [("headline", [(512, 512), (512, 512)]), ("recipe", [(832, 11
             h, w, cin, cout, dil = layers[v][li]
             data.append(((torch.randn(2, h, w, cin, device=dev) * .5).to(dt), (torch.randn(2, h, w, cout, device=dev) * .5).to(dt), dil))
     flops = sum(2.0 * x.numel() * 9 * dy.shape[3] for x, dy, _ in data)
-    shapes = [(x.shape[0] * x.shape[1] * x.shape[2], dy.shape[3], 9 * x.shape[3]) for x, dy, _ in data]
-    targets = [int(v) for v in os.environ["TS"].split(",")] if "TS" in os.environ else [_wgrad_grouped_target(shapes, 64)]
-    if os.environ.get("SW_WGRAD_DIRECT", "1") != "0" and "TS" not in os.environ:
-        targets = [0]                                            # 0: the direct kernel's own split plan (backbone_vgg._wgrad_direct_splits)
+    # 0: the direct kernel's own split plan (backbone_vgg._wgrad_direct_splits)
+    targets = [int(v) for v in os.environ["TS"].split(",")] if "TS" in os.environ else [0]
     plan = _wgrad_direct_splits([(x.shape[0], x.shape[1], x.shape[2], x.shape[3], dy.shape[3], dil) for x, dy, dil in data])
     for T in targets:
         probs, folds, nslabs = [], [], 0
