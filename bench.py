@@ -6,10 +6,14 @@ pseudo-label mining -> 9 losses -> full backward (backbone from plain3 up, FREEZ
 all-reduce when N > 1) -> SGD-momentum update of all 135.8 M trainable parameters.
 "image" = one view, so value = 4 * N * steps / time.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]     (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]     (N > 1: launched by torch.distributed.run, one rank per GPU)
 
-Prints ONE JSON line on rank 0 with the driver's contract plus `roofline` (dominant kernel, timed live with HIP
-events on the launch stream) and `cpu_baseline` (the oracle, timed on this host's cores, rank 0, N == 1 only).
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: build, capture, warm up, time the K steps, write the
+outputs if asked, print `metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype` and the run's configuration.
+--full adds everything else, after the timed steps: the same step issued launch by launch, `roofline` and the other per-kernel figures
+(HIP events on the launch stream), the rank self-checks for N > 1 (`ranks_in_sync`, `rccl_ranks`, `rank_ms_per_step`), and for N == 1
+the other precisions and shapes (--no-fp32-line / --no-extra-shapes skip them) and `cpu_baseline` (the oracle, timed on this host's
+cores; --no-cpu-baseline skips it).
 --dump-outputs DIR: rank 0 writes what the last timed step computed as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
@@ -195,12 +199,15 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline (per-kernel and roofline figures, "
+                         "eager step time, rank self-checks; N == 1: other precisions and shapes, CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (extra key cpu_baseline)")
     ap.add_argument("--images-per-gpu", type=int, default=1,
                     help="images (4-view sets) per GPU per step; BASELINE config #3 = --gpus 8 --images-per-gpu 2")
-    ap.add_argument("--no-fp32-line", action="store_true", help="skip the short fp32 timing (extra key fp32_ms_per_step)")
+    ap.add_argument("--no-fp32-line", action="store_true", help="--full: skip the short fp32 timing (extra key fp32_ms_per_step)")
     ap.add_argument("--no-extra-shapes", action="store_true",
-                    help="skip the short runs of config #3's / #4's / #5's per-GPU shapes (extra keys b2_ms_per_step, coco_ms_per_step, stage3_ms_per_iter)")
+                    help="--full: skip the short runs of config #3's / #4's / #5's per-GPU shapes (extra keys b2_ms_per_step, coco_ms_per_step, stage3_ms_per_iter)")
     ap.add_argument("--graph", type=int, default=None,
                     help="1: replay the step as a captured hipGraph (default for --gpus 1), 0: eager launches (default under DDP)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -291,12 +298,47 @@ def main():
         # loss vector (a static output of the captured step) in place
         dump_outputs(args.dump_outputs, last, model)
         phase(f"outputs of the last timed step written to {args.dump_outputs}")
+    dt_rank = dt
+    if world > 1:                                # `value` uses the MAX over ranks as the contract says
+        t = torch.tensor([dt], device=device, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "images/s (1/2/4/8 MI355X) VGG16+OICR 2000-prop; conv5_3 MFMA-util %",
+            "value": round(4.0 * B * world * args.steps / dt, 3), "unit": "images/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": f"OICR+ training iteration: {4 * B} views/step/GPU ({B} image(s) x 2 scales x h-flip, every view {H}x{W}), "
+                                   f"R={R} proposals/view, K={K}, VGG16 dilated-C5 + ROIPool 7x7 + fc6/fc7 4096 + WSDDN + 4 OICR heads, "
+                                   "fwd+bwd+SGD(momentum, wd)", "views_per_step_per_gpu": 4 * B, "image": "one view",
+                       "oicr_iterations_per_s": round(B * world * args.steps / dt, 3), "parallelism": f"dp{world}"},
+            "backend": (dist.get_backend() if world > 1 else None),
+        }
+
+    def finish(ranks_in_sync=None):
+        if rank == 0:
+            phase("done")
+            sys.stdout.flush()
+            os.write(real_stdout, (json.dumps(out) + "\n").encode())
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+            if ranks_in_sync is False:           # the line above says so; a run whose replicas diverged is not a measurement
+                print(f"[bench] rank {rank}: parameter checksums differ across ranks", file=sys.stderr, flush=True)
+                sys.exit(3)
+
+    if not args.full:
+        finish()
+        return
+    # --full from here on: every figure below is taken AFTER the measured region and changes nothing above
     # per-kernel durations need HIP events between launches: a graph replay has no place for them, and in an eager run they are
     # instrumentation (~0.3 ms of stream time per step) — so the same kernels are timed in a few eager steps AFTER the measured
     # region (same shapes, same data, every rank alike so that the collectives stay in step)
     replays = captures = None
     n_timer_steps = 8
-    eager_ms = dt / args.steps * 1e3
+    eager_ms = dt_rank / args.steps * 1e3
     if graphs is not None or (native is not None and native.use_graph):     # the same step issued launch by launch, for the record
         if graphs is not None:
             replays, captures = graphs.replays, graphs.captures
@@ -332,7 +374,7 @@ def main():
         times["fc6_wgrad"] = ops.TIMER.summary_ms()["fc6_wgrad"]
         ops.TIMER = None
         hd_.__dict__["_fused_opt"] = keep_
-    rank_ms = [dt / args.steps * 1e3]
+    rank_ms = [dt_rank / args.steps * 1e3]
     rccl_ranks = 1
     ranks_in_sync = None
     if world > 1:
@@ -346,16 +388,14 @@ def main():
         dist.all_reduce(lo, op=dist.ReduceOp.MIN); dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         ranks_in_sync = bool((lo == hi).item())
         # self-check of the record: the number of ranks that really took part (an all-reduce of ones over the data-path
-        # communicator) and every rank's own time for the K steps; `value` uses the MAX over ranks as the contract says
+        # communicator) and every rank's own time for the K steps (`value` took the MAX of them above)
         ones = torch.ones(1, device=device)
         dist.all_reduce(ones)
         rccl_ranks = int(round(float(ones.item())))
-        t = torch.tensor([dt], device=device, dtype=torch.float64)
+        t = torch.tensor([dt_rank], device=device, dtype=torch.float64)
         every = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(every, t)
         rank_ms = [float(e.item()) / args.steps * 1e3 for e in every]
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
 
     if rank == 0:
         M = 4 * R * B
@@ -420,16 +460,8 @@ def main():
             return {"mfma_busy_frac": ent[k]["mfma_busy_frac"], "effective_clock_GHz": ent[k]["effective_clock_GHz"],
                     "source": f"profiles/{os.path.basename(busy_path)} (rocprofv3 --pmc, kernel alone)"}
         roofline["mfma_busy_counter"] = busy_of(dom)
-        out = {
-            "metric": "images/s (1/2/4/8 MI355X) VGG16+OICR 2000-prop; conv5_3 MFMA-util %",
-            "value": round(4.0 * B * world * args.steps / dt, 3), "unit": "images/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"OICR+ training iteration: {4 * B} views/step/GPU ({B} image(s) x 2 scales x h-flip, every view {H}x{W}), "
-                                   f"R={R} proposals/view, K={K}, VGG16 dilated-C5 + ROIPool 7x7 + fc6/fc7 4096 + WSDDN + 4 OICR heads, "
-                                   "fwd+bwd+SGD(momentum, wd)", "views_per_step_per_gpu": 4 * B, "image": "one view",
-                       "oicr_iterations_per_s": round(B * world * args.steps / dt, 3), "parallelism": f"dp{world}"},
-            "rccl_ranks": rccl_ranks, "backend": (dist.get_backend() if world > 1 else None), "ranks_in_sync": ranks_in_sync,
+        out.update({
+            "rccl_ranks": rccl_ranks, "ranks_in_sync": ranks_in_sync,
             "rank_ms_per_step": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3)},
             "roofline": roofline,
             # the other two launches of the same GEMM family (`roofline` above is the costliest of the three)
@@ -478,7 +510,7 @@ def main():
                              "instrumented_ms_per_step": round(instrumented_ms, 3)}
                             if replays is not None else
                             {"mode": "eager launches", "instrumented_ms_per_step": round(instrumented_ms, 3)}),
-        }
+        })
         if world == 1 and dtype == torch.bfloat16:
             # the same two kernels ALONE on the maps the recipe / COCO run on (round 6): conv5 at 99x165, ROIPool forward at 99x165 / 8000
             # ROIs and 150x200 / 4000 ROIs (one call = view + flip of one scale), 10-20 launches each, HIP events on the launch stream
@@ -770,15 +802,7 @@ def main():
         phase("extras done; cpu baseline")
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
-        phase("done")
-        sys.stdout.flush()
-        os.write(real_stdout, (json.dumps(out) + "\n").encode())
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-        if ranks_in_sync is False:               # the line above says so; a run whose replicas diverged is not a measurement
-            print(f"[bench] rank {rank}: parameter checksums differ across ranks", file=sys.stderr, flush=True)
-            sys.exit(3)
+    finish(ranks_in_sync)
 
 
 if __name__ == "__main__":

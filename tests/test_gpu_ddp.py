@@ -116,8 +116,9 @@ def test_real_model_two_ranks_at_config3_per_gpu_size(tmp_path, panels):
 
 
 def test_bench_launches_its_own_ranks():
-    """`python bench.py --gpus 2` with no launcher around it prints one line with n_gpus 2 (both ranks on cuda:0 over gloo here)"""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    """`python bench.py --gpus 2 --full` with no launcher around it prints one line with n_gpus 2 (both ranks on cuda:0 over gloo
+    here) and the rank self-checks that --full adds"""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     env = _env()
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
