@@ -418,19 +418,23 @@ __global__ void roi_align_bwd_kernel(int H, int W, int C, int PH, int PW, float 
 // Deterministic backward (round 6).  The f32 atomics above add in arrival order: two runs of one iteration differ in the last bits of
 // the feature gradients, the student drifts, pseudo boxes jitter, position-keyed anchor sampling flips (tests had to allow 6e-2 on the
 // pseudo RPN losses).  Here the SAME contributions are accumulated as 64-bit fixed-point integers — integer addition commutes, so the sum
-// does not depend on the order: contribution v (|v| <= max|gout|: a bin hands out exactly its gradient, weights sum to count) is added as
-// llrint(v * 2^40 / max|gout|); a pixel collects at most R * PH * PW * 2^40 < 2^63 for R < 170 000 ROIs; resolution 2^-40 of the largest
-// gradient against f32's 2^-24.  acc [N][H][W][C] int64, zero-filled by the caller; fx_to_float_kernel turns it into the map (NaN / Inf in
-// gout: absmax reports it, the whole map comes out NaN — the f32 form poisoned the pixels the ROI touched).
-constexpr float FX_ONE = 1099511627776.0f;          // 2^40
+// does not depend on the order: contribution v (|v| <= max|gout| = am: a bin hands out exactly its gradient, weights sum to count) is
+// added as llrint(v * 2^(40 - e)) with am = f * 2^e, f in [0.5, 1) (frexpf): |v * 2^(40 - e)| < 2^40; a pixel collects at most
+// R * PH * PW * 2^40 < 2^63 for R < 170 000 ROIs; resolution 2^-40 of 2^e <= 2 am against f32's 2^-24.  The scale is a power of two
+// applied by ldexpf: exact, no intermediate overflows for any finite am > 0 (2^40 / am overflowed below am ~ 3e-27), and a gradient
+// scaled by 2^k yields the same integers.  acc [N][H][W][C] int64, zero-filled by the caller; fx_to_float_kernel turns it into the map
+// (NaN / Inf in gout: absmax reports it, the whole map comes out NaN — the f32 form poisoned the pixels the ROI touched).
+constexpr int FX_BITS = 40;
 template <typename T>
 __global__ void roi_align_bwd_fx_kernel(int H, int W, int C, int PH, int PW, float scale, int sampling_ratio,
                                         const T* __restrict__ gout, long ld, const float* __restrict__ rois,
                                         const int* __restrict__ sel, int n_sel, const int* __restrict__ n_sel_dev,
                                         const float* __restrict__ absmax, unsigned long long* __restrict__ acc) {
   const float am = absmax[0];
-  if (!(am > 0.f) || !(am <= 3.0e38f)) return;                      // zero gradient: nothing to add; NaN / Inf: the conversion reports it
-  const float S = __fdiv_rn(FX_ONE, am);
+  if (!(am > 0.f) || !__builtin_isfinite(am)) return;               // zero gradient: nothing to add; NaN / Inf: the conversion reports it
+  int e;
+  (void)frexpf(am, &e);
+  const int sh = FX_BITS - e;                                        // v * 2^sh, |v| <= am < 2^e
   const long n = (long)(n_sel_dev ? min(n_sel_dev[0], n_sel) : n_sel) * PH * PW * C;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i % C); long r = i / C;
@@ -440,7 +444,7 @@ __global__ void roi_align_bwd_fx_kernel(int H, int W, int C, int PH, int PW, flo
     const AlignGeom g = align_geom(rois + (long)row * 5, scale, PH, PW, sampling_ratio);
     const float go = Elem<T>::load(gout + (long)row * ld + ((long)c * PH + ph) * PW + pw);
     unsigned long long* d = acc + (long)g.batch * H * W * C + c;
-    auto add = [&](unsigned long long* p, float v) { atomicAdd(p, (unsigned long long)__float2ll_rn(__fmul_rn(v, S))); };
+    auto add = [&](unsigned long long* p, float v) { atomicAdd(p, (unsigned long long)__float2ll_rn(ldexpf(v, sh))); };
     if (g.grid_h < AXIS_MAX && g.grid_w < AXIS_MAX && g.bin_h <= (float)g.grid_h && g.bin_w <= (float)g.grid_w) {
       const AxisW ay = align_axis_weights(g.start_h, ph, g.bin_h, g.grid_h, H);
       const AxisW ax = align_axis_weights(g.start_w, pw, g.bin_w, g.grid_w, W);
@@ -474,8 +478,10 @@ __global__ void roi_align_bwd_fx_kernel(int H, int W, int C, int PH, int PW, flo
 template <typename T>
 __global__ void fx_to_float_kernel(long n, const long long* __restrict__ acc, const float* __restrict__ absmax, T* __restrict__ out) {
   const float am = absmax[0];
-  const bool bad = !(am <= 3.0e38f);                                  // NaN or Inf somewhere in the gradient
-  const double inv = (double)am / (double)FX_ONE;
+  const bool bad = !__builtin_isfinite(am);                           // NaN or Inf somewhere in the gradient
+  int e = 0;
+  if (!bad) (void)frexpf(am, &e);
+  const double inv = ldexp(1.0, e - FX_BITS);                         // the exact inverse of roi_align_bwd_fx_kernel's 2^(40 - e)
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
     Elem<T>::store(out + i, bad ? __uint_as_float(0x7FC00000u) : (float)((double)acc[i] * inv));
 }

@@ -1096,15 +1096,25 @@ int sw_sgd_tile_t_block(int rows, int cols, float* param, const float* grad, flo
                         float mom, float gscale, unsigned short* st0, long ld0, unsigned short* st1, long ld1, const float* hyper,
                         hipStream_t stream);                                 // elementwise.hip
 
-// shapes the fused-SGD epilogue covers: launch_auto's ping-pong form (the only epilogue that implements it), whole 16-byte pieces
+// shapes the fused-SGD epilogue covers: launch_auto's ping-pong form (the only epilogue that implements it), whole 16-byte pieces, and
+// whole 64 x 64 blocks of the tiled update kernel (M % 64, N % 64): the epilogue is bit-identical to sw_sgd_multi's tiled form, which
+// exists for those shapes only, and the peeled tail columns of sw_gemm go through that kernel itself
 static bool sgd_fused_shape_ok(int dtype, int a_kstrided, int b_kstrided, int M, int N, int K) {
   if (dtype != SW_BF16 || a_kstrided) return false;
   (void)b_kstrided;
-  if ((M % 32) || (N % 64) || (K % 64) || K < 1024 || N <= 128) return false;
+  if ((M % 64) || (N % 64) || (K % 64) || K < 1024 || N <= 128) return false;
   return ((long)((M + 255) / 256) * ((N + 255) / 256)) >= 200;
 }
+// what sw_gemm accepts with an sgd_fused epilogue (and no split-K): the whole shape, and under a tail peel also the whole-round part
+static bool sgd_fused_accepts(int dtype, int a_kstrided, int b_kstrided, int M, int N, int K) {
+  if (!sgd_fused_shape_ok(dtype, a_kstrided, b_kstrided, M, N, K)) return false;
+  int r = 0; long sk = 1;
+  if (!peel_geometry(M, N, &r, &sk)) return true;
+  const int N1 = (int)(((N + 255) / 256 - r) * 256);
+  return sgd_fused_shape_ok(dtype, a_kstrided, b_kstrided, M, N1, K) && ((N - N1) % 64) == 0;
+}
 extern "C" int sw_gemm_sgd_fused_supported(int dtype, int a_kstrided, int b_kstrided, int M, int N, int K) {
-  return sgd_fused_shape_ok(dtype, a_kstrided, b_kstrided, M, N, K) ? 1 : 0;
+  return sgd_fused_accepts(dtype, a_kstrided, b_kstrided, M, N, K) ? 1 : 0;
 }
 
 extern "C" int sw_gemm(int dtype, int a_kstrided, int b_kstrided, int M, int N, int K, const void* A, long lda,
@@ -1143,7 +1153,8 @@ extern "C" int sw_gemm(int dtype, int a_kstrided, int b_kstrided, int M, int N, 
       ep1.out_dtype = SW_F32; ep1.drop_scale = 1.f; ep1.ref_scale = 1.f;
       const sw_sgd_tensor* fz = ep ? ep->sgd_fused : nullptr;
       if (fz) {                                     // the whole rounds update the parameter in their epilogue; the tail below goes through C
-        if (!sgd_fused_shape_ok(dtype, a_kstrided, b_kstrided, M, N1, K)) return -5;
+        // everything the tail's update kernel (sw_sgd_tile_t_block) checks is checked here, before the first launch writes a parameter
+        if (!sgd_fused_accepts(dtype, a_kstrided, b_kstrided, M, N, K) || !fz->stage1) return -5;
         ep1.sgd_fused = fz; ep1.sgd_momentum = ep->sgd_momentum; ep1.sgd_grad_scale = ep->sgd_grad_scale;
       }
       int rc = sw_gemm(dtype, a_kstrided, b_kstrided, M, N1, K, A, lda, B, ldb, C, ldc, &ep1, 1, stream);
@@ -1167,7 +1178,7 @@ extern "C" int sw_gemm(int dtype, int a_kstrided, int b_kstrided, int M, int N, 
   }
   if (ep && ep->sgd_fused) {
     const sw_sgd_tensor* fz = ep->sgd_fused;
-    if (!plain || splitk > 1 || !sgd_fused_shape_ok(dtype, a_kstrided, b_kstrided, M, N, K)) return -5;
+    if (!plain || splitk > 1 || !sgd_fused_accepts(dtype, a_kstrided, b_kstrided, M, N, K)) return -5;
     if (fz->stage_kind != 3 || fz->stage_dtype != SW_BF16 || !fz->stage1 || fz->d0 < N || !fz->param || !fz->momentum_buf) return -5;
     if ((ldc % 4) || (fz->ld0 % 4) || (fz->ld1 % 8) || ((((uintptr_t)fz->param) | ((uintptr_t)fz->momentum_buf)) & 15) ||
         (((uintptr_t)fz->stage0) & 7) || (((uintptr_t)fz->stage1) & 15)) return -4;

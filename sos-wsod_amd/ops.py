@@ -1155,8 +1155,8 @@ def roi_align_bwd(gout, rois, sel_i32, dfeat_f32, scale, PH=7, PW=7, sampling_ra
 
 def roi_align_bwd_fx(gout, rois, sel_i32, acc_i64, scale, gout_absmax, PH=7, PW=7, sampling_ratio=0, n_sel_dev=None):
     """the deterministic ROIAlign backward (sw_roi_align_bwd_fx): acc_i64 (N, H, W, C) int64, zero-filled, collects the level's
-    contributions as 64-bit fixed-point integers scaled by 2^40 / gout_absmax (device scalar from ops.absmax(gout)); fx_to_float
-    turns it into the gradient map"""
+    contributions as 64-bit fixed-point integers scaled by 2^(40 - e), where gout_absmax = f * 2^e with
+    f in [0.5, 1) (device scalar from ops.absmax(gout)); fx_to_float turns it into the gradient map"""
     _need_gpu(gout, rois, sel_i32, acc_i64, gout_absmax)
     assert acc_i64.dtype == torch.int64 and acc_i64.is_contiguous()
     n, H, W, C = acc_i64.shape
@@ -1165,7 +1165,7 @@ def roi_align_bwd_fx(gout, rois, sel_i32, acc_i64, scale, gout_absmax, PH=7, PW=
 
 
 def fx_to_float(acc_i64, absmax, out):
-    """out[i] = acc_i64[i] * absmax / 2^40 (sw_fx_to_float); out f32 or bf16, same element count"""
+    """out[i] = acc_i64[i] * 2^(e - 40), absmax = f * 2^e with f in [0.5, 1) (sw_fx_to_float); out f32 or bf16, same element count"""
     _need_gpu(acc_i64, absmax, out)
     assert acc_i64.dtype == torch.int64 and out.numel() == acc_i64.numel() and out.is_contiguous()
     check(lib.sw_fx_to_float(dt(out), acc_i64.numel(), _p(acc_i64), _p(absmax), _p(out), _stream()), "sw_fx_to_float")

@@ -87,7 +87,9 @@ class HipSGD(torch.optim.Optimizer):
         st = self.state[p]
         first = "momentum_buffer" not in st
         if first:
-            st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)
+            # zeros, not empty: should the GEMM never run (or fail), the next step sees first=False and applies momentum * 0 + d_p,
+            # which is torch.optim.SGD's first step, instead of momentum taken from uninitialised memory
+            st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
         entry = dict(param=p, buf=st["momentum_buffer"], lr=group["lr"], weight_decay=group["weight_decay"], first=first,
                      staging=staging, hyper=self._hyper_dev[gi] if self.device_hyper else None)
 

@@ -76,9 +76,10 @@ def test_gemm_splitk_deterministic_slabs(ops, dtype, M, N, K, pad, sk):
     want = a.double().t() @ b.double()
     outs = []
     for _ in range(3):
-        C = torch.full((M, N + pad), float("nan"), device="cuda")[:, :N]
+        base, C = _sentinel_out(M, N, torch.float32, ldc=N + pad)         # NaN-payload fill, one extra row below C
         ops.gemm(a, b, C, M, N, K, a_kstrided=True, b_kstrided=True, splitk=sk)
         assert torch.isfinite(C).all()
+        _assert_no_stray_writes(base, M, N)
         assert ((C.double() - want).abs().max() / want.abs().max()) < (2e-5 if dtype == torch.float32 else 2e-5)
         outs.append(C.clone())
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[1], outs[2])
@@ -94,21 +95,201 @@ def test_gemm_tail_peel_with_column_local_epilogue(ops, plain):
     a = _rand((M, K), 41, dt).cuda(); w = _rand((N, K), 42, dt).cuda()
     want = a.double() @ w.double().t()
     if plain:
-        C = torch.full((M, N), float("nan"), device="cuda")
+        base, C = _sentinel_out(M, N, torch.float32)
         ops.gemm(a, w, C, M, N, K)
         assert ((C.double() - want).abs().max() / want.abs().max()) < 2e-5
+        _assert_no_stray_writes(base, M, N)
         return
     bias = _rand((N,), 43).cuda(); refm = _rand((M, N), 44, dt).cuda()
     amax = torch.zeros(1, device="cuda")
-    C = torch.full((M, N + 8), float("nan"), device="cuda", dtype=dt)[:, :N]
+    base, C = _sentinel_out(M, N, dt, ldc=N + 8)
     ep = ops.make_epilogue(bias=bias, relu_ref=refm, ref_scale=1.0, out_dtype=dt, absmax_out=amax)
     ops.gemm(a, w, C, M, N, K, ep=ep)
+    _assert_no_stray_writes(base, M, N)
     ref = (want + bias.double()) * (refm.double() > 0)
     assert torch.isfinite(C.float()).all()
     assert ((C.double() - ref).abs().max() / ref.abs().max()) < 1e-2          # bf16 output rounding
     assert abs(amax.item() - C.float().abs().max().item()) <= 1e-2 * amax.item()
     for c in (0, 4095, 4096, 4599):                                          # either side of the peel boundary
         assert ((C[:, c].double() - ref[:, c]).abs().max() / ref.abs().max()) < 1e-2
+
+
+# ---- GEMM tile-form edge matrix.  Every case names the form launch_auto (gemm.hip) picks for it; _gemm_form restates that choice
+# (and sw_gemm's tail peel) so that a case whose shape no longer reaches its form fails instead of testing something else:
+#   * N > 128, >= 200 tiles of 256x256 (x splits), K >= 1024: the 256x256 tile; bf16 inputs, A K-contiguous, K % 64 == 0 and one
+#     split -> the ping-pong form "pp256", else the 16-wave form "w16_256"; "+persistent" when its patched grid (8 x 8 tile patches,
+#     launch2) exceeds the CU count (one split only)
+#   * else N <= 64 and one split -> "256x64"
+#   * else bf16, both operands plain or K-strided, <= 256 tiles of 128x128 (x splits), K >= 512 -> "128x128s4" (4-stage ring)
+#   * else "128x128s2"
+# A split-K case names the form of its slab / atomic launch; the peel case (plain f32 C, peel_geometry) its whole-round launch.
+def _gemm_form(bf16, M, N, K, a_ks, b_ks, sk, ncu):
+    cdiv = lambda a, b: (a + b - 1) // b
+    tiles = lambda bm, bn: cdiv(M, bm) * cdiv(N, bn) * sk
+    if N > 128 and tiles(256, 256) >= 200 and K >= 1024:
+        form = "pp256" if (bf16 and not a_ks and K % 64 == 0 and sk == 1) else "w16_256"
+        tm, tn = cdiv(M, 256), cdiv(N, 256)
+        pml = 3
+        if tn < 8:
+            pml = 6 - (tn - 1).bit_length()
+        elif tm < 8:
+            pml = (tm - 1).bit_length()
+        grid = cdiv(tm, 1 << pml) * cdiv(tn, 64 >> pml) * 64
+        return form + ("+persistent" if sk == 1 and ncu % 8 == 0 and grid > ncu else "")
+    if N <= 64 and sk == 1:
+        return "256x64"
+    if bf16 and tiles(128, 128) <= 256 and K >= 512:
+        return "128x128s4"
+    return "128x128s2"
+
+
+def _peel_split(M, N):
+    """peel_geometry (gemm.hip): the whole-round column count N1, or None when sw_gemm does not peel"""
+    tm, tn = (M + 255) // 256, (N + 255) // 256
+    t = tm * tn
+    if not (t >= 512 and t % 256 and t % 256 <= 160):
+        return None
+    for c in range(1, 5):
+        if tn - c >= 2 and (tm * (tn - c)) % 256 == 0:
+            return (tn - c) * 256
+    return None
+
+
+_F32_SENTINEL, _BF16_SENTINEL = 0x7FA5A5A5, 0x7FA5          # quiet NaNs with a payload no kernel writes
+
+
+def _sentinel_out(M, N, dtype, ldc=None):
+    """C as an (M, N) view of an (M + 1, ldc) block filled with sentinel bits: ldc > N (a multiple of 8, 16-byte rows) and one extra row"""
+    ldc = ((N + 15) // 8) * 8 if ldc is None else ldc
+    if dtype == torch.float32:
+        base = torch.full((M + 1, ldc), _F32_SENTINEL, device="cuda", dtype=torch.int32).view(torch.float32)
+    else:
+        base = torch.full((M + 1, ldc), _BF16_SENTINEL, device="cuda", dtype=torch.int16).view(torch.bfloat16)
+    return base, base[:M, :N]
+
+
+def _assert_no_stray_writes(base, M, N):
+    if base.dtype == torch.float32:
+        bits, s = base.view(torch.int32), _F32_SENTINEL
+    else:
+        bits, s = base.view(torch.int16), _BF16_SENTINEL
+    bad_cols = int((bits[:, N:] != s).sum())
+    bad_row = int((bits[M] != s).sum())
+    assert bad_cols == 0 and bad_row == 0, f"writes outside C: {bad_cols} in columns [N, ldc), {bad_row} in row M"
+
+
+def _bf16_ulp(x):
+    _, e = torch.frexp(x.float())
+    return torch.where(x == 0, torch.zeros_like(x, dtype=torch.float64), torch.ldexp(torch.ones_like(x, dtype=torch.float64), e - 8))
+
+
+def _assert_close_to_float64(C, ref):
+    """f32 C: within 2e-5 of max|ref|.  bf16 C: every element within one bf16 ulp of ref rounded to bf16 (plus the f32 accumulation
+    error, 2e-5 of max|ref|, which only matters where the result nearly cancels)"""
+    scale = float(ref.abs().max())
+    assert scale > 0
+    if C.dtype == torch.float32:
+        err = float((C.double() - ref).abs().max())
+        assert err <= 2e-5 * scale, (err, scale)
+        return
+    r16 = ref.to(torch.bfloat16)
+    ulp = torch.maximum(_bf16_ulp(r16), _bf16_ulp(C))
+    over = (C.double() - r16.double()).abs() - (ulp + 2e-5 * scale)
+    n_bad = int((over > 0).sum())
+    assert n_bad == 0, f"{n_bad} bf16 elements beyond 1 ulp of the float64 result (worst excess {float(over.max()):.3g})"
+
+
+# (form, tag, input dtype, M, N, K, mode, out dtype, epilogue, split-K)
+#   mode "nt": A [M][K], B [N][K]; "nn": B [K][N] (K-strided, N % 8 == 0); "tn": A [K][M] too (M % 8 == 0)
+#   epilogue letters: b bias, r ReLU, R relu_ref (bf16 / f32 reference as the input dtype), s residual (bf16 / f32 as the output),
+#   d mask dropout, h hash dropout, w row_scale, x absmax_out, a atomic split-K
+_BF, _F = torch.bfloat16, torch.float32
+_GEMM_EDGE_CASES = [
+    ("pp256", "M%256=1,N%8=7,bf16out", _BF, 3841, 3583, 1024, "nt", _BF, "brx", 1),
+    ("pp256", "M%256=255,Bkstrided,f32out", _BF, 4095, 3336, 1024, "nn", _F, "Rsx", 1),
+    ("pp256+persistent", "N%8=4,bf16out", _BF, 8000, 4100, 1024, "nt", _BF, "bhs", 1),
+    ("w16_256", "Ktail24,M%256=1,f32out", _BF, 3841, 3583, 1048, "nt", _F, "brx", 1),
+    ("w16_256", "f32in,Ktail12,N%8=7,bf16out", _F, 4095, 3327, 1036, "nt", _BF, "Rd", 1),
+    ("w16_256+persistent", "tn,Ktail24,row_scale", _BF, 7944, 4104, 1048, "tn", _F, "w", 1),
+    ("256x64", "M%256=1,N=61,Ktail24,bf16out", _BF, 8193, 61, 1048, "nt", _BF, "brd", 1),
+    ("256x64", "f32in,M%256=255,Ktail4", _F, 1279, 64, 100, "nt", _F, "Rx", 1),
+    ("128x128s4", "M%128=1,N%128=127,Ktail40,bf16out", _BF, 1025, 1151, 1000, "nt", _BF, "bsr", 1),
+    ("128x128s4", "M%128=127,Bkstrided,Ktail8,f32out", _BF, 1151, 1032, 520, "nn", _F, "Rhx", 1),
+    ("128x128s2", "f32in,M%128=1,N%128=127,Ktail12", _F, 1025, 1151, 1036, "nt", _F, "brx", 1),
+    ("128x128s2", "M%128=127,N%128=1,bf16out", _BF, 2047, 2049, 520, "nt", _BF, "bRh", 1),
+    ("128x128s4", "splitk4-fold,bias,relu,N%8=4,bf16out", _BF, 300, 1028, 4096, "nt", _BF, "br", 4),
+    ("128x128s4", "splitk3-fold,tn,Ktail32,residual,row_scale", _BF, 264, 1000, 4000, "tn", _F, "sw", 3),
+    ("128x128s2", "splitk4-atomic,f32in,relu_ref", _F, 200, 263, 2048, "nt", _F, "Ra", 4),
+    ("peel", "M%64=32,pp256+persistent+128x128s4-slabs", _BF, 2016, 16640, 1024, "nt", _F, "", 1),
+]
+
+
+@pytest.mark.parametrize("form,tag,dtype,M,N,K,mode,out,epi,sk", _GEMM_EDGE_CASES, ids=[f"{c[0]}:{c[1]}" for c in _GEMM_EDGE_CASES])
+def test_gemm_tile_form_edges_against_float64(ops, form, tag, dtype, M, N, K, mode, out, epi, sk):
+    """Each tile form of launch_auto at ragged M / N / K, with the epilogues that run on its path: the result against float64, the
+    padding columns [N, ldc) and the row below C untouched, and absmax_out equal to max|C| for f32 output"""
+    a_ks, b_ks = mode == "tn", mode in ("nn", "tn")
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    bf16 = dtype == torch.bfloat16
+    if form == "peel":
+        n1 = _peel_split(M, N)
+        assert epi == "" and out == torch.float32 and n1 is not None and M % 64 == 32
+        assert _gemm_form(bf16, M, n1, K, a_ks, b_ks, 1, ncu) == "pp256+persistent"
+    else:
+        assert _gemm_form(bf16, M, N, K, a_ks, b_ks, sk, ncu) == form
+    g = torch.Generator(device="cuda"); g.manual_seed(M * 7 + N * 3 + K)
+    a = torch.randn(M, K, device="cuda", generator=g).to(dtype)
+    b = torch.randn(N, K, device="cuda", generator=g).to(dtype)
+    ref = a.double() @ b.double().t()
+    A = a.t().contiguous() if a_ks else a                          # tn: A stored [K][M]
+    B = b.t().contiguous() if b_ks else b                          # nn / tn: B stored [K][N]
+    kw = {}
+    if "w" in epi:
+        rs = torch.rand(M, device="cuda", generator=g) + 0.5
+        kw["row_scale"] = rs
+        ref = ref * rs.double()[:, None]
+    if "b" in epi:
+        bias = torch.randn(N, device="cuda", generator=g)
+        kw["bias"] = bias
+        ref = ref + bias.double()
+    if "s" in epi:
+        res = (torch.randn(M, N + 8, device="cuda", generator=g) * 8).to(out)[:, :N]      # a pitch of its own
+        kw["residual"] = res
+        ref = ref + res.double()
+    if "r" in epi:
+        kw["relu"] = True
+        ref = ref.clamp(min=0)
+    if "d" in epi or "h" in epi:
+        keep = torch.empty(M, N, device="cuda", dtype=torch.uint8)
+        ops.dropout_mask(keep, 0xC0FFEE + M, 1234, 0.3)
+        if "d" in epi:
+            kw["drop_mask"] = keep
+        else:
+            kw["drop_hash"] = (0xC0FFEE + M, 1234, 0.3)
+        kw["drop_scale"] = 1.5
+        ref = ref * keep.double() * 1.5
+    if "R" in epi:
+        refm = torch.randn(M, N + 16, device="cuda", generator=g).to(dtype)[:, :N]
+        kw["relu_ref"], kw["ref_scale"] = refm, 0.75
+        ref = ref * (refm.double() > 0) * 0.75
+    amax = None
+    if "x" in epi:
+        amax = torch.zeros(1, device="cuda")
+        kw["absmax_out"] = amax
+    base, C = _sentinel_out(M, N, out)
+    if "a" in epi:
+        kw["atomic"] = True
+        C.zero_()
+    ep = ops.make_epilogue(out_dtype=out, **kw)
+    ops.gemm(A, B, C, M, N, K, a_kstrided=a_ks, b_kstrided=b_ks, ep=ep, splitk=sk)
+    torch.cuda.synchronize()
+    _assert_no_stray_writes(base, M, N)
+    _assert_close_to_float64(C, ref)
+    if amax is not None:
+        if out == torch.float32:
+            assert float(amax) == float(C.abs().max())
+        else:                                                       # (taken before the bf16 rounding of the stored value)
+            assert abs(float(amax) - float(C.float().abs().max())) <= 2 ** -8 * float(amax)
 
 
 # ------------------------------------------------------------------------------------------ conv
@@ -800,13 +981,15 @@ def test_refine_loss_and_grad(ops, R, K):
 
 
 @pytest.mark.parametrize("first", [True, False])
-@pytest.mark.parametrize("M,N,K", [(4096, 25088, 2048), (512, 25600, 1024)])
+@pytest.mark.parametrize("M,N,K", [(4096, 25088, 2048), (512, 25600, 1024), (2016, 16640, 1024), (4128, 25088, 1024)])
 def test_gemm_fused_sgd_epilogue_equals_gemm_then_optimizer(ops, M, N, K, first):
     """sw_epilogue.sgd_fused (round 6): the weight-gradient GEMM applies the SGD update in its epilogue — parameter, momentum buffer, the
     row-major and the transposed bf16 copies come out BIT-identical to the GEMM writing the gradient followed by the optimizer's tiled
     kernel (sw_sgd_multi, stage_kind 3), whole rounds through the epilogue and the peeled tail columns through the tiled kernel
     ((4096, 25088): fc6's shape = 6 rounds + 2 peeled tile columns; (512, 25600): 200 tiles, no peel), first step (no momentum yet) or not,
-    learning rate / weight decay from a device buffer."""
+    learning rate / weight decay from a device buffer, and within f32 rounding of the float64 update.  A shape the support query turns
+    down must make the fused GEMM raise before it writes anything: (2016, 16640) peels its tail onto the tiled kernel, which takes
+    whole 64-row blocks only (M % 64 == 32); (4128, 25088) has no peel and no tiled update of its own to be identical to."""
     dt = torch.bfloat16
     g = torch.Generator(device="cuda"); g.manual_seed(M + N + K + int(first))
     A = (torch.randn(M, K + 64, device="cuda", generator=g) * 0.05).to(dt)[:, :K]          # dZ^T (K-contiguous)
@@ -814,30 +997,83 @@ def test_gemm_fused_sgd_epilogue_equals_gemm_then_optimizer(ops, M, N, K, first)
     w0 = torch.randn(M, N, device="cuda", generator=g) * 0.01
     m0 = torch.randn(M, N, device="cuda", generator=g) * 0.001
     hyper = torch.tensor([1e-3, 5e-4], device="cuda")
-    assert ops.gemm_sgd_fused_supported(dt, M, N, K, False, True)
+    supported = ops.gemm_sgd_fused_supported(dt, M, N, K, False, True)
+    assert supported == (M % 64 == 0), (M, N, K, supported)
 
     def state():
         w, mo = w0.clone(), m0.clone()
         st0 = torch.zeros(M, N + 128, device="cuda", dtype=dt)[:, :N]; st1 = torch.zeros(N, M + 128, device="cuda", dtype=dt)[:, :M]
         staging = dict(kind=3, dtype=dt, stage0=st0, stage1=st1, d0=N, d1=0, d2=0, ld0=st0.stride(0), ld1=st1.stride(0))
         return w, mo, st0, st1, staging
-    # reference: gradient to memory, then the optimizer's kernel
-    w, mo, st0, st1, staging = state()
-    dW = torch.empty(M, N, device="cuda")
-    ops.gemm(A, B, dW, M, N, K, b_kstrided=True)
-    ops.sgd_multi([dict(param=w, grad=dW, buf=mo, lr=123.0, weight_decay=456.0, first=first, staging=staging, hyper=hyper)], 0.9, 1.0)
     # fused
     w2, mo2, st02, st12, staging2 = state()
     dW2 = torch.full((M, N), float("nan"), device="cuda")
     ep = ops.make_epilogue(out_dtype=torch.float32)
     ops.attach_sgd_fused(ep, dict(param=w2, buf=mo2, lr=123.0, weight_decay=456.0, first=first, staging=staging2, hyper=hyper), 0.9, 1.0)
+    if not supported:
+        with pytest.raises(RuntimeError, match="sw_gemm failed"):
+            ops.gemm(A, B, dW2, M, N, K, b_kstrided=True, ep=ep)
+        torch.cuda.synchronize()
+        assert torch.equal(w2, w0) and torch.equal(mo2, m0)
+        assert not st02.view(torch.int16).any() and not st12.view(torch.int16).any()
+        return
     ops.gemm(A, B, dW2, M, N, K, b_kstrided=True, ep=ep)
+    # reference: gradient to memory, then the optimizer's kernel
+    w, mo, st0, st1, staging = state()
+    dW = torch.empty(M, N, device="cuda")
+    ops.gemm(A, B, dW, M, N, K, b_kstrided=True)
+    ops.sgd_multi([dict(param=w, grad=dW, buf=mo, lr=123.0, weight_decay=456.0, first=first, staging=staging, hyper=hyper)], 0.9, 1.0)
     torch.cuda.synchronize()
     assert torch.equal(w2, w) and torch.equal(mo2, mo)
     assert torch.equal(st02.view(torch.int16), st0.view(torch.int16)) and torch.equal(st12.view(torch.int16), st1.view(torch.int16))
     assert not torch.equal(w, w0)
     n_written = int(torch.isfinite(dW2).any(dim=0).sum())                     # only the peeled tail columns carry a gradient
     assert n_written in (0, 512), n_written
+    del dW, w, mo, st0, st1
+    # float64: d = g + wd * w0, m = d (first) or 0.9 m0 + d, w = w0 - lr * m (lr, wd from the device buffer)
+    lr, wd = float(hyper[0]), float(hyper[1])
+    grad = A.double() @ B.double()
+    m64 = grad + wd * w0.double()
+    del grad
+    if not first:
+        m64 += 0.9 * m0.double()
+    scale_m = float(m64.abs().max())
+    assert float((mo2.double() - m64).abs().max()) <= 2e-5 * scale_m
+    w64 = w0.double() - lr * m64
+    del m64
+    assert float((w2.double() - w64).abs().max()) <= 2 ** -23 * float(w64.abs().max()) + lr * 2e-5 * scale_m
+
+
+def test_fused_update_entry_without_its_gemm_leaves_a_first_step(ops):
+    """HipSGD.fused_update_entry creates the momentum buffer before the fused GEMM runs.  When that GEMM is never launched (or fails), the
+    next ordinary step() already counts as a later step (momentum * buffer + d_p): the buffer must hold zeros then, so that the step is
+    torch.optim.SGD's first one — the same bits as a fresh HipSGD's first step, and torch's up to rounding."""
+    from sos_wsod_amd.solver import HipSGD
+    M, N = 128, 256
+    gen = torch.Generator(device="cuda"); gen.manual_seed(5)
+    w_init = torch.randn(M, N, device="cuda", generator=gen)
+    grad = torch.randn(M, N, device="cuda", generator=gen)
+    hp = dict(lr=0.01, momentum=0.9, weight_decay=1e-4)
+
+    def stepped(fused_entry_first):
+        p = torch.nn.Parameter(w_init.clone())
+        st0 = torch.zeros(M, N, device="cuda", dtype=torch.bfloat16); st1 = torch.zeros(N, M, device="cuda", dtype=torch.bfloat16)
+        ops.register_staging(p, 3, torch.bfloat16, stage0=st0, stage1=st1, d0=N, ld0=N, ld1=M)
+        opt = HipSGD([dict(params=[p], **hp)], hp["lr"], momentum=hp["momentum"])
+        if fused_entry_first:
+            junk = torch.full((M, N), 1e30, device="cuda"); del junk      # the block the buffer is carved from holds garbage
+            plan = opt.fused_update_entry(p)
+            assert plan is not None and plan[0]["first"]                  # ... and the GEMM that would consume it never runs
+        p.grad = grad.clone()
+        opt.step()
+        torch.cuda.synchronize()
+        return p.detach().clone(), opt.state[p]["momentum_buffer"].clone(), st0.clone()
+    w_a, m_a, s_a = stepped(True)
+    w_b, m_b, s_b = stepped(False)
+    assert torch.equal(w_a, w_b) and torch.equal(m_a, m_b) and torch.equal(s_a, s_b)
+    q = torch.nn.Parameter(w_init.clone()); q.grad = grad.clone()
+    torch.optim.SGD([q], **hp).step()
+    assert float((w_a - q.detach()).abs().max()) <= 1e-6 * float(q.detach().abs().max())
 
 
 def test_gemm_hash_dropout_equals_mask_dropout(ops):

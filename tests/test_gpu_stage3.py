@@ -137,6 +137,61 @@ def test_roi_align_backward_fixed_point_form_is_reproducible(ops, dtype):
     assert torch.isnan(ops.fx_to_float(acc, an, torch.empty(N, H, W, C, device="cuda"))).all()
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_roi_align_backward_fixed_point_form_at_extreme_scales(ops, dtype):
+    """The fixed-point ROIAlign backward scales by a power of two taken from max|g|'s exponent: a gradient g * 2^k gives the same
+    integers as g, so its map is map(g) * 2^k bit for bit wherever that is a normal float (or zero, or overflows to Inf), and within
+    one fixed-point unit, 2^(e - 40) with max|g * 2^k| = f * 2^e, f in [0.5, 1), below the normal range.  k runs up to a max|g * 2^k|
+    above 3.0e38 (the conversion took that for Inf).  At k = -110 (2^40 / max|g| overflowed f32 there) the small entries of g * 2^k
+    and the kernel's products round to f32's subnormal spacing 2^-149, coarser than the unit 2^-150: there the map must match to
+    2^-20 of max|g * 2^k|.  An Inf in the gradient must not give a finite map."""
+    torch.manual_seed(3)
+    N, C, H, W, R = 2, 16, 25, 38, 600
+    x1 = torch.rand(R) * 240; y1 = torch.rand(R) * 150
+    rois = torch.stack([(torch.arange(R) % N).float(), x1, y1, x1 + 2 + torch.rand(R) * 200, y1 + 2 + torch.rand(R) * 120], 1)
+    scale = 1.0 / 8
+    g = torch.randn(R, C, 7, 7) * torch.exp(torch.randn(R, 1, 1, 1) * 2)           # heavy-tailed magnitudes
+    g = (g * (0.95 / g.abs().max())).to(dtype)            # max|g| = f * 2^0 with f ~ 0.95: g * 2^128 has max|.| in (3.0e38, FLT_MAX]
+    gf = g.float()
+    am0 = float(gf.abs().max())
+    assert 0.9 < am0 < 1.0
+    rc, sel = rois.cuda(), torch.arange(R, dtype=torch.int32).cuda()
+    gref = torch.from_numpy(FO.roi_align_bwd(gf.numpy(), rois.numpy(), scale, (N, C, H, W))).permute(0, 2, 3, 1).double()
+
+    def fx_map(gs):
+        gc = gs.reshape(R, -1).cuda().contiguous()
+        amax = ops.absmax(gc)
+        acc = torch.zeros(N, H, W, C, device="cuda", dtype=torch.int64)
+        ops.roi_align_bwd_fx(gc, rc, sel, acc, scale, amax)
+        return ops.fx_to_float(acc, amax, torch.empty(N, H, W, C, device="cuda", dtype=torch.float32)).cpu()
+    base = fx_map(g)
+    assert torch.isfinite(base).all()
+    assert float((base.double() - gref).abs().max() / gref.abs().max()) < 3e-5
+    tiny = torch.finfo(torch.float32).tiny
+    for k in (-60, 60, 128, -110):
+        gk = (gf.double() * 2.0 ** k).float().to(dtype)
+        amk = float(gk.float().abs().max())
+        assert amk == am0 * 2.0 ** k
+        if k == 128:
+            assert 3.0e38 < amk <= torch.finfo(torch.float32).max
+        got = fx_map(gk)
+        want = (base.double() * 2.0 ** k).float()                 # exact scaling; Inf where it overflows
+        if k == -110:
+            assert float((got.double() - base.double() * 2.0 ** k).abs().max()) <= 2.0 ** -20 * amk
+        else:
+            assert torch.equal(gk.double(), gf.double() * 2.0 ** k)
+            normal = (want == 0) | (want.abs() >= tiny)
+            assert torch.equal(got[normal], want[normal]), k
+            _, e = torch.frexp(torch.tensor(amk))
+            sub = (got[~normal].double() - base[~normal].double() * 2.0 ** k).abs()
+            assert sub.numel() == 0 or float(sub.max()) <= 2.0 ** (int(e) - 40), k
+        fin = torch.isfinite(got)
+        assert bool((fin | (gref.abs() * 2.0 ** k > 0.99 * torch.finfo(torch.float32).max)).all()), k
+        assert float((got[fin].double() * 2.0 ** -k - gref[fin]).abs().max() / gref.abs().max()) < 3e-5, k
+    gi = g.clone(); gi[7, 3, 2, 4] = float("inf")
+    assert not torch.isfinite(fx_map(gi)).any()
+
+
 def test_stem_pool_and_join_kernels_against_torch(ops):
     torch.manual_seed(1)
     # stem: 7x7 s2 p3 + affine + ReLU, then 3x3 s2 p1 max pool (resnet.py:334-359)
