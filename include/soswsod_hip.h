@@ -623,6 +623,21 @@ int sw_rpn_loss(long n, long n_anchors, const float* logits, const float* deltas
                 const float* matched_gt_boxes, const float* weights4, float inv_norm, float* losses2, float* dlogits,
                 float* ddeltas, float* workspace, sw_stream_t stream);
 
+/* Stage-2 pseudo-ground-truth filtering of one split (tools/pgf.py: class_filter :273-292 and the two loops of pgf :221-271 with
+ * contain_cal :209-219; these replace the per-image Python double loop).  Detections are grouped per image in list order (CSR):
+ * image i owns rows [det_off[i], det_off[i + 1]) of boxes [N][4] f64 (16-byte aligned; read as [x, y, w, h] as contain_cal does),
+ * scores [N] f64 and classes [N] i32 in [0, K).  gt_mask [n_img][(K + 31) / 32] and diff_mask [(K + 31) / 32] are class bitmasks.
+ * Stage 3 keeps a detection whose class is in its image's gt_mask; stage 4 keeps the first stage-3 survivor of each class and a
+ * later one iff !(score < t_keep); stage 5 drops a stage-4 survivor i when another stage-4 survivor j of its class has
+ * contain_cal(box_i, box_j) >= t_con, unless use_diff == 0 and the class is in diff_mask.  keep [N] u8: 1 = kept; workspace [N]
+ * u8: used by images of more than SW_PGF_LDS_CAP detections; counts [4] (8-byte aligned, zeroed here): detections before stage 3,
+ * after stage 3, after stage 4, after stage 5.  K <= SW_PGF_MAX_CLASSES.  All f64 arithmetic follows contain_cal's operations. */
+#define SW_PGF_LDS_CAP 256
+#define SW_PGF_MAX_CLASSES 256
+int sw_pgf_keep(int n_img, const int64_t* det_off, const double* boxes, const double* scores, const int32_t* classes, int K,
+                const uint32_t* gt_mask, const uint32_t* diff_mask, double t_keep, double t_con, int use_diff, uint8_t* keep,
+                uint8_t* workspace, long long* counts, sw_stream_t stream);
+
 const char* sw_version(void);
 
 #ifdef __cplusplus

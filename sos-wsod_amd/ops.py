@@ -1341,3 +1341,25 @@ def rpn_loss(logits, deltas, labels_i8, anchors, matched_gt, weights, inv_norm, 
     check(lib.sw_rpn_loss(logits.numel(), anchors.shape[0], _p(logits), _p(deltas), _p(labels_i8), _p(anchors), _p(matched_gt), rw,
                           float(inv_norm), _p(losses2), _p(dlogits), _p(ddeltas), _p(ws), _stream()), "sw_rpn_loss")
     return losses2
+
+
+def pgf_keep(det_off, boxes, scores, classes, K, gt_mask, diff_mask, t_keep, t_con, use_diff):
+    """Stage-2 pseudo-ground-truth filtering of one split (sw_pgf_keep): det_off [n_img + 1] i64, boxes [N, 4] f64, scores [N] f64,
+    classes [N] i32 in [0, K), gt_mask [n_img, (K + 31) // 32] and diff_mask [(K + 31) // 32] i32 class bitmasks, all on the GPU.
+    -> packed u8 [32 + N]: bytes [0, 32) the four int64 counts (before the class filter, after it, after the keep stage, after the
+    containment stage), bytes [32, 32 + N) the keep flags — one tensor, so the host reads everything with one copy."""
+    _need_gpu(det_off, boxes, scores, classes, gt_mask, diff_mask)
+    n_img, n = det_off.numel() - 1, boxes.shape[0]
+    words = (K + 31) // 32
+    assert det_off.dtype == torch.int64 and boxes.dtype == torch.float64 and scores.dtype == torch.float64
+    assert classes.dtype == torch.int32 and gt_mask.dtype == torch.int32 and diff_mask.dtype == torch.int32
+    assert boxes.shape == (n, 4) and scores.shape == (n,) and classes.shape == (n,) and n_img >= 0
+    assert gt_mask.shape == (n_img, words) and diff_mask.shape == (words,)
+    for t in (det_off, boxes, scores, classes, gt_mask, diff_mask):
+        assert t.is_contiguous()
+    packed = torch.empty(32 + n, device=boxes.device, dtype=torch.uint8)
+    workspace = torch.empty(max(n, 1), device=boxes.device, dtype=torch.uint8)
+    check(lib.sw_pgf_keep(n_img, _p(det_off), _p(boxes), _p(scores), _p(classes), int(K), _p(gt_mask), _p(diff_mask),
+                          float(t_keep), float(t_con), int(bool(use_diff)), ctypes.c_void_p(packed.data_ptr() + 32), _p(workspace),
+                          _p(packed), _stream()), "sw_pgf_keep")
+    return packed
