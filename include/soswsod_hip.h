@@ -638,6 +638,25 @@ int sw_pgf_keep(int n_img, const int64_t* det_off, const double* boxes, const do
                 const uint32_t* gt_mask, const uint32_t* diff_mask, double t_keep, double t_con, int use_diff, uint8_t* keep,
                 uint8_t* workspace, long long* counts, sw_stream_t stream);
 
+/* VOC AP and CorLoc of one split at the ten IoU thresholds (evaluation/pascal_voc_evaluation.py: the detection loops, cumulative
+ * sums, precision / recall and voc_ap of voc_eval :295-408 and voc_ap :263-292, and the loop of voc_eval_corloc :411-505; these
+ * replace the 2 x 10 Python walks per class).  Detections of class c are rows [det_off[c], det_off[c + 1]) in rank order
+ * (descending score, ties in line order): det_img [N] i32 image index in [0, n_img), det_box [N][4] f64 [xmin, ymin, xmax, ymax]
+ * (16-byte aligned).  The ground truth of image i and class c is rows [gt_off[i * K + c], gt_off[i * K + c + 1]) of gt_box [G][4]
+ * f64 (16-byte aligned) and gt_diff [G] u8, in annotation order.  npos [K] / npos_im [K] i64: non-difficult objects / images with
+ * at least one, counted over the split's lines.  thr [SW_VOC_THRESHOLDS] f64: IoU thresholds (a match needs IoU > thr);
+ * t11 [11] f64: the 11-point recall levels.  out [3][K][SW_VOC_THRESHOLDS] f64 (8-byte aligned): area AP, 11-point AP, CorLoc
+ * (0 for a class without detections; npos_im == 0 gives NaN, which callers reject).  workspace: sw_voc_eval_workspace_bytes(...)
+ * bytes, 256-byte aligned.  K <= SW_VOC_MAX_CLASSES, N <= SW_VOC_MAX_DETS, G * SW_VOC_THRESHOLDS < 2^31.  The f64 arithmetic
+ * follows numpy's operations and summation order, so each value is bit-identical to the reference run in stable tie order. */
+#define SW_VOC_MAX_CLASSES 256
+#define SW_VOC_THRESHOLDS 10
+#define SW_VOC_MAX_DETS (1LL << 30)
+long long sw_voc_eval_workspace_bytes(int K, int n_img, long long N, long long G);
+int sw_voc_eval(int K, int n_img, long long N, long long G, const int64_t* det_off, const int32_t* det_img, const double* det_box,
+                const int64_t* gt_off, const double* gt_box, const uint8_t* gt_diff, const int64_t* npos, const int64_t* npos_im,
+                const double* thr, const double* t11, double* out, void* workspace, sw_stream_t stream);
+
 const char* sw_version(void);
 
 #ifdef __cplusplus

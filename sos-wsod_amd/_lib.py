@@ -242,6 +242,10 @@ SIGNATURES = {
     # ---- Stage-2 pseudo labels (csrc/pseudo_labels.hip)
     "sw_pgf_keep": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double,
                             ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ---- VOC evaluation (csrc/evaluation.hip)
+    "sw_voc_eval_workspace_bytes": (ctypes.c_longlong, [c_int, c_int, ctypes.c_longlong, ctypes.c_longlong]),
+    "sw_voc_eval": (c_int, [c_int, c_int, ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sw_version": (ctypes.c_char_p, []),
 }
 

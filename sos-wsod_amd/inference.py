@@ -120,6 +120,13 @@ class VOCDetectionWriter:
         self.num_classes = num_classes
         self.reset()
 
+    @classmethod
+    def from_lines(cls, lines):
+        """a writer holding {class: [line]} (e.g. the lines of several ranks, concatenated)"""
+        w = cls(len(lines))
+        w._predictions = {c: list(lines[c]) for c in range(w.num_classes)}
+        return w
+
     def reset(self):
         self._predictions = {c: [] for c in range(self.num_classes)}
 

@@ -1363,3 +1363,31 @@ def pgf_keep(det_off, boxes, scores, classes, K, gt_mask, diff_mask, t_keep, t_c
                           float(t_keep), float(t_con), int(bool(use_diff)), ctypes.c_void_p(packed.data_ptr() + 32), _p(workspace),
                           _p(packed), _stream()), "sw_pgf_keep")
     return packed
+
+
+VOC_THRESHOLDS = 10
+
+
+def voc_eval(det_off, det_img, det_box, gt_off, gt_box, gt_diff, npos, npos_im, thr, t11):
+    """VOC AP and CorLoc of one split at every IoU threshold (sw_voc_eval), all inputs on the GPU: det_off [K + 1] i64 (detections
+    grouped by class in rank order), det_img [N] i32, det_box [N, 4] f64, gt_off [n_img * K + 1] i64 (ground truth per (image,
+    class)), gt_box [G, 4] f64, gt_diff [G] u8, npos [K] / npos_im [K] i64, thr [10] f64 IoU thresholds, t11 [11] f64 recall levels.
+    -> f64 [3, K, 10] on the GPU: area AP, 11-point AP, CorLoc (the caller copies it back once)."""
+    _need_gpu(det_off, det_img, det_box, gt_off, gt_box, gt_diff, npos, npos_im, thr, t11)
+    K, N, G = det_off.numel() - 1, det_img.numel(), gt_diff.numel()
+    n_img = (gt_off.numel() - 1) // K
+    assert det_off.dtype == torch.int64 and det_img.dtype == torch.int32 and det_box.dtype == torch.float64
+    assert gt_off.dtype == torch.int64 and gt_box.dtype == torch.float64 and gt_diff.dtype == torch.uint8
+    assert npos.dtype == torch.int64 and npos_im.dtype == torch.int64 and thr.dtype == torch.float64 and t11.dtype == torch.float64
+    assert det_box.shape == (N, 4) and gt_box.shape == (G, 4) and gt_off.numel() == n_img * K + 1
+    assert npos.shape == (K,) and npos_im.shape == (K,) and thr.shape == (VOC_THRESHOLDS,) and t11.shape == (11,)
+    for t in (det_off, det_img, det_box, gt_off, gt_box, gt_diff, npos, npos_im, thr, t11):
+        assert t.is_contiguous()
+    nbytes = lib.sw_voc_eval_workspace_bytes(K, n_img, N, G)
+    assert nbytes > 0, "sw_voc_eval_workspace_bytes"
+    ws = torch.empty(nbytes + 256, device=det_box.device, dtype=torch.uint8)
+    ws_p = ctypes.c_void_p((ws.data_ptr() + 255) // 256 * 256)
+    out = torch.empty(3, K, VOC_THRESHOLDS, device=det_box.device, dtype=torch.float64)
+    check(lib.sw_voc_eval(K, n_img, N, G, _p(det_off), _p(det_img), _p(det_box), _p(gt_off), _p(gt_box), _p(gt_diff), _p(npos),
+                          _p(npos_im), _p(thr), _p(t11), _p(out), ws_p, _stream()), "sw_voc_eval")
+    return out
