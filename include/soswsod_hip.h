@@ -622,6 +622,28 @@ long sw_rpn_loss_workspace_floats(void);
 int sw_rpn_loss(long n, long n_anchors, const float* logits, const float* deltas, const int8_t* labels, const float* anchors,
                 const float* matched_gt_boxes, const float* weights4, float inv_norm, float* losses2, float* dlogits,
                 float* ddeltas, float* workspace, sw_stream_t stream);
+/* Per-image detector losses for the Stage-3 split (unbias/split_single.py:66-75: one training forward per image, the four losses
+ * summed), for n_img images scored in one batch, each normalised as if it were alone: out [n_img][5] f32 = loss_cls,
+ * loss_box_reg, loss_rpn_cls, loss_rpn_loc and their sum, added left to right (split_single.py:74).
+ *   RPN (proposal_generator/rpn.py:395-425, box_regression.py:229-268): rpn_logits [n_img * n_anchors], rpn_deltas / rpn_matched
+ *   [n_img * n_anchors][4], rpn_labels int8 in {-1, 0, 1}, anchors [n_anchors][4] shared by the images.  loss_rpn_cls = BCE sum /
+ *   rpn_batch_size; loss_rpn_loc = L1 sum / rpn_batch_size (rpn_loss_type 0, smooth_l1 with beta 0) or the mean over the
+ *   4 x (foreground anchors) elements / rpn_batch_size (1, smooth_l1_mean).
+ *   ROI (roi_heads/fast_rcnn.py:73-105 + detectron2 fast_rcnn.py:497-564): roi_logits [roi_rows][ld] = [K + 1 class | 4K box],
+ *   roi_classes [roi_rows], roi_boxes / roi_gt_boxes [roi_rows][4], image i's rows packed after those of images < i, their
+ *   number roi_counts[i] read from device memory, at most max_rows (the sampler's batch_size_per_image; the rows are spread over
+ *   ceil(max_rows / 64) workgroups per image).  loss_cls = sum (1 - p)^gamma CE / rows (gamma 0: cross-entropy, mean over the
+ *   rows, 0 without rows: layers/wrappers.py:26-33); loss_box_reg = class-specific L1 sum / max(rows, 1) (roi_loss_type 0) or the
+ *   mean over the 4 x (foreground rows) elements (1).  An empty foreground set under type 1 gives NaN (torch's empty mean); counts
+ *   that overrun roi_rows or exceed max_rows give NaN, a class outside [0, K] a NaN loss_cls.
+ * Grid (anchor chunks + 1, n_img), partials folded in chunk order: deterministic.  workspace: sw_det_loss_workspace_floats(). */
+long sw_det_loss_workspace_floats(int n_img, long n_anchors, long max_rows);
+int sw_det_loss_per_image(int n_img, long n_anchors, const float* rpn_logits, const float* rpn_deltas, const int8_t* rpn_labels,
+                          const float* anchors, const float* rpn_matched, const float* rpn_weights4, int rpn_batch_size,
+                          int rpn_loss_type, const float* roi_logits, long ld, int K, const int32_t* roi_classes,
+                          const float* roi_boxes, const float* roi_gt_boxes, const int32_t* roi_counts, long roi_rows,
+                          long max_rows, const float* roi_weights4, float gamma, int roi_loss_type, float* out, float* workspace,
+                          sw_stream_t stream);
 
 /* Stage-2 pseudo-ground-truth filtering of one split (tools/pgf.py: class_filter :273-292 and the two loops of pgf :221-271 with
  * contain_cal :209-219; these replace the per-image Python double loop).  Detections are grouped per image in list order (CSR):

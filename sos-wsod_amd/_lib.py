@@ -239,6 +239,10 @@ SIGNATURES = {
     "sw_rpn_loss_workspace_floats": (c_long, []),
     "sw_rpn_loss": (c_int, [c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _F4, c_float, c_void_p, c_void_p,
                             c_void_p, c_void_p, c_void_p]),
+    "sw_det_loss_workspace_floats": (c_long, [c_int, c_long, c_long]),
+    "sw_det_loss_per_image": (c_int, [c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _F4, c_int, c_int, c_void_p,
+                                      c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, _F4, c_float, c_int,
+                                      c_void_p, c_void_p, c_void_p]),
     # ---- Stage-2 pseudo labels (csrc/pseudo_labels.hip)
     "sw_pgf_keep": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double,
                             ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

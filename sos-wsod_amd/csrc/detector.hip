@@ -653,6 +653,127 @@ __global__ __launch_bounds__(256) void stage_weights_multi_kernel(int n, const s
   }
 }
 
+// ---------------------------------------------------------------- per-image detector losses (Stage-3 split scoring)
+// Each image's four training losses as if it were alone in its batch (unbias/split_single.py:66-75 runs one image per forward).
+// Grid (DETLOSS_CHUNK-anchor chunks + DETLOSS_ROWS-row chunks, images): column c < chunks sums one chunk of that image's anchors
+// (BCE over label >= 0, |delta - get_deltas(anchor, gt)|_1 and the count over label == 1); the columns after them each run up to
+// DETLOSS_ROWS of the image's sampled ROI rows (one wave per row: focal / CE term, class-specific L1 box term, foreground count), as
+// many columns as max_rows (the sampler's batch_size_per_image) needs, so an image's 512 rows spread over 8 workgroups instead of
+// queuing behind one.  Partials go to [image][column][4]; det_loss_fold_kernel adds them in column order (deterministic) and
+// applies the per-image normalisers.
+constexpr int DETLOSS_CHUNK = 4096;
+constexpr int DETLOSS_ROWS = 64;
+__global__ __launch_bounds__(256) void det_loss_partial_kernel(
+    long A, int chunks, const float* __restrict__ logits, const float* __restrict__ deltas, const signed char* __restrict__ labels,
+    const float* __restrict__ anchors, const float* __restrict__ matched, float rx, float ry, float rw, float rh,
+    const float* __restrict__ roi_logits, long ld, int K, const int* __restrict__ roi_cls, const float* __restrict__ roi_boxes,
+    const float* __restrict__ roi_gt, const int* __restrict__ roi_counts, long roi_rows, long max_rows, float bx, float by,
+    float bw, float bh, float gamma, float* __restrict__ partial) {
+  __shared__ float red[32];
+  const int img = blockIdx.y, c = blockIdx.x;
+  float* out = partial + ((long)img * gridDim.x + c) * 4;
+  if (c < chunks) {
+    const long lo = (long)c * DETLOSS_CHUNK, hi = lo + DETLOSS_CHUNK < A ? lo + DETLOSS_CHUNK : A;
+    const long base = (long)img * A;
+    float s_obj = 0.f, s_loc = 0.f, s_fg = 0.f;
+    for (long a = lo + threadIdx.x; a < hi; a += blockDim.x) {
+      const long i = base + a;
+      const int lab = labels[i];
+      if (lab >= 0) {
+        const float x = logits[i], y = (float)lab;
+        s_obj += fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));        // as rpn_loss_kernel
+      }
+      if (lab == 1) {
+        const float* an = anchors + a * 4;
+        const float* g = matched + i * 4;
+        const float sw = an[2] - an[0], sh = an[3] - an[1], sx = an[0] + 0.5f * sw, sy = an[1] + 0.5f * sh;
+        const float tw = g[2] - g[0], th = g[3] - g[1], tx = g[0] + 0.5f * tw, ty = g[1] + 0.5f * th;
+        const float t[4] = {rx * (tx - sx) / sw, ry * (ty - sy) / sh, rw * logf(tw / sw), rh * logf(th / sh)};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s_loc += fabsf(deltas[i * 4 + k] - t[k]);
+        s_fg += 1.f;
+      }
+    }
+    s_obj = block_reduce_sum(s_obj, red);
+    __syncthreads();
+    s_loc = block_reduce_sum(s_loc, red);
+    __syncthreads();
+    s_fg = block_reduce_sum(s_fg, red);
+    if (threadIdx.x == 0) { out[0] = s_obj; out[1] = s_loc; out[2] = s_fg; out[3] = 0.f; }
+    return;
+  }
+  // ROI rows of this image: packed back to back, image i's rows start at sum(roi_counts[0..i)); this column takes rows
+  // [r0, r1) of them
+  long off = 0;
+  for (int j = 0; j < img; ++j) off += roi_counts[j];
+  const long n = roi_counts[img];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const float nan = __uint_as_float(0x7FC00000u);
+  if (n < 0 || n > max_rows || off < 0 || off + n > roi_rows) {          // inconsistent counts: no read out of bounds, no number
+    if (threadIdx.x == 0) { out[0] = nan; out[1] = nan; out[2] = nan; out[3] = nan; }
+    return;
+  }
+  const long r0 = (long)(c - chunks) * DETLOSS_ROWS, r1 = r0 + DETLOSS_ROWS < n ? r0 + DETLOSS_ROWS : n;
+  const int C = K + 1;
+  float s_ce = 0.f, s_box = 0.f, s_fg = 0.f;                             // lane 0 of each wave
+  for (long r = off + r0 + w; r < off + r1; r += nw) {
+    const float* x = roi_logits + r * ld;
+    const int t = roi_cls[r];
+    if ((unsigned)t >= (unsigned)C) { s_ce = nan; continue; }            // (focal_loss_kernel's rule for a class outside [0, C))
+    float m = -FLT_MAX;
+    for (int j = lane; j < C; j += 64) m = fmaxf(m, x[j]);
+    m = wave_reduce_max(m);
+    float se = 0.f;
+    for (int j = lane; j < C; j += 64) se += expf(x[j] - m);
+    se = wave_reduce_sum(se);
+    const float ce = m + logf(se) - x[t];
+    s_ce += powf(fmaxf(1.f - expf(-ce), 0.f), gamma) * ce;              // gamma 0: the plain cross-entropy term
+    if (t < K) {
+      const float* s = roi_boxes + r * 4;
+      const float* g = roi_gt + r * 4;
+      const float sw = s[2] - s[0], sh = s[3] - s[1], sx = s[0] + 0.5f * sw, sy = s[1] + 0.5f * sh;
+      const float tw = g[2] - g[0], th = g[3] - g[1], tx = g[0] + 0.5f * tw, ty = g[1] + 0.5f * th;
+      const float tg[4] = {__fdiv_rn(bx * (tx - sx), sw), __fdiv_rn(by * (ty - sy), sh), bw * logf(__fdiv_rn(tw, sw)),
+                           bh * logf(__fdiv_rn(th, sh))};              // as oicr_refine_loss_kernel (box_regression.py:59-62)
+      const float* pd = x + C + 4 * t;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s_box += fabsf(pd[k] - tg[k]);
+      s_fg += 1.f;
+    }
+  }
+  __syncthreads();
+  if (lane == 0) { red[w] = s_ce; red[8 + w] = s_box; red[16 + w] = s_fg; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float a = 0.f, b = 0.f, f = 0.f;
+    for (int k = 0; k < nw; ++k) { a += red[k]; b += red[8 + k]; f += red[16 + k]; }   // wave order: deterministic
+    out[0] = a; out[1] = b; out[2] = f; out[3] = (float)(r1 > r0 ? r1 - r0 : 0);
+  }
+}
+
+// out [image][5] = loss_cls, loss_box_reg, loss_rpn_cls, loss_rpn_loc, their sum (f32, left to right: split_single.py:74)
+//   loss_rpn_cls = BCE sum / B_rpn;  loss_rpn_loc = L1 sum / B_rpn (smooth_l1) or L1 sum / (4 fg anchors) / B_rpn (smooth_l1_mean,
+//   rpn.py:405-425 with box_regression.py:261-268);  loss_cls = CE sum / rows, 0 without rows (layers/wrappers.py:26-33);
+//   loss_box_reg = L1 sum / max(rows, 1) (smooth_l1) or L1 sum / (4 fg rows) (smooth_l1_mean, fast_rcnn.py:534-564).  The mean of
+//   an empty foreground set is 0 / 0 = NaN, as torch's mean of an empty tensor.
+__global__ void det_loss_fold_kernel(int n_img, int chunks, int rchunks, const float* __restrict__ partial, float rpn_bs,
+                                     int rpn_mean, int roi_mean, float* __restrict__ out) {
+  const int img = blockIdx.x * blockDim.x + threadIdx.x;
+  if (img >= n_img) return;
+  const float* p = partial + (long)img * (chunks + rchunks) * 4;
+  float so = 0.f, sl = 0.f, sf = 0.f;
+  for (int c = 0; c < chunks; ++c) { so += p[c * 4]; sl += p[c * 4 + 1]; sf += p[c * 4 + 2]; }
+  float ce = 0.f, box = 0.f, fg = 0.f, rows = 0.f;             // (NaN when the image's counts were inconsistent: stays NaN)
+  for (int c = chunks; c < chunks + rchunks; ++c) { ce += p[c * 4]; box += p[c * 4 + 1]; fg += p[c * 4 + 2]; rows += p[c * 4 + 3]; }
+  const float l_cls = rows == 0.f ? 0.f : ce / rows;
+  const float l_box = roi_mean ? box / (4.f * fg) : box / fmaxf(rows, 1.f);
+  const float l_rpn_cls = so / rpn_bs;
+  const float l_rpn_loc = rpn_mean ? (sl / (4.f * sf)) / rpn_bs : sl / rpn_bs;
+  float* o = out + (long)img * 5;
+  o[0] = l_cls; o[1] = l_box; o[2] = l_rpn_cls; o[3] = l_rpn_loc;
+  o[4] = ((l_cls + l_box) + l_rpn_cls) + l_rpn_loc;
+}
+
 }  // namespace
 
 #define DISPATCH_T(dtype, CALL_BF16, CALL_F32) \
@@ -908,6 +1029,37 @@ extern "C" int sw_rpn_loss(long n, long n_anchors, const float* logits, const fl
                      anchors, matched_gt_boxes, weights4[0], weights4[1], weights4[2], weights4[3], inv_norm, workspace, dlogits,
                      ddeltas);
   hipLaunchKernelGGL(rpn_loss_fold_kernel, dim3(1), dim3(64), 0, stream, blocks, (const float*)workspace, inv_norm, losses2);
+  SW_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" long sw_det_loss_workspace_floats(int n_img, long n_anchors, long max_rows) {
+  if (n_img <= 0 || n_anchors <= 0 || max_rows < 0) return 0;
+  const long rchunks = max_rows > 0 ? (max_rows + DETLOSS_ROWS - 1) / DETLOSS_ROWS : 1;
+  return (long)n_img * ((n_anchors + DETLOSS_CHUNK - 1) / DETLOSS_CHUNK + rchunks) * 4;
+}
+
+extern "C" int sw_det_loss_per_image(int n_img, long n_anchors, const float* rpn_logits, const float* rpn_deltas,
+                                     const int8_t* rpn_labels, const float* anchors, const float* rpn_matched,
+                                     const float* rpn_weights4, int rpn_batch_size, int rpn_loss_type, const float* roi_logits,
+                                     long ld, int K, const int32_t* roi_classes, const float* roi_boxes, const float* roi_gt_boxes,
+                                     const int32_t* roi_counts, long roi_rows, long max_rows, const float* roi_weights4, float gamma,
+                                     int roi_loss_type, float* out, float* workspace, hipStream_t stream) {
+  SW_ENTER();
+  if (n_img <= 0) return 0;
+  if (n_img > 65535 || n_anchors <= 0 || K <= 0 || ld < 5L * K + 1 || rpn_batch_size <= 0 || roi_rows < 0 || max_rows < 0) return -5;
+  if ((unsigned)rpn_loss_type > 1u || (unsigned)roi_loss_type > 1u || !roi_counts) return -5;
+  if (roi_rows > 0 && (!roi_logits || !roi_classes || !roi_boxes || !roi_gt_boxes)) return -5;
+  const long chunks = (n_anchors + DETLOSS_CHUNK - 1) / DETLOSS_CHUNK;
+  const long rchunks = max_rows > 0 ? (max_rows + DETLOSS_ROWS - 1) / DETLOSS_ROWS : 1;
+  if (chunks + rchunks > 2147483647L) return -5;
+  hipLaunchKernelGGL(det_loss_partial_kernel, dim3((unsigned)(chunks + rchunks), (unsigned)n_img), dim3(256), 0, stream, n_anchors,
+                     (int)chunks, rpn_logits, rpn_deltas, (const signed char*)rpn_labels, anchors, rpn_matched, rpn_weights4[0],
+                     rpn_weights4[1], rpn_weights4[2], rpn_weights4[3], roi_logits, ld, K, roi_classes, roi_boxes, roi_gt_boxes,
+                     roi_counts, roi_rows, max_rows, roi_weights4[0], roi_weights4[1], roi_weights4[2], roi_weights4[3], gamma,
+                     workspace);
+  hipLaunchKernelGGL(det_loss_fold_kernel, dim3((n_img + 63) / 64), dim3(64), 0, stream, n_img, (int)chunks, (int)rchunks,
+                     (const float*)workspace, (float)rpn_batch_size, rpn_loss_type, roi_loss_type, out);
   SW_CHECK_LAUNCH();
   return 0;
 }

@@ -1255,9 +1255,12 @@ class PseudoLabRPN(nn.Module):
     """unbias/ubteacher/modeling/proposal_generator/rpn.py:11-57 over detectron2's RPN"""
 
     def __init__(self, sampler, batch_size_per_image=256, positive_fraction=0.25, pre_nms_topk=(2000, 1000), post_nms_topk=(1000, 1000),
-                 nms_thresh=0.7, anchor_sizes=(32, 64, 128, 256, 512), aspect_ratios=(0.5, 1.0, 2.0)):
+                 nms_thresh=0.7, anchor_sizes=(32, 64, 128, 256, 512), aspect_ratios=(0.5, 1.0, 2.0), box_loss_type="smooth_l1"):
         super().__init__()
+        assert box_loss_type in ("smooth_l1", "smooth_l1_mean"), box_loss_type
         self.rpn_head = StandardRPNHead(len(aspect_ratios))
+        self.box_loss_type = box_loss_type
+        self.keep_loss_inputs = False                 # set by TwoStagePseudoLabGeneralizedRCNN.image_losses for its one forward
         self.sampler = sampler
         self.batch_size_per_image, self.positive_fraction = batch_size_per_image, positive_fraction
         self.pre_nms_topk, self.post_nms_topk, self.nms_thresh = pre_nms_topk, post_nms_topk, nms_thresh
@@ -1353,9 +1356,17 @@ class PseudoLabRPN(nn.Module):
         logits, deltas = ops.rpn_unpack(y.detach(), N, A, hw)                              # (N, At), (N, At, 4), anchor order
         losses = {}
         if (self.training and compute_loss) or compute_val_loss:
+            mean = self.box_loss_type == "smooth_l1_mean"
+            if mean and torch.is_grad_enabled() and y.requires_grad:
+                raise NotImplementedError("MODEL.RPN.BBOX_REG_LOSS_TYPE = 'smooth_l1_mean' is implemented for loss evaluation only "
+                                          "(no gradient): run the forward under torch.no_grad()")
             labels, matched = self.label_and_sample_anchors(anchors_all, [g.gt_boxes.tensor.to(dev).float() for g in gt_instances])
             l_cls, l_loc = _RpnLossFn.apply(y, logits, deltas, labels.reshape(-1), anchors_all, matched.reshape(-1, 4), self.bbox_weights,
                                             1.0 / (self.batch_size_per_image * N), (N, A, hw))
+            if mean:                  # box_regression.py:261-268: the mean over the (foreground anchors x 4) elements; 0 / 0 = NaN
+                l_loc = l_loc / (4 * (labels == 1).sum()).to(l_loc.dtype)
+            if self.keep_loss_inputs:
+                self.last_loss_inputs = (logits, deltas, labels, matched, anchors_all)
             losses = {"loss_rpn_cls": l_cls, "loss_rpn_loc": l_loc}
             self.last_labels = labels
         proposals = self.predict_proposals(anchors, logits, deltas, image_sizes)
@@ -1417,8 +1428,16 @@ class FastRCNNFocaltLossOutputLayers(nn.Module):
 class StandardROIHeadsPseudoLab(nn.Module):
     """unbias/ubteacher/modeling/roi_heads/roi_heads.py:377-546"""
 
-    def __init__(self, num_classes, sampler, batch_size_per_image=512, positive_fraction=0.25, proposal_append_gt=True):
+    def __init__(self, num_classes, sampler, batch_size_per_image=512, positive_fraction=0.25, proposal_append_gt=True, loss="FocalLoss",
+                 box_loss_type="smooth_l1"):
         super().__init__()
+        # ROI_HEADS.LOSS (roi_heads.py:106-113, 405-406): "FocalLoss" (gamma 1.5) or detectron2's "CrossEntropy" (mean softmax CE
+        # over the sampled rows) — the focal kernel with gamma 0 is that CE: (1 - p)^0 = 1, and its gradient term in gamma vanishes
+        assert loss in ("FocalLoss", "CrossEntropy"), loss
+        assert box_loss_type in ("smooth_l1", "smooth_l1_mean"), box_loss_type
+        self.loss, self.gamma = loss, (1.5 if loss == "FocalLoss" else 0.0)
+        self.box_loss_type = box_loss_type
+        self.keep_loss_inputs = False                 # set by TwoStagePseudoLabGeneralizedRCNN.image_losses for its one forward
         self.box_head = FastRCNNConvFCHead()
         self.box_predictor = FastRCNNFocaltLossOutputLayers(1024, num_classes)
         self.num_classes, self.sampler = num_classes, sampler
@@ -1461,6 +1480,8 @@ class StandardROIHeadsPseudoLab(nn.Module):
             SPECULATE.expect(cnt, got)
         else:
             got = cnt.tolist() if need else None
+        if self.keep_loss_inputs:
+            self.last_counts = cnt                   # each image's sampled-row count, on the device (min(B, candidates) without gt)
         out = []
         for i, p in enumerate(proposals):
             n = int(got[i]) if got is not None else min(B, len(p))
@@ -1491,10 +1512,18 @@ class StandardROIHeadsPseudoLab(nn.Module):
         K = self.num_classes
         if (self.training and compute_loss) or compute_val_loss:
             self.last_sampled, self.last_logits = proposals, logits
+            mean = self.box_loss_type == "smooth_l1_mean"
+            if mean and torch.is_grad_enabled() and logits.requires_grad:
+                raise NotImplementedError("MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE = 'smooth_l1_mean' is implemented for loss evaluation "
+                                          "only (no gradient): run the forward under torch.no_grad()")
             R = logits.shape[0]
             if R == 0:
                 z = 0.0 * logits.sum()
-                return proposals, {"loss_cls": z, "loss_box_reg": z}
+                if self.keep_loss_inputs:
+                    self.last_loss_inputs = (logits, torch.empty(0, dtype=torch.int32, device=logits.device),
+                                             torch.empty(0, 4, device=logits.device),
+                                             torch.zeros(len(proposals), dtype=torch.int32, device=logits.device))
+                return proposals, {"loss_cls": z, "loss_box_reg": z / 0.0 if mean else z}
             dense = [getattr(p, "_sw_dense", None) for p in proposals]
             B = self.batch_size_per_image
             if all(d is not None and d[0] is dense[0][0] and d[3] == B for d in dense) and dense[0][0].shape[1] == len(proposals):
@@ -1503,7 +1532,11 @@ class StandardROIHeadsPseudoLab(nn.Module):
             else:
                 boxes2 = torch.cat([p.proposal_boxes.tensor for p in proposals] + [p.gt_boxes.tensor for p in proposals]).contiguous()
                 gtc = torch.cat([p.gt_classes for p in proposals]).to(torch.int32).contiguous()
-            l_cls, l_box = _RoiLossFn.apply(logits, K, gtc, boxes2, self.box_predictor.bbox_weights, 1.5)
+            l_cls, l_box = _RoiLossFn.apply(logits, K, gtc, boxes2, self.box_predictor.bbox_weights, self.gamma)
+            if mean:                  # fast_rcnn.py:534-564: the mean over the (foreground rows x 4) elements, not / R; 0 / 0 = NaN
+                l_box = l_box * R / (4 * ((gtc >= 0) & (gtc < K)).sum()).to(l_box.dtype)
+            if self.keep_loss_inputs:
+                self.last_loss_inputs = (logits, gtc, boxes2, self.last_counts)
             return proposals, {"loss_cls": l_cls, "loss_box_reg": l_box}
         # inference form (fast_rcnn.py:44-160): softmax, decode, clip, score > 0.05, per-class NMS 0.5, top 100
         pred, off = [], 0
@@ -1535,6 +1568,25 @@ class StandardROIHeadsPseudoLab(nn.Module):
         return pred, logits
 
 
+def _loss_kwargs(M):
+    """The loss-selection keys of a detector config -> (RPN kwargs, ROI-head kwargs): ROI_HEADS.LOSS "FocalLoss" / "CrossEntropy"
+    (code_release/voc_baseline.yaml, voc_split.yaml); RPN. and ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE "smooth_l1" / "smooth_l1_mean" (the
+    split configs; without gradient only: the heads raise NotImplementedError on a forward that would need its gradient).  Anything
+    else is refused."""
+    def get(node, key, default):
+        return node.get(key, default) if hasattr(node, "get") else default
+    R, H, B = get(M, "RPN", {}), get(M, "ROI_HEADS", {}), get(M, "ROI_BOX_HEAD", {})
+    loss = get(H, "LOSS", "FocalLoss")
+    assert loss in ("FocalLoss", "CrossEntropy"), \
+        f"MODEL.ROI_HEADS.LOSS = {loss!r} is not implemented by this detector (implemented: 'FocalLoss', 'CrossEntropy')"
+    types = {}
+    for key, node in (("RPN", R), ("ROI_BOX_HEAD", B)):
+        got = types[key] = get(node, "BBOX_REG_LOSS_TYPE", "smooth_l1")
+        assert got in ("smooth_l1", "smooth_l1_mean"), \
+            f"MODEL.{key}.BBOX_REG_LOSS_TYPE = {got!r} is not implemented by this detector (implemented: 'smooth_l1', 'smooth_l1_mean')"
+    return dict(box_loss_type=types["RPN"]), dict(loss=loss, box_loss_type=types["ROI_BOX_HEAD"])
+
+
 @META_ARCH_REGISTRY.register()
 class TwoStagePseudoLabGeneralizedRCNN(nn.Module):
     """unbias/ubteacher/modeling/meta_arch/rcnn.py:8-107.  `TwoStagePseudoLabGeneralizedRCNN(cfg)` (the registry call of
@@ -1550,13 +1602,15 @@ class TwoStagePseudoLabGeneralizedRCNN(nn.Module):
             assert M.BACKBONE.get("NAME", "build_resnet_fpn_backbone") == "build_resnet_fpn_backbone"
             assert M.get("PROPOSAL_GENERATOR", {}).get("NAME", "PseudoLabRPN") == "PseudoLabRPN"
             assert M.ROI_HEADS.get("NAME", "StandardROIHeadsPseudoLab") == "StandardROIHeadsPseudoLab"
-            assert M.ROI_HEADS.get("LOSS", "FocalLoss") == "FocalLoss" and M.get("RPN", {}).get("LOSS", "CrossEntropy") == "CrossEntropy"
+            assert M.get("RPN", {}).get("LOSS", "CrossEntropy") == "CrossEntropy"          # (ROI_HEADS.LOSS: _loss_kwargs)
             num_classes, freeze_at = M.ROI_HEADS.NUM_CLASSES, M.BACKBONE.get("FREEZE_AT", 2)
             pixel_mean, pixel_std = M.PIXEL_MEAN, M.PIXEL_STD
             dt_name = M.get("AMD", {}).get("COMPUTE_DTYPE", "fp32")
             compute_dtype = torch.bfloat16 if dt_name == "bf16" else torch.float32
             sampler = Sampler(int(cfg.get("SEED", 0)) if int(cfg.get("SEED", 0)) >= 0 else 0)
             rpn_kw, roi_kw, pred_kw = self._cfg_kwargs(M, cfg.get("TEST", {}))
+            rpn_loss_kw, roi_loss_kw = _loss_kwargs(M)
+            rpn_kw = dict(rpn_kw, **rpn_loss_kw); roi_kw = dict(roi_kw, **roi_loss_kw)
         else:
             rpn_kw, roi_kw, pred_kw = {}, {}, {}
         sampler = sampler if sampler is not None else Sampler()
@@ -1591,7 +1645,7 @@ class TwoStagePseudoLabGeneralizedRCNN(nn.Module):
         pred_kw = dict(test_score_thresh=get(H, "SCORE_THRESH_TEST", 0.05), test_nms_thresh=get(H, "NMS_THRESH_TEST", 0.5),
                        test_topk_per_image=get(T, "DETECTIONS_PER_IMAGE", 100))
         fixed = [(get(R, "IOU_THRESHOLDS", [0.3, 0.7]), [0.3, 0.7], "RPN.IOU_THRESHOLDS"), (get(R, "IOU_LABELS", [0, -1, 1]), [0, -1, 1], "RPN.IOU_LABELS"),
-                 (get(R, "SMOOTH_L1_BETA", 0.0), 0.0, "RPN.SMOOTH_L1_BETA"), (get(R, "BBOX_REG_LOSS_TYPE", "smooth_l1"), "smooth_l1", "RPN.BBOX_REG_LOSS_TYPE"),
+                 (get(R, "SMOOTH_L1_BETA", 0.0), 0.0, "RPN.SMOOTH_L1_BETA"),
                  (tuple(get(R, "BBOX_REG_WEIGHTS", (1.0, 1.0, 1.0, 1.0))), (1.0, 1.0, 1.0, 1.0), "RPN.BBOX_REG_WEIGHTS"),
                  (get(R, "LOSS_WEIGHT", 1.0), 1.0, "RPN.LOSS_WEIGHT"), (get(R, "BBOX_REG_LOSS_WEIGHT", 1.0), 1.0, "RPN.BBOX_REG_LOSS_WEIGHT"),
                  (get(R, "BOUNDARY_THRESH", -1), -1, "RPN.BOUNDARY_THRESH"),
@@ -1599,7 +1653,6 @@ class TwoStagePseudoLabGeneralizedRCNN(nn.Module):
                  (get(B, "FC_DIM", 1024), 1024, "ROI_BOX_HEAD.FC_DIM"), (get(B, "NUM_FC", 2), 2, "ROI_BOX_HEAD.NUM_FC"), (get(B, "NUM_CONV", 0), 0, "ROI_BOX_HEAD.NUM_CONV"),
                  (get(B, "POOLER_RESOLUTION", 7), 7, "ROI_BOX_HEAD.POOLER_RESOLUTION"), (get(B, "POOLER_SAMPLING_RATIO", 0), 0, "ROI_BOX_HEAD.POOLER_SAMPLING_RATIO"),
                  (get(B, "POOLER_TYPE", "ROIAlignV2"), "ROIAlignV2", "ROI_BOX_HEAD.POOLER_TYPE"), (get(B, "SMOOTH_L1_BETA", 0.0), 0.0, "ROI_BOX_HEAD.SMOOTH_L1_BETA"),
-                 (get(B, "BBOX_REG_LOSS_TYPE", "smooth_l1"), "smooth_l1", "ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE"),
                  (tuple(get(B, "BBOX_REG_WEIGHTS", (10.0, 10.0, 5.0, 5.0))), (10.0, 10.0, 5.0, 5.0), "ROI_BOX_HEAD.BBOX_REG_WEIGHTS"),
                  (get(B, "CLS_AGNOSTIC_BBOX_REG", False), False, "ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG"), (get(B, "TRAIN_ON_PRED_BOXES", False), False, "ROI_BOX_HEAD.TRAIN_ON_PRED_BOXES")]
         for got, want, name in fixed:
@@ -1737,6 +1790,30 @@ class TwoStagePseudoLabGeneralizedRCNN(nn.Module):
             losses = dict(det_losses); losses.update(rpn_losses)
             return losses, [], [], None
         raise ValueError(branch)
+
+    @torch.no_grad()
+    def image_losses(self, batched_inputs):
+        """Each image's four training losses as if it were alone in its batch (unbias/split_single.py:66-75 scores one image per
+        forward) -> (N, 5) f32 on the device: loss_cls, loss_box_reg, loss_rpn_cls, loss_rpn_loc, their sum (ops.det_loss_per_image).
+        The training-mode forward of the "supervised" branch (train-mode RPN top-k, label sampling, proposal_append_gt) without
+        gradient; the model must be in training mode."""
+        if not self.training:
+            raise ValueError("image_losses: the model must be in training mode (the reference scores with the training forward)")
+        if SPECULATE is not None:
+            raise ValueError("image_losses: not inside a Speculation ledger (its padded rows would not match the sampled counts)")
+        rpn, roi = self.proposal_generator, self.roi_heads
+        rpn.keep_loss_inputs = roi.keep_loss_inputs = True
+        try:
+            self.forward(batched_inputs, branch="supervised")
+            logits, deltas, labels, matched, anchors = rpn.__dict__.pop("last_loss_inputs")
+            lg, gtc, boxes2, cnt = roi.__dict__.pop("last_loss_inputs")
+            roi.__dict__.pop("last_counts", None)
+        finally:
+            rpn.keep_loss_inputs = roi.keep_loss_inputs = False
+        R = lg.shape[0]
+        return ops.det_loss_per_image(logits, deltas, labels, anchors, matched, rpn.bbox_weights, rpn.batch_size_per_image,
+                                      rpn.box_loss_type, lg, roi.num_classes, gtc, boxes2[:R], boxes2[R:], cnt,
+                                      roi.batch_size_per_image, roi.box_predictor.bbox_weights, roi.gamma, roi.box_loss_type)
 
     @torch.no_grad()
     def inference(self, batched_inputs, do_postprocess=True):

@@ -1343,6 +1343,41 @@ def rpn_loss(logits, deltas, labels_i8, anchors, matched_gt, weights, inv_norm, 
     return losses2
 
 
+DET_LOSS_TYPES = {"smooth_l1": 0, "smooth_l1_mean": 1}
+
+
+def det_loss_per_image(rpn_logits, rpn_deltas, rpn_labels_i8, anchors, rpn_matched, rpn_weights, rpn_batch_size, rpn_loss_type,
+                       roi_logits, K, roi_classes_i32, roi_boxes, roi_gt_boxes, roi_counts_i32, roi_batch_size, roi_weights, gamma,
+                       roi_loss_type):
+    """Each image's four detector losses as if it were alone in its batch (sw_det_loss_per_image): rpn_logits (N, A), rpn_deltas /
+    rpn_matched (N, A, 4), rpn_labels int8 (N, A), anchors (A, 4); roi_logits (R, >= 5K+1) packed [cls | box], roi_classes (R,),
+    roi_boxes / roi_gt_boxes (R, 4), image i's rows after those of images < i, roi_counts (N,) int32 on the device (no host read),
+    each <= roi_batch_size (the ROI sampler's batch_size_per_image; a larger count gives NaN).
+    Loss types: "smooth_l1" / "smooth_l1_mean"; gamma 0 = cross-entropy.  -> (N, 5) f32: loss_cls, loss_box_reg, loss_rpn_cls,
+    loss_rpn_loc, their sum."""
+    _need_gpu(rpn_logits, rpn_deltas, rpn_labels_i8, anchors, rpn_matched, roi_logits, roi_classes_i32, roi_boxes, roi_gt_boxes,
+              roi_counts_i32)
+    N, A = rpn_logits.shape
+    R = roi_logits.shape[0]
+    assert rpn_logits.dtype == torch.float32 and rpn_deltas.dtype == torch.float32 and rpn_matched.dtype == torch.float32
+    assert rpn_labels_i8.dtype == torch.int8 and anchors.dtype == torch.float32 and roi_logits.dtype == torch.float32
+    assert roi_classes_i32.dtype == torch.int32 and roi_counts_i32.dtype == torch.int32
+    assert rpn_deltas.shape == (N, A, 4) and rpn_matched.shape == (N, A, 4) and rpn_labels_i8.shape == (N, A) and anchors.shape == (A, 4)
+    assert roi_logits.dim() == 2 and roi_logits.shape[1] >= 5 * K + 1 and roi_logits.stride(1) == 1
+    assert roi_classes_i32.shape == (R,) and roi_boxes.shape == (R, 4) and roi_gt_boxes.shape == (R, 4) and roi_counts_i32.shape == (N,)
+    for t in (rpn_logits, rpn_deltas, rpn_labels_i8, anchors, rpn_matched, roi_classes_i32, roi_boxes, roi_gt_boxes, roi_counts_i32):
+        assert t.is_contiguous()
+    out = torch.empty(N, 5, device=rpn_logits.device, dtype=torch.float32)
+    ws = torch.empty(max(int(lib.sw_det_loss_workspace_floats(N, A, int(roi_batch_size))), 1), device=rpn_logits.device,
+                     dtype=torch.float32)
+    rw = (ctypes.c_float * 4)(*[float(v) for v in rpn_weights]); bw = (ctypes.c_float * 4)(*[float(v) for v in roi_weights])
+    check(lib.sw_det_loss_per_image(N, A, _p(rpn_logits), _p(rpn_deltas), _p(rpn_labels_i8), _p(anchors), _p(rpn_matched), rw,
+                                    int(rpn_batch_size), DET_LOSS_TYPES[rpn_loss_type], _p(roi_logits), roi_logits.stride(0), int(K),
+                                    _p(roi_classes_i32), _p(roi_boxes), _p(roi_gt_boxes), _p(roi_counts_i32), R, int(roi_batch_size), bw, float(gamma),
+                                    DET_LOSS_TYPES[roi_loss_type], _p(out), _p(ws), _stream()), "sw_det_loss_per_image")
+    return out
+
+
 def pgf_keep(det_off, boxes, scores, classes, K, gt_mask, diff_mask, t_keep, t_con, use_diff):
     """Stage-2 pseudo-ground-truth filtering of one split (sw_pgf_keep): det_off [n_img + 1] i64, boxes [N, 4] f64, scores [N] f64,
     classes [N] i32 in [0, K), gt_mask [n_img, (K + 31) // 32] and diff_mask [(K + 31) // 32] i32 class bitmasks, all on the GPU.
