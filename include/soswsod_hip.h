@@ -679,6 +679,57 @@ int sw_voc_eval(int K, int n_img, long long N, long long G, const int64_t* det_o
                 const int64_t* gt_off, const double* gt_box, const uint8_t* gt_diff, const int64_t* npos, const int64_t* npos_im,
                 const double* thr, const double* t11, double* out, void* workspace, sw_stream_t stream);
 
+/* Stage-3 strong augmentation of a planar u8 [3][H][W] image, every pixel operation bit-identical to Pillow's (replaces
+ * build_strong_augmentation, unbias/ubteacher/data/detection_utils.py:9-46, applied by DatasetMapperTwoCropSeparate.__call__,
+ * unbias/ubteacher/data/dataset_mapper.py:141-149; the blur is unbias/ubteacher/data/transforms/augmentation_impl.py GaussianBlur):
+ *   colour jitter   order[s] = the op of slot s (SW_AUG_*; -1 = empty slot), applied s = 0..3.  brightness / contrast / saturation
+ *                   are ImageEnhance blends `u8(clip(d + f * (x - d)))` in float32 with d = 0 / int(mean(L) + 0.5) of the image at
+ *                   that point / L of the pixel, f = factor[op]; hue is convert("HSV"), H += hue_shift (0..255, modulo 256),
+ *                   convert("RGB") with Pillow's float / double widths;
+ *   grayscale       convert("L") replicated to three channels: (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16;
+ *   blur            ImageFilter.GaussianBlur: three box passes along x, then three along y, each rounding to u8, with the integer
+ *                   weights of sw_gaussian_blur_weights (blur_r < 0: no blur);
+ *   erasing         rect[e] = (top, left, h, w), h = 0: none; e = 0..2 in turn, a later rectangle overwrites an earlier one.  Each
+ *                   sample is byte(255 * n) truncated toward zero and wrapped modulo 256 (RandomErasing(value="random") between
+ *                   ToTensor and ToPILImage), n ~ N(0, 1) from splitmix64 over (seed, key, e * 4 + channel, (y - top) << 32 |
+ *                   (x - left)) and Box-Muller: reproducible, independent of launch geometry.  Pixels outside pass through.
+ * The image is always read as R, G, B planes, as the reference's Image.fromarray(..., "RGB") does whatever INPUT.FORMAT says. */
+#define SW_AUG_BRIGHTNESS 0
+#define SW_AUG_CONTRAST 1
+#define SW_AUG_SATURATION 2
+#define SW_AUG_HUE 3
+typedef struct sw_aug_recipe {
+  uint64_t seed, key;
+  int32_t order[4];
+  float factor[4];            /* by op code; [SW_AUG_HUE] is not read (hue_shift is) */
+  int32_t hue_shift;
+  int32_t grayscale;
+  int32_t blur_r;
+  uint32_t blur_ww, blur_fw;
+  int32_t rect[3][4];
+  int32_t pad_;
+} sw_aug_recipe;
+/* one image of a batch: tmp = 3 * H * W bytes (read only when the recipe blurs), lsum = one u64 (only with contrast); both lie in
+ * a workspace of sw_strong_aug_workspace_bytes(H, W) bytes per image */
+typedef struct sw_aug_item {
+  const uint8_t* in; uint8_t* out; uint8_t* tmp; uint64_t* lsum;
+  int32_t H, W;
+  sw_aug_recipe recipe;
+} sw_aug_item;
+#define SW_AUG_STAGE_CONTRAST 1 /* some image's recipe has contrast */
+#define SW_AUG_STAGE_BLUR 2     /* some image's recipe blurs */
+#define SW_AUG_STAGE_POINT 4    /* some image's recipe does not blur */
+/* HOST arithmetic, no GPU work: sigma -> radius r and the 24-bit fixed-point weights of one box pass (Pillow's
+ * _gaussian_blur_radius and ImagingLineBoxBlur8's ww, both in float32).  -1: sigma <= 0; -6: 3 * (r + 1) > 9 (sigma >~ 3.4). */
+int sw_gaussian_blur_weights(float sigma, int32_t* r, uint32_t* ww, uint32_t* fw);
+long sw_strong_aug_workspace_bytes(int H, int W);
+/* one image; `recipe` is a HOST pointer; workspace 256-byte aligned; out must not alias in */
+int sw_strong_aug_u8(int H, int W, const uint8_t* in, const sw_aug_recipe* recipe, uint8_t* out, void* workspace,
+                     sw_stream_t stream);
+/* a batch of images of different sizes in one launch sequence: items_dev is a DEVICE array of n entries; max_h / max_w: the
+ * largest H and W among them; stages: SW_AUG_STAGE_* bits, which launches the batch needs.  Same bytes as n single calls. */
+int sw_strong_aug_multi_u8(int n, const sw_aug_item* items_dev, int max_h, int max_w, int stages, sw_stream_t stream);
+
 const char* sw_version(void);
 
 #ifdef __cplusplus

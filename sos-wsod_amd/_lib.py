@@ -46,6 +46,20 @@ class WgradFold(ctypes.Structure):
                 ("dw_oihw", ctypes.c_void_p)]
 
 
+class AugRecipe(ctypes.Structure):
+    """sw_aug_recipe"""
+    _fields_ = [("seed", ctypes.c_uint64), ("key", ctypes.c_uint64), ("order", ctypes.c_int32 * 4), ("factor", ctypes.c_float * 4),
+                ("hue_shift", ctypes.c_int32), ("grayscale", ctypes.c_int32), ("blur_r", ctypes.c_int32),
+                ("blur_ww", ctypes.c_uint32), ("blur_fw", ctypes.c_uint32), ("rect", (ctypes.c_int32 * 4) * 3),
+                ("pad_", ctypes.c_int32)]
+
+
+class AugItem(ctypes.Structure):
+    """sw_aug_item"""
+    _fields_ = [("src", ctypes.c_void_p), ("out", ctypes.c_void_p), ("tmp", ctypes.c_void_p), ("lsum", ctypes.c_void_p),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("recipe", AugRecipe)]
+
+
 class GemmKKProblem(ctypes.Structure):
     """sw_gemm_kk_problem"""
     _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("slabs", ctypes.c_void_p), ("M", ctypes.c_int32), ("N", ctypes.c_int32),
@@ -198,6 +212,11 @@ SIGNATURES = {
     "sw_scale_scalars": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sw_counter_add": (c_int, [c_void_p, c_u64, c_void_p]),
     "sw_focal_loss": (c_int, [c_int, c_int, c_void_p, c_long, c_void_p, c_float, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
+    "sw_gaussian_blur_weights": (c_int, [c_float, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32),
+                                         ctypes.POINTER(ctypes.c_uint32)]),
+    "sw_strong_aug_workspace_bytes": (c_long, [c_int, c_int]),
+    "sw_strong_aug_u8": (c_int, [c_int, c_int, c_void_p, ctypes.POINTER(AugRecipe), c_void_p, c_void_p, c_void_p]),
+    "sw_strong_aug_multi_u8": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "sw_copy_multi": (c_int, [c_int, ctypes.POINTER(CopyDesc), c_void_p]),
     "sw_pack_views": (c_int, [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
                               c_void_p]),

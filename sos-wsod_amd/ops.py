@@ -884,6 +884,98 @@ def color_jitter_u8(src, w_bright=None, w_sat=None, with_flip=False):
     return (out, flip) if with_flip else out
 
 
+_AUG_OPS = {"brightness": 0, "contrast": 1, "saturation": 2, "hue": 3}
+
+
+def _fill_aug_recipe(c, recipe):
+    """strong_aug.Recipe -> sw_aug_recipe: op names to codes, the hue factor to its H-channel shift (`int(hue * 255)` truncated
+    toward zero, modulo 256 — the rule chosen for the reference's `np.uint8(negative float)`), sigma to Pillow's integer box weights"""
+    from ._lib import lib as _l
+    order = tuple(recipe.order)
+    assert len(order) <= 4 and len(set(order)) == len(order) and all(o in _AUG_OPS for o in order), \
+        f"order {order!r}: distinct ops out of {tuple(_AUG_OPS)}"
+    c.seed, c.key = int(recipe.seed) & 0xFFFFFFFFFFFFFFFF, int(recipe.key) & 0xFFFFFFFFFFFFFFFF
+    for s in range(4):
+        c.order[s] = _AUG_OPS[order[s]] if s < len(order) else -1
+    c.factor[0], c.factor[1], c.factor[2], c.factor[3] = recipe.brightness, recipe.contrast, recipe.saturation, recipe.hue
+    if "hue" in order and not -0.5 <= recipe.hue <= 0.5:
+        raise ValueError(f"hue factor {recipe.hue} is not in [-0.5, 0.5]")
+    c.hue_shift = int(recipe.hue * 255) % 256
+    c.grayscale = 1 if recipe.grayscale else 0
+    c.blur_r = -1
+    if recipe.blur_sigma is not None:
+        r, ww, fw = ctypes.c_int32(), ctypes.c_uint32(), ctypes.c_uint32()
+        check(_l.sw_gaussian_blur_weights(float(recipe.blur_sigma), ctypes.byref(r), ctypes.byref(ww), ctypes.byref(fw)),
+              "sw_gaussian_blur_weights")
+        c.blur_r, c.blur_ww, c.blur_fw = r.value, ww.value, fw.value
+    rects = tuple(recipe.rects)
+    assert len(rects) <= 3
+    for e in range(3):
+        t, l, h, w = rects[e] if e < len(rects) and rects[e] is not None else (0, 0, 0, 0)
+        c.rect[e][0], c.rect[e][1], c.rect[e][2], c.rect[e][3] = int(t), int(l), int(h), int(w)
+    return c
+
+
+def _check_aug_image(img, recipe):
+    _need_gpu(img)
+    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[0] == 3 and img.is_contiguous(), "planar (3, H, W) uint8, contiguous"
+    H, W = img.shape[1], img.shape[2]
+    for rc in recipe.rects:
+        if rc is not None and rc[2] > 0:
+            t, l, h, w = rc
+            assert 0 <= t and 0 <= l and h > 0 and w > 0 and t + h <= H and l + w <= W, f"rectangle {rc} leaves the {H} x {W} image"
+    return H, W
+
+
+def strong_augment_u8(img, recipe, out=None):
+    """The Stage-3 strong augmentation of one planar (3, H, W) u8 image (sw_strong_aug_u8): `recipe` is a strong_aug.Recipe —
+    colour jitter in its drawn order, grayscale, Gaussian blur, up to three erased rectangles; pixels equal to Pillow's.
+    -> out (a new tensor unless given; never `img` itself)"""
+    from ._lib import AugRecipe
+    H, W = _check_aug_image(img, recipe)
+    if out is None:
+        out = torch.empty_like(img)
+    _need_gpu(out)
+    assert out.shape == img.shape and out.dtype == torch.uint8 and out.is_contiguous() and out.data_ptr() != img.data_ptr()
+    ws = torch.empty(lib.sw_strong_aug_workspace_bytes(H, W), dtype=torch.uint8, device=img.device)
+    c = _fill_aug_recipe(AugRecipe(), recipe)
+    check(lib.sw_strong_aug_u8(H, W, _p(img), ctypes.byref(c), _p(out), _p(ws), _stream()), "sw_strong_aug_u8")
+    return out
+
+
+def strong_augment_multi_u8(imgs, recipes, outs=None):
+    """strong_augment_u8 for a list of images of different sizes in one launch sequence (sw_strong_aug_multi_u8): the per-image
+    pointers, sizes and recipes travel as one record array (pinned host buffer, asynchronous copy: no host synchronisation).
+    Bit-identical to the per-image calls.  -> list of outputs"""
+    from ._lib import AugItem
+    assert len(imgs) == len(recipes)
+    n = len(imgs)
+    if n == 0:
+        return []
+    dev = imgs[0].device
+    if outs is None:
+        outs = [torch.empty_like(im) for im in imgs]
+    sizes = [_check_aug_image(im, rc) for im, rc in zip(imgs, recipes)]
+    per = [lib.sw_strong_aug_workspace_bytes(h, w) for h, w in sizes]
+    ws = torch.empty(sum(per), dtype=torch.uint8, device=dev)
+    stage = torch.empty(n * ctypes.sizeof(AugItem), dtype=torch.uint8, pin_memory=True)
+    items = (AugItem * n).from_address(stage.data_ptr())
+    stages, off = 0, ws.data_ptr()
+    for i, (im, rc, o) in enumerate(zip(imgs, recipes, outs)):
+        _need_gpu(o)
+        assert im.device == dev and o.shape == im.shape and o.dtype == torch.uint8 and o.is_contiguous() and o.data_ptr() != im.data_ptr()
+        it = items[i]
+        it.src, it.out, it.tmp, it.lsum = im.data_ptr(), o.data_ptr(), off, off + per[i] - 256
+        it.H, it.W = sizes[i]
+        _fill_aug_recipe(it.recipe, rc)
+        stages |= (2 if it.recipe.blur_r >= 0 else 4) | (1 if "contrast" in rc.order else 0)
+        off += per[i]
+    items_dev = stage.to(dev, non_blocking=True)
+    check(lib.sw_strong_aug_multi_u8(n, _p(items_dev), max(h for h, _ in sizes), max(w for _, w in sizes), stages, _stream()),
+          "sw_strong_aug_multi_u8")
+    return outs
+
+
 def transpose_2d(src, dst, rows, cols):
     """dst[c][r] = src[r][c]; src (rows, cols), dst (cols, rows), same dtype, unit inner stride"""
     _need_gpu(src, dst)
