@@ -1,0 +1,289 @@
+"""GPU: the WSDDN / OICR head kernels (csrc/heads.hip, the loss glue of csrc/elementwise.hip) against the float64 restatements of
+tests/heads_ref.py at their edges: V = 1 .. 8, R around the 256-row chunk / the 64-row tile / the 4-row group, K = 1 .. 128 (dynamic
+LDS above 64 KB), logits up to N(0, 40^2) and shifted by 3e4, chunks that differ by more than float32's exp range, saturated and
+clamped image scores, every label kind, the rejections.  Every output buffer starts as a NaN with a payload no kernel writes: what
+the contract says is written must be finite and within the bar of heads_ref.E32 (taken from the float32 error of the reference
+formula, never from the kernel), everything else must still hold the sentinel.  No element is masked and no case skipped; the
+inputs' distance from the two discontinuities (clamp, L1 kink) is asserted by tests/test_heads_ref_cpu.py."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from oracle import oicr_oracle as O  # noqa: E402  (checker only)
+import heads_ref as H  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def ops():
+    import sos_wsod_amd  # noqa: F401
+    import sos_wsod_amd.ops as ops
+    assert torch.cuda.is_available()
+    return ops
+
+
+_F32_SENTINEL, _BF16_SENTINEL, _I32_SENTINEL = 0x7FA5A5A5, 0x7FA5, -123456789
+
+
+def _sent(*shape, dtype=torch.float32):
+    if dtype == torch.float32:
+        return torch.full(shape, _F32_SENTINEL, device="cuda", dtype=torch.int32).view(torch.float32)
+    if dtype == torch.bfloat16:
+        return torch.full(shape, _BF16_SENTINEL, device="cuda", dtype=torch.int16).view(torch.bfloat16)
+    return torch.full(shape, _I32_SENTINEL, device="cuda", dtype=torch.int32)
+
+
+def _untouched(t):
+    """bool tensor: the element still holds the sentinel bits"""
+    if t.dtype == torch.float32:
+        return t.view(torch.int32) == _F32_SENTINEL
+    if t.dtype == torch.bfloat16:
+        return t.view(torch.int16) == _BF16_SENTINEL
+    return t == _I32_SENTINEL
+
+
+def _cu(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _close(kind, regime, got, ref, what):
+    got = got.detach().cpu().numpy().astype(np.float64)
+    assert np.isfinite(got).all(), f"{what}: {kind} holds non-finite values"
+    e, b = H.rel_err(got, ref), H.bar(kind, regime)
+    print(f"{what} {kind}[{regime}]: err {e:.3g} of max|ref|, bar {b:.3g}")
+    assert e <= b, f"{what}: {kind} off by {e:.3g} of max|ref| (bar {b:.3g})"
+
+
+# ------------------------------------------------------------------------------------------------ sw_wsddn_mil
+def _run_wsddn(ops, c, lg, gt, gs, with_grad=True, V=None):
+    V = c["V"] if V is None else V
+    R, K = c["R"], c["K"]
+    cls_col, det_col, ld, ld_d, mp = H.wsddn_layout(K, c["layout"])
+    scores, lv, mean = _sent(V, R, K), _sent(V), _sent(R + 1, mp)
+    dl = _sent(V * R + 2, ld_d) if with_grad else None
+    ops.wsddn_mil(lg, V, R, K, cls_col, det_col, gt, scores, lv, dl, gs if with_grad else None, mean_scores=mean[:R])
+    torch.cuda.synchronize()
+    return scores, lv, mean, dl
+
+
+@pytest.mark.parametrize("c", H.WSDDN_CASES, ids=[c["id"] for c in H.WSDDN_CASES])
+def test_wsddn_mil_against_float64(ops, c):
+    V, R, K = c["V"], c["R"], c["K"]
+    cls_col, det_col, ld, ld_d, mp = H.wsddn_layout(K, c["layout"])
+    lg, gt, gs = H.wsddn_inputs(c)
+    ref = H.wsddn_ref(np.nan_to_num(lg).astype(np.float64), V, R, K, cls_col, det_col, gt, gs)
+    lg_d, gt_d, gs_d = _cu(lg), _cu(gt), _cu(np.array([gs], np.float32))
+    scores, lv, mean, dl = _run_wsddn(ops, c, lg_d, gt_d, gs_d)
+    reg, what = H.wsddn_tol_regime(c), c["id"]
+    _close("wsddn.scores", reg, scores, ref["scores"], what)
+    _close("wsddn.loss", reg, lv, ref["loss"], what)
+    _close("wsddn.mean", reg, mean[:R, :K], ref["mean"], what)
+    assert bool((mean[:R, K:] == 0).all()), "pad columns of the mean scores must be exactly 0"
+    assert bool(_untouched(mean[R]).all())
+    g = dl[:V * R].view(V, R, ld_d)
+    dcls, ddet = g[:, :, cls_col:cls_col + K], g[:, :, det_col:det_col + K]
+    _close("wsddn.grad", reg, torch.cat([dcls, ddet], 2), np.concatenate([ref["dcls"], ref["ddet"]], 2), what)
+    outside = torch.ones(ld_d, dtype=torch.bool, device="cuda")
+    outside[cls_col:cls_col + K] = False; outside[det_col:det_col + K] = False
+    assert bool(_untouched(dl[:V * R][:, outside]).all()), "gradient columns outside the two blocks were written"
+    assert bool(_untouched(dl[V * R:]).all()), "gradient rows beyond V * R were written"
+    clamped = torch.from_numpy(ref["clamped"]).cuda()                       # (V, K)
+    assert bool((ddet.permute(0, 2, 1)[clamped] == 0).all()), "a clamped class must have an exactly zero detection gradient"
+    for v in range(V):
+        if bool(clamped[v].all()):
+            assert bool((dcls[v] == 0).all() and (ddet[v] == 0).all()), "every class clamped: both blocks exactly 0"
+    # the launch without a gradient (one chunk per view in the last kernel) gives the same bits
+    s2, lv2, m2, _ = _run_wsddn(ops, c, lg_d, gt_d, gs_d, with_grad=False)
+    assert torch.equal(s2.view(torch.int32), scores.view(torch.int32)) and torch.equal(lv2.view(torch.int32), lv.view(torch.int32))
+    assert torch.equal(m2.view(torch.int32), mean.view(torch.int32))
+    if V == 4:                                                                # views are independent: V = 1 on a view's rows
+        for v in range(V):
+            s1, lv1, _, _ = _run_wsddn(ops, c, lg_d[v * R:(v + 1) * R], gt_d, gs_d, with_grad=False, V=1)
+            assert torch.equal(s1[0].view(torch.int32), scores[v].view(torch.int32))
+            assert torch.equal(lv1.view(torch.int32), lv[v:v + 1].view(torch.int32))
+
+
+@pytest.mark.parametrize("V,K", [(9, 20), (4, 129)])
+def test_wsddn_mil_rejects_beyond_its_limits_and_writes_nothing(ops, V, K):
+    R, ld = 37, 2 * K + 5
+    lg = torch.randn(V * R, ld, device="cuda")
+    scores, lv, mean, dl = _sent(V, R, K), _sent(V), _sent(R, K + 1), _sent(V * R, ld)
+    with pytest.raises(Exception, match="sw_wsddn_mil"):
+        ops.wsddn_mil(lg, V, R, K, 1, K + 2, torch.zeros(K, device="cuda"), scores, lv, dl, torch.ones(1, device="cuda"),
+                      mean_scores=mean)
+    torch.cuda.synchronize()
+    for t in (scores, lv, mean, dl):
+        assert bool(_untouched(t).all())
+
+
+# ------------------------------------------------------------------------------------------------ sw_oicr_mean_probs
+@pytest.mark.parametrize("c", H.MEAN_PROBS_CASES, ids=[c["id"] for c in H.MEAN_PROBS_CASES])
+def test_mean_probs_against_float64(ops, c):
+    V, R, K, NR = c["V"], c["R"], c["K"], c["NR"]
+    cls_col, _, stride, _ = H.head_layout(K, NR)
+    lg = H.mean_probs_inputs(c)
+    ref = H.mean_probs_ref(np.nan_to_num(lg).astype(np.float64), V, R, K, NR, cls_col, stride)
+    n = NR * R * (K + 1)
+    flat = _sent(n + 16)
+    ops.oicr_mean_probs(_cu(lg), V, R, K, NR, cls_col, stride, flat[:n].view(NR, R, K + 1))
+    torch.cuda.synchronize()
+    _close("mean_probs", f"sd{c['sd']:g}", flat[:n].view(NR, R, K + 1), ref, c["id"])
+    assert bool(_untouched(flat[n:]).all())
+
+
+def test_mean_probs_rejects_what_exceeds_lds_and_more_than_8_views(ops):
+    for V, K in (H.MEAN_PROBS_TOO_BIG, (9, 20)):
+        R = 70
+        out = _sent(1, R, K + 1)
+        with pytest.raises(Exception, match="sw_oicr_mean_probs"):
+            ops.oicr_mean_probs(torch.randn(V * R, K + 1, device="cuda"), V, R, K, 1, 0, 0, out)
+        torch.cuda.synchronize()
+        assert bool(_untouched(out).all())
+
+
+# ------------------------------------------------------------------------------------------------ sw_oicr_refine_loss
+@pytest.mark.parametrize("c", H.REFINE_CASES, ids=[c["id"] for c in H.REFINE_CASES])
+def test_refine_loss_against_float64(ops, c):
+    V, R, K, NR = c["V"], c["R"], c["K"], c["NR"]
+    i = H.refine_inputs(c)
+    cls_col, box_col, stride, ld = i["cls_col"], i["box_col"], i["stride"], i["ld"]
+    ref = H.refine_ref(np.nan_to_num(i["logits"]).astype(np.float64), V, R, K, cls_col, box_col, i["boxes"], i["lab_class"],
+                       i["lab_weight"], i["lab_index"], i["pred_view"], H.REG_WEIGHTS, i["grad_scale"], NR, stride)
+    ld_d = ld + 3
+    lv, dl = _sent(NR, 2, V), _sent(V * R + 2, ld_d)
+    ops.oicr_refine_loss(_cu(i["logits"]), V, R, K, cls_col, box_col, _cu(i["boxes"]), _cu(i["lab_class"]), _cu(i["lab_weight"]),
+                         _cu(i["lab_index"]), _cu(i["pred_view"]), H.REG_WEIGHTS, lv, dl, _cu(i["grad_scale"]), n_rounds=NR,
+                         col_stride=stride)
+    torch.cuda.synchronize()
+    reg, what = H.refine_tol_regime(c), c["id"]
+    _close("refine.loss_cls", reg, lv[:, 0], ref["loss"][:, 0], what)
+    _close("refine.loss_box", reg, lv[:, 1], ref["loss"][:, 1], what)
+    g = dl[:V * R].view(V, R, ld_d)
+    dcls = torch.stack([g[:, :, cls_col + k * stride:cls_col + k * stride + K + 1] for k in range(NR)])
+    dbox = torch.stack([g[:, :, box_col + k * stride:box_col + k * stride + 4 * K] for k in range(NR)])
+    _close("refine.dcls", reg, dcls, ref["dcls"], what)
+    _close("refine.dbox", reg, dbox, ref["dbox"], what)
+    outside = torch.ones(ld_d, dtype=torch.bool, device="cuda")
+    for k in range(NR):
+        outside[cls_col + k * stride:cls_col + k * stride + 5 * K + 1] = False
+    assert bool(_untouched(dl[:V * R][:, outside]).all()), "gradient columns outside the heads were written"
+    assert bool(_untouched(dl[V * R:]).all()), "gradient rows beyond V * R were written"
+    for pv in sorted(set(range(V)) - set(int(x) for x in i["pred_view"])):     # a view that serves no target: zeros, not the sentinel
+        assert bool((dcls[:, pv] == 0).all() and (dbox[:, pv] == 0).all())
+    if c["labels"] in ("self", "ignore", "bg"):                                 # sign(0) / no foreground: exactly no box gradient, no box loss
+        assert bool((dbox == 0).all() and (lv[:, 1] == 0).all())
+    if c["labels"] == "ignore":
+        assert bool((dcls == 0).all() and (lv == 0).all())
+
+
+# ------------------------------------------------------------------------------------------------ sw_oicr_predict
+@pytest.mark.parametrize("c", H.PREDICT_CASES, ids=[c["id"] for c in H.PREDICT_CASES])
+def test_predict_against_float64(ops, c):
+    R, K, RK = c["R"], c["K"], c["RK"]
+    lg, boxes, base, stride = H.predict_inputs(c)
+    s64, b64 = H.predict_ref(np.nan_to_num(lg).astype(np.float64), R, K, RK, base, stride, boxes, H.REG_WEIGHTS, c["clamp"])
+    sc, bx = _sent(R + 1, K + 1), _sent(R + 1, 4 * K)
+    ops.oicr_predict(_cu(lg), R, K, RK, base, stride, _cu(boxes), H.REG_WEIGHTS, c["clamp"], sc, bx)
+    torch.cuda.synchronize()
+    _close("predict.scores", "all", sc[:R], s64, c["id"])
+    _close("predict.boxes", "all", bx[:R], b64, c["id"])
+    assert bool(_untouched(sc[R]).all() and _untouched(bx[R]).all())
+
+
+def test_predict_of_no_rows_is_a_no_op(ops):
+    K = 20
+    sc, bx = _sent(3, K + 1), _sent(3, 4 * K)
+    ops.oicr_predict(torch.randn(3, 5 * K + 1, device="cuda"), 0, K, 1, 0, 5 * K + 1, torch.zeros(3, 4, device="cuda"), H.REG_WEIGHTS,
+                     H.SCALE_CLAMP, sc, bx)
+    torch.cuda.synchronize()
+    assert bool(_untouched(sc).all() and _untouched(bx).all())
+
+
+# ------------------------------------------------------------------------------------------------ loss glue
+@pytest.mark.parametrize("n,V,B", H.FINALIZE_CASES)
+def test_loss_finalize_against_float64(ops, n, V, B):
+    lv = H.finalize_inputs(n, V, B)
+    o64, t64 = H.loss_finalize_ref(lv.astype(np.float64))
+    out, total = _sent(n + 3), _sent(5)
+    ops.loss_finalize(_cu(lv), out[:n], total[:2])
+    torch.cuda.synchronize()
+    _close("finalize.out", "all", out[:n], o64, f"n{n}-V{V}-B{B}")
+    _close("finalize.total", "all", total[:1], np.array([t64]), f"n{n}-V{V}-B{B}")
+    assert float(total[1]) == 1.0                                            # the sum is finite
+    assert bool(_untouched(out[n:]).all() and _untouched(total[2:]).all())
+    if B == 1:                                                                # the 2-D form is the one-image form
+        out2 = _sent(n)
+        ops.loss_finalize(_cu(lv[0]), out2)
+        assert torch.equal(out2.view(torch.int32), out[:n].view(torch.int32))
+
+
+def test_loss_finalize_rejects_more_than_64_losses(ops):
+    out, total = _sent(65), _sent(2)
+    with pytest.raises(Exception, match="sw_loss_finalize"):
+        ops.loss_finalize(torch.ones(1, 65, 4, device="cuda"), out, total)
+    torch.cuda.synchronize()
+    assert bool(_untouched(out).all() and _untouched(total).all())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("M,N,nv,xin,xout,with_g", H.SCALE_COLS_CASES)
+def test_scale_cols_loss_against_float64(ops, dtype, M, N, nv, xin, xout, with_g):
+    src, gl, gt, c2l, mul = H.scale_cols_inputs(M, N, nv)
+    ref = H.scale_cols_loss_ref(np.nan_to_num(src).astype(np.float64), gl if with_g else None, gt, c2l, mul, nv)
+    src_d = torch.full((M, N + xin), float("nan"), device="cuda")
+    src_d[:, :N] = _cu(src)                                                    # the pad columns [nv, N) hold NaN: never read
+    dst = _sent(M + 1, N + xout, dtype=dtype)
+    ops.scale_cols_loss(src_d[:, :N], _cu(gl) if with_g else None, _cu(gt), _cu(c2l), float(mul), dst[:M, :N], M, N, nv)
+    torch.cuda.synchronize()
+    got = dst[:M, :N]
+    assert bool((got[:, nv:] == 0).all()), "pad columns must come out exactly 0"
+    assert bool(_untouched(dst[:M, N:]).all() and _untouched(dst[M]).all())
+    if dtype == torch.float32:
+        _close("scale_cols.f32", "all", got, ref, f"{M}x{N}")
+    else:
+        # bf16 keeps 8 significant bits: round-to-nearest of the float32 product is within 2^-9 of it; 2^-8 covers the product's own
+        # float32 rounding moving a value across a rounding boundary
+        g64 = got.float().cpu().numpy().astype(np.float64)
+        assert np.isfinite(g64).all() and np.all(np.abs(g64 - ref) <= 2.0 ** -8 * np.abs(ref))
+
+
+@pytest.mark.parametrize("V,n", H.MEAN_VIEWS_CASES)
+def test_mean_views_against_float64(ops, V, n):
+    x = H.mean_views_inputs(V, n)
+    out = _sent(n + 8)
+    ops.mean_views(_cu(x), out[:n])
+    torch.cuda.synchronize()
+    _close("mean_views", "all", out[:n], H.mean_views_ref(x.astype(np.float64)), f"V{V}-n{n}")
+    assert bool(_untouched(out[n:]).all())
+
+
+# ------------------------------------------------------------------------------------------------ sw_oicr_mine_label
+@pytest.mark.parametrize("c", H.MINE_CASES, ids=[c["id"] for c in H.MINE_CASES])
+def test_mining_sweep_bit_exact_against_the_oracle(ops, c):
+    """scores from a small value set (exact ties, values at and one ulp below the threshold), duplicated boxes; every launch form
+    (keys and lists in LDS / keys in LDS / keys in the workspace: test_heads_ref_cpu.py asserts the sweep holds all three)"""
+    R, K, G, NR = c["R"], c["K"], c["G"], c["NR"]
+    scores, boxes, gt = H.mine_inputs(c)
+    top_k = H.mine_top_k(R)
+    form = H.mine_form(R, top_k, G)
+    base_bytes = (top_k * G * 20 + 64 + 15) // 16 * 16
+    assert (ops.mine_workspace_bytes(R, top_k, G) > base_bytes) == (form == "ws")
+    lab_c, lab_w, lab_i = _sent(NR, R, dtype=torch.int32), _sent(NR, R), _sent(NR, R, dtype=torch.int32)
+    cnt = _sent(NR, dtype=torch.int32)
+    pi, pc, ps = _sent(NR, top_k * G, dtype=torch.int32), _sent(NR, top_k * G, dtype=torch.int32), _sent(NR, top_k * G)
+    ws = torch.empty(ops.mine_workspace_bytes(R, top_k, G, NR), dtype=torch.uint8, device="cuda")
+    ops.oicr_mine_label(_cu(scores), _cu(gt.astype(np.int32)), _cu(boxes), K, top_k, H.MINE_THRESH, H.MINE_NMS, 0.5, 0.6, lab_c, lab_w,
+                        lab_i, cnt, pi, pc, ps, ws)
+    torch.cuda.synchronize()
+    for k in range(NR):
+        o = O.get_pgt_mist(scores[k], boxes, gt, H.MINE_TOP_P, H.MINE_THRESH, H.MINE_NMS)
+        lab = O.label_proposals(o, boxes, K)
+        n = int(cnt[k].item())
+        assert n == len(o["index"]), (form, k, n, len(o["index"]))
+        assert np.array_equal(pi[k, :n].cpu().numpy(), o["index"]) and np.array_equal(pc[k, :n].cpu().numpy(), o["classes"])
+        assert np.array_equal(ps[k, :n].cpu().numpy().view(np.int32), o["scores"].view(np.int32))
+        assert bool(_untouched(pi[k, n:]).all() and _untouched(pc[k, n:]).all() and _untouched(ps[k, n:]).all())
+        assert np.array_equal(lab_c[k].cpu().numpy(), lab["gt_classes"])
+        assert np.array_equal(lab_i[k].cpu().numpy(), lab["gt_index"])
+        assert np.array_equal(lab_w[k].cpu().numpy().view(np.int32), lab["gt_weights"].astype(np.float32).view(np.int32))
