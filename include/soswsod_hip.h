@@ -679,6 +679,43 @@ int sw_voc_eval(int K, int n_img, long long N, long long G, const int64_t* det_o
                 const int64_t* gt_off, const double* gt_box, const uint8_t* gt_diff, const int64_t* npos, const int64_t* npos_im,
                 const double* thr, const double* t11, double* out, void* workspace, sw_stream_t stream);
 
+/* COCO bbox evaluation of one split (evaluation/fast_eval_api.py COCOeval_opt over layers/csrc/cocoeval/cocoeval.cpp:
+ * MatchDetectionsToGroundTruth :61-140 with SortInstancesByIgnore :33-56, Accumulate :223-371; the IoU is pycocotools' maskApi.c
+ * bbIou).  A pair is an (image, category) that has detections.  Detections are grouped by pair, the pairs of a category
+ * contiguous and in image order, each pair's detections in stable descending score order and at most SW_COCO_MAX_PAIR_DETS of
+ * them (the evaluator cuts at 100): pair p owns rows [pair_off[p], pair_off[p + 1]) of det_box [N][4] f64 [x, y, w, h] (16-byte
+ * aligned), det_rank [N] u8 (the row's position in its pair) and det_score [N] f64; category c owns rows [cat_off[c],
+ * cat_off[c + 1]), and order [N] i32 lists each category's rows stably sorted by descending score (order[cat_off[c] ..] are rows
+ * of c).  The pair's ground truth is rows [gt_off[pair_gt[p]], gt_off[pair_gt[p] + 1]) of gt_box [G][4] f64 [x, y, w, h] (16-byte
+ * aligned), gt_area [G] f64 (the annotation's own area) and gt_flags [G] u8 (bit 0: iscrowd, which is also its ignore flag; bit 1:
+ * annotation id > 0), in annotation order.  area_rng [SW_COCO_AREAS][2], iou_thr [SW_COCO_THRESHOLDS], rec_thr [SW_COCO_RECALLS] f64,
+ * max_dets [SW_COCO_MAXDETS] i32 ascending; npig [K][SW_COCO_AREAS] i64: the non-ignored ground truth of a category and area range
+ * over all images.  A pair with G <= 64 and D * G <= lds_doubles (<= SW_COCO_LDS_DOUBLES) is matched in LDS; any other pair needs
+ * sw_coco_eval_workspace_bytes(D, G, lds_doubles) bytes (0 for a pair that fits) starting at 8 * pair_ws[p] bytes behind the
+ * workspace's SW_COCO_WS_HEADER-byte header (pair_ws [P] i64, read only for such pairs); ws_bytes is the size of the whole
+ * workspace (256-byte aligned), header included.  A region outside it is not touched and turns every output into NaN; so does a
+ * pair of more than SW_COCO_MAX_PAIR_DETS detections or SW_COCO_MAX_PAIR_GT ground truths (within them D * G fits an int).
+ * match [N][2] u64: bit a * SW_COCO_THRESHOLDS + t of word 0 / 1 is the detection's matched / ignored flag in area range a at
+ * threshold t.  out f64: precision [T][R][K][A][M], scores [T][R][K][A][M], recall [T][K][A][M], one after the other, each value
+ * bit-identical to the reference's.  Kept from the reference: "matched" means the ground truth's id is > 0. */
+#define SW_COCO_MAX_CLASSES 4096
+#define SW_COCO_THRESHOLDS 10
+#define SW_COCO_RECALLS 101
+#define SW_COCO_AREAS 4
+#define SW_COCO_MAXDETS 3
+#define SW_COCO_MAX_PAIR_DETS 255
+#define SW_COCO_MAX_PAIR_GT ((1 << 23) - 1)
+#define SW_COCO_MAX_DETS ((1LL << 31) - 1)
+#define SW_COCO_LDS_DOUBLES 1600
+#define SW_COCO_WS_HEADER 256
+long long sw_coco_eval_workspace_bytes(int D, long long G, int lds_doubles);
+int sw_coco_eval(int K, long long N, long long P, const int64_t* pair_off, const int64_t* pair_gt, const int64_t* pair_ws,
+                 long long ws_bytes, int lds_doubles, const double* det_box, const int64_t* gt_off, const double* gt_box,
+                 const double* gt_area, const uint8_t* gt_flags, const double* area_rng, const double* iou_thr, const double* rec_thr,
+                 const int32_t* max_dets, const int64_t* cat_off, const int32_t* order, const uint8_t* det_rank,
+                 const double* det_score, const int64_t* npig, unsigned long long* match, double* out, void* workspace,
+                 sw_stream_t stream);
+
 /* Stage-3 strong augmentation of a planar u8 [3][H][W] image, every pixel operation bit-identical to Pillow's (replaces
  * build_strong_augmentation, unbias/ubteacher/data/detection_utils.py:9-46, applied by DatasetMapperTwoCropSeparate.__call__,
  * unbias/ubteacher/data/dataset_mapper.py:141-149; the blur is unbias/ubteacher/data/transforms/augmentation_impl.py GaussianBlur):

@@ -269,6 +269,10 @@ SIGNATURES = {
     "sw_voc_eval_workspace_bytes": (ctypes.c_longlong, [c_int, c_int, ctypes.c_longlong, ctypes.c_longlong]),
     "sw_voc_eval": (c_int, [c_int, c_int, ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ---- COCO evaluation (csrc/evaluation.hip)
+    "sw_coco_eval_workspace_bytes": (ctypes.c_longlong, [c_int, ctypes.c_longlong, c_int]),
+    "sw_coco_eval": (c_int, [c_int, ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int]
+                     + [c_void_p] * 18),
     "sw_version": (ctypes.c_char_p, []),
 }
 

@@ -1518,3 +1518,53 @@ def voc_eval(det_off, det_img, det_box, gt_off, gt_box, gt_diff, npos, npos_im, 
     check(lib.sw_voc_eval(K, n_img, N, G, _p(det_off), _p(det_img), _p(det_box), _p(gt_off), _p(gt_box), _p(gt_diff), _p(npos),
                           _p(npos_im), _p(thr), _p(t11), _p(out), ws_p, _stream()), "sw_voc_eval")
     return out
+
+
+COCO_THRESHOLDS, COCO_RECALLS, COCO_AREAS, COCO_MAXDETS = 10, 101, 4, 3
+COCO_LDS_DOUBLES = 1600                           # SW_COCO_LDS_DOUBLES
+COCO_MAX_CLASSES = 4096                           # SW_COCO_MAX_CLASSES
+COCO_WS_HEADER = 256                              # SW_COCO_WS_HEADER
+
+
+def coco_eval(pair_off, pair_gt, pair_ws, ws_words, det_box, gt_off, gt_box, gt_area, gt_flags, area_rng, iou_thr, rec_thr, max_dets,
+              cat_off, order, det_rank, det_score, npig, lds_doubles=COCO_LDS_DOUBLES, match=None, out=None):
+    """COCO bbox matching and accumulation of one split (sw_coco_eval; the layouts are in include/soswsod_hip.h), all inputs on the
+    GPU: pair_off [P + 1] / pair_gt [P] / pair_ws [P] i64, det_box [N, 4] f64 XYWH, gt_off i64, gt_box [G, 4] f64, gt_area [G] f64,
+    gt_flags [G] u8, area_rng [4, 2] / iou_thr [10] / rec_thr [101] f64, max_dets [3] i32, cat_off [K + 1] i64, order [N] i32,
+    det_rank [N] u8, det_score [N] f64, npig [K, 4] i64.  ws_words: the 8-byte words the pairs outside the LDS path need in all
+    (pair_ws holds each one's offset in words).  match [N, 2] u64-as-i64 and out f64 [2 * 10 * 101 * K * 12 + 10 * K * 12] may be
+    passed in (tests fill them with sentinels).
+    -> (out, match) on the GPU: out is precision [10, 101, K, 4, 3], scores [10, 101, K, 4, 3], recall [10, K, 4, 3] flattened one
+    after the other (the caller copies it back once)."""
+    ts = (pair_off, pair_gt, pair_ws, det_box, gt_off, gt_box, gt_area, gt_flags, area_rng, iou_thr, rec_thr, max_dets, cat_off,
+          order, det_rank, det_score, npig)
+    _need_gpu(*ts)
+    K, N, P, G = cat_off.numel() - 1, det_score.numel(), pair_gt.numel(), gt_flags.numel()
+    for t in (pair_off, pair_gt, pair_ws, gt_off, cat_off, npig):
+        assert t.dtype == torch.int64
+    for t in (det_box, gt_box, gt_area, area_rng, iou_thr, rec_thr, det_score):
+        assert t.dtype == torch.float64
+    assert gt_flags.dtype == torch.uint8 and det_rank.dtype == torch.uint8 and max_dets.dtype == torch.int32
+    assert order.dtype == torch.int32
+    assert pair_off.shape == (P + 1,) and pair_ws.shape == (P,) and det_box.shape == (N, 4) and gt_box.shape == (G, 4)
+    assert gt_area.shape == (G,) and order.shape == (N,) and det_rank.shape == (N,) and npig.shape == (K, COCO_AREAS)
+    assert area_rng.shape == (COCO_AREAS, 2) and iou_thr.shape == (COCO_THRESHOLDS,) and rec_thr.shape == (COCO_RECALLS,)
+    assert max_dets.shape == (COCO_MAXDETS,) and K >= 1 and ws_words >= 0
+    for t in ts:
+        assert t.is_contiguous()
+    n_cell = COCO_THRESHOLDS * K * COCO_AREAS * COCO_MAXDETS
+    n_out = 2 * COCO_RECALLS * n_cell + n_cell
+    dev = det_box.device
+    if out is None:
+        out = torch.empty(n_out, device=dev, dtype=torch.float64)
+    if match is None:
+        match = torch.empty(N, 2, device=dev, dtype=torch.int64)
+    assert out.is_cuda and match.is_cuda and out.dtype == torch.float64 and match.dtype == torch.int64
+    assert out.shape == (n_out,) and match.shape == (N, 2) and out.is_contiguous() and match.is_contiguous()
+    ws_bytes = COCO_WS_HEADER + 8 * int(ws_words)
+    ws = torch.empty(ws_bytes + 256, device=dev, dtype=torch.uint8)
+    ws_p = ctypes.c_void_p((ws.data_ptr() + 255) // 256 * 256)
+    check(lib.sw_coco_eval(K, N, P, _p(pair_off), _p(pair_gt), _p(pair_ws), ws_bytes, int(lds_doubles), _p(det_box), _p(gt_off),
+                           _p(gt_box), _p(gt_area), _p(gt_flags), _p(area_rng), _p(iou_thr), _p(rec_thr), _p(max_dets), _p(cat_off),
+                           _p(order), _p(det_rank), _p(det_score), _p(npig), _p(match), _p(out), ws_p, _stream()), "sw_coco_eval")
+    return out, match
