@@ -112,40 +112,29 @@ typedef struct sw_conv_problem {
   const sw_epilogue* ep;
 } sw_conv_problem;
 int sw_conv3x3_multi(int dtype, int n, const sw_conv_problem* probs, sw_stream_t stream);
-/* dW (OIHW f32, overwritten) from x [nimg][H][W][Cin] and dy [nimg][H][W][Cout].  workspace: at least
- * sw_conv3x3_wgrad_workspace_floats(...) floats: every K-split stores its partial [co][tap][ci] tile into its own
- * slab (plain stores), a second kernel adds the slabs in fixed order and permutes to OIHW (deterministic). */
+/* dW (OIHW f32) from x [nimg][H][W][Cin] and dy [nimg][H][W][Cout]: dw = (accumulate ? dw : 0) + cout_scale[co] * sum.  workspace: at
+ * least sw_conv3x3_wgrad_workspace_floats(...) floats: every K-split stores its partial [co][tap][ci] tile into its own slab (plain
+ * stores), a second kernel adds the slabs in fixed order, scales and permutes to OIHW (deterministic).  cout_scale (DEVICE [Cout]
+ * or NULL): the FrozenBN fold of a 3x3 convolution's weight gradient.  accumulate != 0: the second use of a convolution inside one
+ * backward pass (the Stage-3 student runs two forward passes per iteration; unbias/ubteacher/engine/trainer.py:527-538 leaves that
+ * sum to autograd). */
 long sw_conv3x3_wgrad_workspace_floats(int dtype, int nimg, int H, int W, int Cin, int Cout, int splitk);
-int sw_conv3x3_wgrad(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x,
-                     const void* dy, float* dw_oihw, float* workspace, int splitk, sw_stream_t stream);
-/* The two halves of sw_conv3x3_wgrad on their own: `_slabs` writes this problem's workspace_floats / (Cout*9*Cin) partial
- * slabs at `workspace`; `_fold` adds `nslab` consecutive slabs in fixed order into dW (OIHW).  Several problems with the same
- * weight (the views of one iteration, possibly running on different streams) put their slabs back to back and share ONE
- * fold: the sum over views that autograd would otherwise form with one add per parameter. */
-/* sw_conv3x3_wgrad with dW[co] multiplied by cout_scale[co] (DEVICE [Cout] or NULL) inside the slab fold: the FrozenBN fold of a 3x3
- * convolution's weight gradient */
-int sw_conv3x3_wgrad_scaled(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x, const void* dy,
-                            float* dw_oihw, float* workspace, int splitk, const float* cout_scale, sw_stream_t stream);
-/* sw_conv3x3_wgrad_scaled that ADDS to dw_oihw when accumulate != 0 (dw += cout_scale * fold): the second use of a convolution inside
- * one backward pass (the Stage-3 student runs two forward passes per iteration; unbias/ubteacher/engine/trainer.py:527-538 leaves
- * that sum to autograd). */
-int sw_conv3x3_wgrad_acc(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x, const void* dy,
-                         float* dw_oihw, float* workspace, int splitk, const float* cout_scale, int accumulate, sw_stream_t stream);
+int sw_conv3x3_wgrad(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x, const void* dy,
+                     float* dw_oihw, float* workspace, int splitk, const float* cout_scale, int accumulate, sw_stream_t stream);
 /* the same weight gradient (dilation 1) for maps of a few pixels (nimg * H * W <= 4096: FPN p5 / p6 of small images, below the tile
  * geometry of the MFMA loader: sw_conv3x3_wgrad returns -6 there): one thread per (co, ci), plain f32 sums in pixel order. */
 int sw_conv3x3_wgrad_small(int dtype, int nimg, int H, int W, int Cin, int Cout, const void* x, const void* dy,
-                           const float* cout_scale, float* dw_oihw, sw_stream_t stream);
-/* sw_conv3x3_wgrad_small that adds to dw_oihw when accumulate != 0 (see sw_conv3x3_wgrad_acc) */
-int sw_conv3x3_wgrad_small_acc(int dtype, int nimg, int H, int W, int Cin, int Cout, const void* x, const void* dy,
-                               const float* cout_scale, float* dw_oihw, int accumulate, sw_stream_t stream);
+                           const float* cout_scale, float* dw_oihw, int accumulate, sw_stream_t stream);
+/* The two halves of sw_conv3x3_wgrad on their own: `_slabs` writes this problem's workspace_floats / (Cout*9*Cin) partial
+ * slabs at `workspace`; `_fold` adds `nslab` consecutive slabs in fixed order into dW (OIHW), with cout_scale and accumulate as
+ * above.  Several problems with the same weight (the views of one iteration, possibly running on different streams, or the (x, dy)
+ * pairs written by sw_conv3x3_wgrad_grouped — the RPN head's convolution runs on 5 FPN levels in each of the student's two passes,
+ * rpn.py:118-133) put their slabs back to back and share ONE fold: the sum that autograd would otherwise form with one add per
+ * parameter. */
 int sw_conv3x3_wgrad_slabs(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x,
                            const void* dy, float* workspace, int splitk, sw_stream_t stream);
-int sw_conv3x3_wgrad_fold(int Cin, int Cout, int nslab, const float* workspace, float* dw_oihw, sw_stream_t stream);
-/* sw_conv3x3_wgrad_fold with dW[co] multiplied by cout_scale[co] (DEVICE [Cout] or NULL) and, when accumulate != 0, added to
- * dw_oihw: the ONE fold over the slabs of several (x, dy) pairs of the same weight written by sw_conv3x3_wgrad_grouped — the RPN
- * head's convolution runs on 5 FPN levels in each of the student's two passes (rpn.py:118-133) */
-int sw_conv3x3_wgrad_fold_acc(int Cin, int Cout, int nslab, const float* workspace, float* dw_oihw, const float* cout_scale,
-                              int accumulate, sw_stream_t stream);
+int sw_conv3x3_wgrad_fold(int Cin, int Cout, int nslab, const float* workspace, float* dw_oihw, const float* cout_scale,
+                          int accumulate, sw_stream_t stream);
 /* ALL weight gradients of a backward pass in ONE launch: problem i writes the slabs sw_conv3x3_wgrad_slabs(..., splitk =
  * nsplit) would write (sw_conv3x3_wgrad_workspace_floats(...) floats at `slabs`), computed by resident workgroups walking the
  * (problem, split, tile) list — instead of one launch of 128x128 tiles per layer and view, each cut into many K-splits to fill the
@@ -176,7 +165,7 @@ long sw_gemm_kk_grouped_slabs(int dtype, int K, int nsplit);
  * DEVICE [M] or NULL; N % 4 == 0, ldc % 4 == 0, 16-byte aligned).  `folds` is a HOST array. */
 typedef struct sw_splitk_fold { int32_t M, N, nslab, accumulate; const float* workspace; float* C; long ldc; const float* row_scale; } sw_splitk_fold;
 int sw_splitk_fold_multi(int n, const sw_splitk_fold* folds, sw_stream_t stream);
-/* n folds (sw_conv3x3_wgrad_fold) in ONE launch; `folds` is a HOST array */
+/* n folds (sw_conv3x3_wgrad_fold without scale, overwriting) in ONE launch; `folds` is a HOST array */
 typedef struct { int Cin, Cout, nslab; const float* workspace; float* dw_oihw; } sw_wgrad_fold;
 int sw_conv3x3_wgrad_fold_multi(int n, const sw_wgrad_fold* folds, sw_stream_t stream);
 /* OIHW f32 master weights -> kernel layout.  mode 0: wk[co][tap][ci_pad] (forward, ci zero padded to cin_pad);
@@ -209,20 +198,15 @@ int sw_preprocess_multi(int dtype, int n, int H, int W, int cpad, const uint8_t*
  * traffic.  row_scale (may be NULL): out *= (row_scale[r] + row_scale_add) = the objectness prior of
  * roi_heads_oicrplus.py:200-221.  A +NaN map value never wins a bin (reference: 'val > maxval').
  * ld_out: row pitch (elements) of out AND argmax, 0 = C*PH*PW.  The fc6 GEMM reads `out` fastest when the pitch is not a
- * multiple of 1 KiB (HBM channel / L2 set spread): the hot path passes C*PH*PW + 64. */
+ * multiple of 1 KiB (HBM channel / L2 set spread): the hot path passes C*PH*PW + 64.
+ * workspace: NULL, or a device buffer of >= sw_roi_pool_fwd_workspace_bytes(nimg, R, PH, PW) bytes (16-byte aligned; contents need
+ * not survive the call).  With it, on bf16 maps of < 65535 pixels (H, W <= 255; PH, PW <= 8; C % 8 == 0) the ROI geometry — bin
+ * ranges, size classes, the (image, row band, class) task lists — is computed ONCE per call by a small kernel instead of once per
+ * channel slab inside the pooling kernel (large maps: half of that kernel's cycles).  The results are identical either way. */
+long sw_roi_pool_fwd_workspace_bytes(int nimg, int R, int PH, int PW);
 int sw_roi_pool_fwd(int dtype, int nimg, int H, int W, int C, int PH, int PW, float spatial_scale, const void* feat,
                     const float* rois, int R, const float* row_scale, float row_scale_add, void* out,
-                    void* argmax, int argmax_bits, long ld_out, sw_stream_t stream);
-/* The same with a device workspace of >= sw_roi_pool_fwd_workspace_bytes(nimg, R, PH, PW) bytes (16-byte aligned; contents need not
- * survive the call).  With it, on bf16 maps of < 65535 pixels (H, W <= 255; PH, PW <= 8; C % 8 == 0) the ROI geometry — bin ranges,
- * size classes, the (image, row band, class) task lists — is computed ONCE per call by a small kernel instead of once per channel
- * slab inside the pooling kernel (large maps: half of that kernel's cycles).  Results are identical to sw_roi_pool_fwd's;
- * workspace == NULL is sw_roi_pool_fwd. */
-long sw_roi_pool_fwd_workspace_bytes(int nimg, int R, int PH, int PW);
-int sw_roi_pool_fwd_ws(int dtype, int nimg, int H, int W, int C, int PH, int PW, float spatial_scale, const void* feat,
-                       const float* rois, int R, const float* row_scale, float row_scale_add, void* out,
-                       void* argmax, int argmax_bits, long ld_out, void* workspace, long workspace_bytes,
-                       sw_stream_t stream);
+                    void* argmax, int argmax_bits, long ld_out, void* workspace, long workspace_bytes, sw_stream_t stream);
 /* dfeat [nimg][H][W][C] (dtype, fully overwritten) = scatter-add of dout by argmax, times the same row scale,
  * times (relu_ref > 0) when relu_ref != NULL (relu_ref has feat's layout/dtype).
  * dout_absmax (device scalar >= max|dout|, e.g. from sw_absmax or a GEMM epilogue; may be NULL): selects the fixed-point LDS
@@ -325,23 +309,19 @@ int sw_oicr_predict(int R, int K, int refine_k, const float* logits, long ld, in
 /* sw_detect_postprocess: clip boxes to the image, keep score > score_thresh (background column excluded), per-class
  * greedy NMS (IoU > nms_thresh on boxes offset by class*(max_coord+1), as batched_nms forms them), first topk by
  * score.  Outputs det_count[1], det_boxes [topk][4], det_scores, det_classes, det_rows (proposal index).
- * workspace >= sw_detect_workspace_bytes(K, topk).  Limits: R <= 16384, K*topk <= 16384. */
-long sw_detect_workspace_bytes(int K, int topk);
+ * Limits: R <= 16384, K*topk <= 16384.
+ * workspace_bytes says how large the workspace is.  With >= sw_detect_workspace_bytes(R, K, topk) bytes the per-class NMS of every
+ * class that holds >= 256 candidates runs in its mask form — candidates sorted per class, the 64 x 64 IoU tiles of every class
+ * computed over all CUs, one wave per class resolving the chunks in order (the RPN's per-level lists of detectron2's
+ * find_top_rpn_proposals, proposal_utils.py:20-130: 2000 candidates per level; 20-80 classes of fast_rcnn_inference_single_image).
+ * Below that size the per-class form runs: one workgroup per class doing its N^2 / 2 tests alone.  It needs
+ * sw_detect_workspace_bytes(0, K, topk) bytes, which is also all that sw_detect_workspace_bytes(R, K, topk) returns when the mask
+ * matrices would exceed 96 MiB.  Identical outputs in both forms. */
+long sw_detect_workspace_bytes(int R, int K, int topk);
 int sw_detect_postprocess(int R, int K, const float* all_scores, const float* all_boxes, int img_h, int img_w,
                           float score_thresh, float nms_thresh, int topk, int32_t* det_count, float* det_boxes,
                           float* det_scores, int32_t* det_classes, int32_t* det_rows, void* workspace,
-                          sw_stream_t stream);
-/* The same, told how large the workspace is: with workspace_bytes >= sw_detect_workspace_bytes2(R, K, topk) the per-class NMS of
- * every class that holds >= 256 candidates runs in its mask form — candidates sorted per class, the 64 x 64 IoU tiles of every class computed over all CUs,
- * one wave per class resolving the chunks in order — instead of one workgroup per class doing its N^2 / 2 tests alone (the RPN's
- * per-level lists of detectron2's find_top_rpn_proposals, proposal_utils.py:20-130: 2000 candidates per level; 20-80 classes of
- * fast_rcnn_inference_single_image).  Identical outputs.  sw_detect_workspace_bytes2 returns the plain size when the mask
- * matrices would exceed 96 MiB (then this call runs the single-workgroup form). */
-long sw_detect_workspace_bytes2(int R, int K, int topk);
-int sw_detect_postprocess2(int R, int K, const float* all_scores, const float* all_boxes, int img_h, int img_w,
-                           float score_thresh, float nms_thresh, int topk, int32_t* det_count, float* det_boxes,
-                           float* det_scores, int32_t* det_classes, int32_t* det_rows, void* workspace,
-                           long workspace_bytes, sw_stream_t stream);
+                          long workspace_bytes, sw_stream_t stream);
 
 /* ---- small utilities ------------------------------------------------------------------------------------ */
 /* dst[c][r] = src[r][c] (rows x cols elements of `dtype`, row pitches in elements, multiples of 16 bytes).  The weight-gradient
@@ -391,15 +371,12 @@ int sw_counter_add(uint64_t* counter, uint64_t increment, sw_stream_t stream);
  * `Tensor.copy_` calls of DatasetMapperMultiInput-shaped batches, dataset_mapper.py:272-439).  Regions must not overlap. */
 typedef struct sw_copy_desc { const void* src; void* dst; long bytes; } sw_copy_desc;
 int sw_copy_multi(int n, const sw_copy_desc* copies, sw_stream_t stream);
-/* out[n] = sum_m X[m][ld..] (column sums; the bias gradients of the reference's conv / Linear backward).  out f32,
- * overwritten.  With `workspace` (sw_colsum_workspace_floats floats) the sum is deterministic: partial rows per row chunk,
- * then an ordered fold.  workspace NULL (or N / ld not a multiple of 16 bytes): zero fill + one f32 atomic per column and
- * row chunk. */
+/* out[n] = (accumulate ? out[n] : 0) + sum_m X[m][ld..] (column sums; the bias gradients of the reference's conv / Linear
+ * backward; accumulate != 0: a bias gradient that exists already inside one backward pass, see sw_conv3x3_wgrad).  out f32.  With
+ * `workspace` (sw_colsum_workspace_floats floats) the sum is deterministic: partial rows per row chunk, then an ordered fold.
+ * workspace NULL (or N / ld not a multiple of 16 bytes): zero fill (unless accumulating) + one f32 atomic per column and row chunk. */
 long sw_colsum_workspace_floats(int dtype, int M, int N);
-int sw_colsum(int dtype, int M, int N, const void* X, long ld, float* out, float* workspace, sw_stream_t stream);
-/* sw_colsum that adds to out when accumulate != 0 (a bias gradient that exists already inside one backward pass; see
- * sw_conv3x3_wgrad_acc) */
-int sw_colsum_acc(int dtype, int M, int N, const void* X, long ld, float* out, float* workspace, int accumulate, sw_stream_t stream);
+int sw_colsum(int dtype, int M, int N, const void* X, long ld, float* out, float* workspace, int accumulate, sw_stream_t stream);
 /* halves of the workspace form: `_partial` writes sw_colsum_workspace_floats(dtype, M, N) / N partial rows at `workspace`,
  * `_fold` adds n_partial_rows consecutive rows (of one or several matrices) in fixed order */
 int sw_colsum_partial(int dtype, int M, int N, const void* X, long ld, float* workspace, sw_stream_t stream);
@@ -428,11 +405,9 @@ int sw_convert_2d_t(int dtype, int rows, int cols, const float* src, long ld_src
 /* f32 NCHW -> dtype NHWC, channels zero padded to cpad (generic backbone entry, vgg.py:216-223 takes NCHW). */
 int sw_nchw_to_nhwc(int dtype, int N, int C, int H, int W, int cpad, const float* in_nchw, void* out_nhwc,
                     sw_stream_t stream);
-/* ReLU backward in place: grad = ref > 0 ? grad : 0  (F.relu_ backward, vgg.py:105-116). */
-int sw_relu_bwd(int dtype, long n, const void* ref, void* grad, sw_stream_t stream);
-/* The same into a separate buffer: out = ref > 0 ? grad : 0 (the backbone's entry gradient belongs to autograd and is not
- * modified; out == grad is allowed). */
-int sw_relu_bwd_out(int dtype, long n, const void* ref, const void* grad, void* out, sw_stream_t stream);
+/* ReLU backward: out = ref > 0 ? grad : 0  (F.relu_ backward, vgg.py:105-116).  out == grad is the in-place form; a separate out
+ * leaves grad alone (the backbone's entry gradient belongs to autograd). */
+int sw_relu_bwd(int dtype, long n, const void* ref, const void* grad, void* out, sw_stream_t stream);
 /* out[m][n] = in[m][n] * colscale[n] (f32 -> dtype): applies each loss term's cotangent to its logit columns. */
 int sw_scale_cols(int dtype, int M, int N, const float* in, long ld_in, const float* colscale, void* out,
                   long ld_out, sw_stream_t stream);
@@ -561,7 +536,7 @@ int sw_decode_boxes(long n, long n_boxes, const float* deltas, long ld_deltas, c
  * RPN proposal selection (detectron2/detectron2/modeling/proposal_generator/proposal_utils.py:22-130 find_top_rpn_proposals, up to its
  * batched_nms): for every image and level the pre_topk highest objectness logits (= sort(descending, stable)[:k]: ties -> ascending
  * anchor index), their boxes decoded (box_regression.py:88-116, weights4, scale_clamp), and the candidate rows written in the form
- * sw_detect_postprocess2 takes with "class" = level: image `i` owns rows [i * L * pre_topk, (i + 1) * L * pre_topk), level l the
+ * sw_detect_postprocess takes with "class" = level: image `i` owns rows [i * L * pre_topk, (i + 1) * L * pre_topk), level l the
  * pre_topk rows from l * pre_topk, in descending score order; cand_scores [rows][L + 1] = -inf except column l (-inf there too for
  * unused rows and for boxes that are empty after clipping to img_hw_dev[i] = (h, w): proposal_utils.py:96-106), cand_boxes
  * [rows][4 L] the box repeated.  finite_dev[i] = 0 if a selected box / logit is not finite (:86-94), else nonzero.

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("SW_LIB_PATH") or os.path.join(_HERE, "libsoswsod_hip.
 SW_F32, SW_BF16 = 0, 1
 
 c_int, c_long, c_float, c_void_p, c_u64 = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint64
+c_int32, c_uint32, c_double, c_longlong = ctypes.c_int32, ctypes.c_uint32, ctypes.c_double, ctypes.c_longlong
 
 
 class Epilogue(ctypes.Structure):
@@ -35,52 +36,52 @@ class Epilogue(ctypes.Structure):
 
 class WgradProblem(ctypes.Structure):
     """sw_wgrad_problem"""
-    _fields_ = [("nimg", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("Cin", ctypes.c_int), ("Cout", ctypes.c_int),
-                ("dilation", ctypes.c_int), ("nsplit", ctypes.c_int), ("x", ctypes.c_void_p), ("dy", ctypes.c_void_p),
-                ("slabs", ctypes.c_void_p)]
+    _fields_ = [("nimg", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("Cout", c_int),
+                ("dilation", c_int), ("nsplit", c_int), ("x", c_void_p), ("dy", c_void_p),
+                ("slabs", c_void_p)]
 
 
 class WgradFold(ctypes.Structure):
     """sw_wgrad_fold"""
-    _fields_ = [("Cin", ctypes.c_int), ("Cout", ctypes.c_int), ("nslab", ctypes.c_int), ("workspace", ctypes.c_void_p),
-                ("dw_oihw", ctypes.c_void_p)]
+    _fields_ = [("Cin", c_int), ("Cout", c_int), ("nslab", c_int), ("workspace", c_void_p),
+                ("dw_oihw", c_void_p)]
 
 
 class AugRecipe(ctypes.Structure):
     """sw_aug_recipe"""
-    _fields_ = [("seed", ctypes.c_uint64), ("key", ctypes.c_uint64), ("order", ctypes.c_int32 * 4), ("factor", ctypes.c_float * 4),
-                ("hue_shift", ctypes.c_int32), ("grayscale", ctypes.c_int32), ("blur_r", ctypes.c_int32),
-                ("blur_ww", ctypes.c_uint32), ("blur_fw", ctypes.c_uint32), ("rect", (ctypes.c_int32 * 4) * 3),
-                ("pad_", ctypes.c_int32)]
+    _fields_ = [("seed", c_u64), ("key", c_u64), ("order", c_int32 * 4), ("factor", c_float * 4),
+                ("hue_shift", c_int32), ("grayscale", c_int32), ("blur_r", c_int32),
+                ("blur_ww", c_uint32), ("blur_fw", c_uint32), ("rect", (c_int32 * 4) * 3),
+                ("pad_", c_int32)]
 
 
 class AugItem(ctypes.Structure):
     """sw_aug_item"""
-    _fields_ = [("src", ctypes.c_void_p), ("out", ctypes.c_void_p), ("tmp", ctypes.c_void_p), ("lsum", ctypes.c_void_p),
-                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("recipe", AugRecipe)]
+    _fields_ = [("src", c_void_p), ("out", c_void_p), ("tmp", c_void_p), ("lsum", c_void_p),
+                ("H", c_int32), ("W", c_int32), ("recipe", AugRecipe)]
 
 
 class GemmKKProblem(ctypes.Structure):
     """sw_gemm_kk_problem"""
-    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("slabs", ctypes.c_void_p), ("M", ctypes.c_int32), ("N", ctypes.c_int32),
-                ("K", ctypes.c_int32), ("nsplit", ctypes.c_int32), ("lda", ctypes.c_long), ("ldb", ctypes.c_long)]
+    _fields_ = [("A", c_void_p), ("B", c_void_p), ("slabs", c_void_p), ("M", c_int32), ("N", c_int32),
+                ("K", c_int32), ("nsplit", c_int32), ("lda", c_long), ("ldb", c_long)]
 
 
 class SplitkFold(ctypes.Structure):
     """sw_splitk_fold"""
-    _fields_ = [("M", ctypes.c_int32), ("N", ctypes.c_int32), ("nslab", ctypes.c_int32), ("accumulate", ctypes.c_int32),
-                ("workspace", ctypes.c_void_p), ("C", ctypes.c_void_p), ("ldc", ctypes.c_long), ("row_scale", ctypes.c_void_p)]
+    _fields_ = [("M", c_int32), ("N", c_int32), ("nslab", c_int32), ("accumulate", c_int32),
+                ("workspace", c_void_p), ("C", c_void_p), ("ldc", c_long), ("row_scale", c_void_p)]
 
 
 class ConvProblem(ctypes.Structure):
     """sw_conv_problem"""
-    _fields_ = [("nimg", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32),
-                ("in_", ctypes.c_void_p), ("wk", ctypes.c_void_p), ("out", ctypes.c_void_p), ("ep", ctypes.POINTER(Epilogue))]
+    _fields_ = [("nimg", c_int32), ("H", c_int32), ("W", c_int32), ("Cin", c_int32), ("Cout", c_int32),
+                ("in_", c_void_p), ("wk", c_void_p), ("out", c_void_p), ("ep", ctypes.POINTER(Epilogue))]
 
 
 class CopyDesc(ctypes.Structure):
     """sw_copy_desc"""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("bytes", ctypes.c_long)]
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("bytes", c_long)]
 
 
 class ColsumPart(ctypes.Structure):
@@ -92,12 +93,12 @@ class StageDesc(ctypes.Structure):
     """struct sw_stage_desc"""
     _fields_ = [("w", c_void_p), ("bn_weight", c_void_p), ("bn_bias", c_void_p), ("bn_mean", c_void_p), ("bn_var", c_void_p),
                 ("scale", c_void_p), ("shift", c_void_p), ("dst", c_void_p),
-                ("kind", ctypes.c_int32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("block_start", ctypes.c_int32)]
+                ("kind", c_int32), ("rows", c_int32), ("cols", c_int32), ("block_start", c_int32)]
 
 
 class ColsumFold(ctypes.Structure):
     """sw_colsum_fold_desc"""
-    _fields_ = [("N", ctypes.c_int), ("n_partial_rows", ctypes.c_int), ("workspace", ctypes.c_void_p), ("out", ctypes.c_void_p)]
+    _fields_ = [("N", c_int), ("n_partial_rows", c_int), ("workspace", c_void_p), ("out", c_void_p)]
 
 
 class SgdTensor(ctypes.Structure):
@@ -114,7 +115,7 @@ SGD_MAX_TENSORS = 24          # SW_SGD_MAX_TENSORS
 _EP = ctypes.POINTER(Epilogue)
 _F4 = ctypes.POINTER(c_float)
 
-# name -> (restype, argtypes); must list every symbol the header declares
+# name -> (restype, argtypes); lists every symbol the header declares (tests/test_cabi_cpu.py compares each row with its prototype)
 SIGNATURES = {
     "sw_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long,
                         _EP, c_int, c_void_p]),
@@ -123,7 +124,7 @@ SIGNATURES = {
     "sw_conv3x3_igemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, _EP,
                                  c_void_p]),
     "sw_conv3x3_wgrad": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_int, c_void_p]),
+                                 c_int, c_void_p, c_int, c_void_p]),
     "sw_conv3x3_wgrad_workspace_floats": (c_long, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "sw_conv_weight_prep": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sw_maxpool2x2_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -132,10 +133,8 @@ SIGNATURES = {
     "sw_preprocess": (c_int, [c_int, c_int, c_int, c_int, c_void_p, _F4, _F4, c_void_p, c_void_p]),
     "sw_preprocess_multi": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p), _F4, _F4, c_void_p, c_void_p]),
     "sw_roi_pool_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int,
-                                c_void_p, c_float, c_void_p, c_void_p, c_int, c_long, c_void_p]),
+                                c_void_p, c_float, c_void_p, c_void_p, c_int, c_long, c_void_p, c_long, c_void_p]),
     "sw_roi_pool_fwd_workspace_bytes": (c_long, [c_int, c_int, c_int, c_int]),
-    "sw_roi_pool_fwd_ws": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int,
-                                   c_void_p, c_float, c_void_p, c_void_p, c_int, c_long, c_void_p, c_long, c_void_p]),
     "sw_roi_pool_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_long, c_void_p, c_int,
                                 c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
     "sw_absmax": (c_int, [c_int, c_long, c_void_p, c_void_p, c_void_p]),
@@ -153,27 +152,17 @@ SIGNATURES = {
                                     c_void_p, c_void_p]),
     "sw_oicr_predict": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_int, c_int, c_void_p, _F4, c_float, c_void_p,
                                 c_void_p, c_void_p]),
-    "sw_detect_workspace_bytes": (c_long, [c_int, c_int]),
+    "sw_detect_workspace_bytes": (c_long, [c_int, c_int, c_int]),
     "sw_detect_postprocess": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "sw_detect_workspace_bytes2": (c_long, [c_int, c_int, c_int]),
-    "sw_detect_postprocess2": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
-    "sw_colsum": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
-    "sw_colsum_acc": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p]),
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "sw_colsum": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p]),
     "sw_colsum_workspace_floats": (c_long, [c_int, c_int, c_int]),
     "sw_colsum_partial": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p]),
     "sw_colsum_fold": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "sw_conv3x3_wgrad_scaled": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                        c_void_p, c_void_p]),
-    "sw_conv3x3_wgrad_acc": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                     c_void_p, c_int, c_void_p]),
-    "sw_conv3x3_wgrad_small": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "sw_conv3x3_wgrad_small_acc": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "sw_conv3x3_wgrad_small": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "sw_conv3x3_wgrad_slabs": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                        c_void_p]),
-    "sw_conv3x3_wgrad_fold": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "sw_conv3x3_wgrad_fold_acc": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "sw_conv3x3_wgrad_fold": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "sw_conv3x3_wgrad_fold_multi": (c_int, [c_int, ctypes.POINTER(WgradFold), c_void_p]),
     "sw_conv3x3_multi": (c_int, [c_int, c_int, ctypes.POINTER(ConvProblem), c_void_p]),
     "sw_gemm_kk_grouped": (c_int, [c_int, c_int, ctypes.POINTER(GemmKKProblem), c_void_p]),
@@ -185,8 +174,7 @@ SIGNATURES = {
     "sw_convert_2d": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p]),
     "sw_split_bf16x3": (c_int, [c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p]),
     "sw_nchw_to_nhwc": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "sw_relu_bwd": (c_int, [c_int, c_long, c_void_p, c_void_p, c_void_p]),
-    "sw_relu_bwd_out": (c_int, [c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sw_relu_bwd": (c_int, [c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sw_scale_cols": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p]),
     "sw_to_f32": (c_int, [c_int, c_long, c_void_p, c_void_p, c_void_p]),
     "sw_fill_zero": (c_int, [c_void_p, c_long, c_void_p]),
@@ -200,11 +188,11 @@ SIGNATURES = {
                                    c_void_p, c_long, c_void_p]),
     "sw_resize_pass_u8": (c_int, [c_int, c_int, c_int, c_long, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                   c_void_p, c_void_p]),
-    "sw_color_jitter_u8": (c_int, [c_int, c_int, c_int, c_void_p, c_float, ctypes.c_double, c_float, c_void_p, c_void_p, c_void_p]),
+    "sw_color_jitter_u8": (c_int, [c_int, c_int, c_int, c_void_p, c_float, c_double, c_float, c_void_p, c_void_p, c_void_p]),
     "sw_transpose_2d": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p]),
     "sw_stage_blocks": (c_int, [c_int, c_int, c_int]),
     "sw_stage_weights_multi": (c_int, [c_int, c_int, c_void_p, c_int, c_float, c_void_p]),
-    "sw_ema_multi": (c_int, [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_long), ctypes.c_double, c_void_p]),
+    "sw_ema_multi": (c_int, [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_long), c_double, c_void_p]),
     "sw_threshold_select": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p]),
     "sw_conv3x3_relu_pool2": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -212,8 +200,8 @@ SIGNATURES = {
     "sw_scale_scalars": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sw_counter_add": (c_int, [c_void_p, c_u64, c_void_p]),
     "sw_focal_loss": (c_int, [c_int, c_int, c_void_p, c_long, c_void_p, c_float, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
-    "sw_gaussian_blur_weights": (c_int, [c_float, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32),
-                                         ctypes.POINTER(ctypes.c_uint32)]),
+    "sw_gaussian_blur_weights": (c_int, [c_float, ctypes.POINTER(c_int32), ctypes.POINTER(c_uint32),
+                                         ctypes.POINTER(c_uint32)]),
     "sw_strong_aug_workspace_bytes": (c_long, [c_int, c_int]),
     "sw_strong_aug_u8": (c_int, [c_int, c_int, c_void_p, ctypes.POINTER(AugRecipe), c_void_p, c_void_p, c_void_p]),
     "sw_strong_aug_multi_u8": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -263,15 +251,15 @@ SIGNATURES = {
                                       c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, _F4, c_float, c_int,
                                       c_void_p, c_void_p, c_void_p]),
     # ---- Stage-2 pseudo labels (csrc/pseudo_labels.hip)
-    "sw_pgf_keep": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double,
-                            ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sw_pgf_keep": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double,
+                            c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     # ---- VOC evaluation (csrc/evaluation.hip)
-    "sw_voc_eval_workspace_bytes": (ctypes.c_longlong, [c_int, c_int, ctypes.c_longlong, ctypes.c_longlong]),
-    "sw_voc_eval": (c_int, [c_int, c_int, ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+    "sw_voc_eval_workspace_bytes": (c_longlong, [c_int, c_int, c_longlong, c_longlong]),
+    "sw_voc_eval": (c_int, [c_int, c_int, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # ---- COCO evaluation (csrc/evaluation.hip)
-    "sw_coco_eval_workspace_bytes": (ctypes.c_longlong, [c_int, ctypes.c_longlong, c_int]),
-    "sw_coco_eval": (c_int, [c_int, ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int]
+    "sw_coco_eval_workspace_bytes": (c_longlong, [c_int, c_longlong, c_int]),
+    "sw_coco_eval": (c_int, [c_int, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_int]
                      + [c_void_p] * 18),
     "sw_version": (ctypes.c_char_p, []),
 }

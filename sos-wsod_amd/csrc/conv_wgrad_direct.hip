@@ -22,7 +22,7 @@
 //     (counted vmcnt), one barrier per step, placed after tap 3 — no wave opens a step by waiting for LDS;
 //   * work items = (problem, pixel split, block): the step list (image, strip, row) of a problem is cut into `nsplit` ranges, each range
 //     x block writes its partial [64][9][64] tile into the range's slab with plain stores — the slab layout and the ordered fold of the
-//     implicit-GEMM path (sw_conv3x3_wgrad_fold*) are unchanged, results are deterministic.
+//     implicit-GEMM path (sw_conv3x3_wgrad_fold, sw_conv3x3_wgrad_fold_multi) are unchanged, results are deterministic.
 // History of the round (profiles/r06_wgrad_*): one 8-wave workgroup per CU (128 x 64 blocks) ran 0.21-0.29 of peak — the two waves of a SIMD
 // sat in the same phase of the same program; two independent 4-wave workgroups 0.30-0.39; the compiler's s_waitcnt vmcnt(0) in front of the
 // first transposed read after every DMA issue (dma16 below) was the rest: 0.45-0.50 of peak by the layers' true FLOP, MFMA pipe 63 % busy.

@@ -1052,7 +1052,7 @@ extern "C" int sw_nchw_to_nhwc(int dtype, int N, int C, int H, int W, int cpad, 
   return 0;
 }
 
-extern "C" int sw_relu_bwd_out(int dtype, long n, const void* ref, const void* grad, void* out, hipStream_t stream) {
+extern "C" int sw_relu_bwd(int dtype, long n, const void* ref, const void* grad, void* out, hipStream_t stream) {
   SW_ENTER();
   if (n <= 0) return 0;
   {
@@ -1071,10 +1071,6 @@ extern "C" int sw_relu_bwd_out(int dtype, long n, const void* ref, const void* g
     hipLaunchKernelGGL(relu_bwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, n, (const float*)ref, (const float*)grad, (float*)out));
   SW_CHECK_LAUNCH();
   return 0;
-}
-
-extern "C" int sw_relu_bwd(int dtype, long n, const void* ref, void* grad, hipStream_t stream) {
-  return sw_relu_bwd_out(dtype, n, ref, grad, grad, stream);
 }
 
 extern "C" int sw_scale_cols(int dtype, int M, int N, const float* in, long ld_in, const float* colscale, void* out,
@@ -1183,12 +1179,8 @@ extern "C" int sw_colsum_fold_multi(int n, const sw_colsum_fold_desc* folds, hip
   return 0;
 }
 
-extern "C" int sw_colsum(int dtype, int M, int N, const void* X, long ld, float* out, float* workspace, hipStream_t stream) {
-  return sw_colsum_acc(dtype, M, N, X, ld, out, workspace, 0, stream);
-}
-
-extern "C" int sw_colsum_acc(int dtype, int M, int N, const void* X, long ld, float* out, float* workspace, int accumulate,
-                             hipStream_t stream) {
+extern "C" int sw_colsum(int dtype, int M, int N, const void* X, long ld, float* out, float* workspace, int accumulate,
+                         hipStream_t stream) {
   SW_ENTER();
   if (N <= 0) return 0;
   if (dtype != SW_BF16 && dtype != SW_F32) return -1;

@@ -1434,20 +1434,9 @@ extern "C" int sw_conv3x3_wgrad_slabs(int dtype, int nimg, int H, int W, int Cin
                           : dispatch_modes<float>(g, OP_KSTRIDED, OP_CONV_B, nslab, stream);
 }
 
-static int wgrad_fold_impl(int Cin, int Cout, int nslab, const float* workspace, float* dw_oihw, const float* cout_scale,
-                           hipStream_t stream, int accumulate = 0);
-extern "C" int sw_conv3x3_wgrad_fold(int Cin, int Cout, int nslab, const float* workspace, float* dw_oihw,
-                                     hipStream_t stream) {
+extern "C" int sw_conv3x3_wgrad_fold(int Cin, int Cout, int nslab, const float* workspace, float* dw_oihw, const float* cout_scale,
+                                     int accumulate, hipStream_t stream) {
   SW_ENTER();
-  return wgrad_fold_impl(Cin, Cout, nslab, workspace, dw_oihw, nullptr, stream);
-}
-extern "C" int sw_conv3x3_wgrad_fold_acc(int Cin, int Cout, int nslab, const float* workspace, float* dw_oihw, const float* cout_scale,
-                                        int accumulate, hipStream_t stream) {
-  SW_ENTER();
-  return wgrad_fold_impl(Cin, Cout, nslab, workspace, dw_oihw, cout_scale, stream, accumulate);
-}
-static int wgrad_fold_impl(int Cin, int Cout, int nslab, const float* workspace, float* dw_oihw, const float* cout_scale,
-                           hipStream_t stream, int accumulate) {
   if (nslab < 1 || (Cin % 4)) return -5;
   if ((size_t)36 * Cin > 65536 || (((uintptr_t)dw_oihw) & 15) || (((uintptr_t)workspace) & 15)) return -5;
   int parts = 1;                                              // input-channel ranges per output channel: >= 1024 workgroups
@@ -1672,23 +1661,11 @@ extern "C" int sw_conv3x3_wgrad_fold_multi(int n, const sw_wgrad_fold* folds, hi
 }
 
 extern "C" int sw_conv3x3_wgrad(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x,
-                                const void* dy, float* dw_oihw, float* workspace, int splitk, hipStream_t stream) {
-  return sw_conv3x3_wgrad_scaled(dtype, nimg, H, W, Cin, Cout, dilation, x, dy, dw_oihw, workspace, splitk, nullptr, stream);
-}
-
-extern "C" int sw_conv3x3_wgrad_scaled(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x,
-                                       const void* dy, float* dw_oihw, float* workspace, int splitk, const float* cout_scale,
-                                       hipStream_t stream) {
-  return sw_conv3x3_wgrad_acc(dtype, nimg, H, W, Cin, Cout, dilation, x, dy, dw_oihw, workspace, splitk, cout_scale, 0, stream);
-}
-
-extern "C" int sw_conv3x3_wgrad_acc(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x,
-                                    const void* dy, float* dw_oihw, float* workspace, int splitk, const float* cout_scale,
-                                    int accumulate, hipStream_t stream) {
+                                const void* dy, float* dw_oihw, float* workspace, int splitk, const float* cout_scale,
+                                int accumulate, hipStream_t stream) {
   const int rc = sw_conv3x3_wgrad_slabs(dtype, nimg, H, W, Cin, Cout, dilation, x, dy, workspace, splitk, stream);
   if (rc) return rc;
   const long nelem = (long)Cout * 9 * Cin;
   const int nslab = (int)(sw_conv3x3_wgrad_workspace_floats(dtype, nimg, H, W, Cin, Cout, splitk) / nelem);
-  if (nslab < 1 || (Cin % 4)) return -5;
-  return wgrad_fold_impl(Cin, Cout, nslab, workspace, dw_oihw, cout_scale, stream, accumulate);
+  return sw_conv3x3_wgrad_fold(Cin, Cout, nslab, workspace, dw_oihw, cout_scale, accumulate, stream);
 }

@@ -739,7 +739,7 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
   __syncthreads();
   bitonic_sort<true>(keys, NPV);
   if (nvalid) {
-    // mask form on offer (sw_detect_postprocess2): a class with mask_min or more candidates hands its sorted list to det_mask_kernel /
+    // mask form on offer (sw_detect_postprocess): a class with mask_min or more candidates hands its sorted list to det_mask_kernel /
     // det_resolve_kernel (nvalid = count); a smaller one is finished right here (nvalid = -1: the two kernels skip it)
     if (nv >= mask_min) {
       for (int u = tid; u < nv; u += blockDim.x) {
@@ -1164,10 +1164,10 @@ extern "C" int sw_oicr_predict(int R, int K, int refine_k, const float* logits, 
   return 0;
 }
 
-extern "C" long sw_detect_workspace_bytes(int K, int topk) { return (long)K * topk * 8 + (long)K * 4 + 64; }
-
 namespace {
 inline long align256(long v) { return (v + 255) / 256 * 256; }
+// workspace of the per-class form: maxcoord (+pad) | cls_count [K] | cls_rows [K][topk] | cls_scores [K][topk]; the mask form's part follows it
+inline long detect_base_bytes(int K, int topk) { return align256((long)K * topk * 8 + (long)K * 4 + 64); }
 // extra workspace of the mask form: nvalid[K] | sorted keys [K][R] | sorted boxes [K][R] float4 | MT [K][NB][R] u64; 0 = not offered
 inline long detect_mask_bytes(int R, int K) {
   if (R < 1 || K < 1 || R > 16384) return 0;
@@ -1178,14 +1178,13 @@ inline long detect_mask_bytes(int R, int K) {
 }
 }  // namespace
 
-extern "C" long sw_detect_workspace_bytes2(int R, int K, int topk) {
-  return align256(sw_detect_workspace_bytes(K, topk)) + detect_mask_bytes(R, K);
-}
+extern "C" long sw_detect_workspace_bytes(int R, int K, int topk) { return detect_base_bytes(K, topk) + detect_mask_bytes(R, K); }
 
-static int detect_postprocess_impl(int R, int K, const float* all_scores, const float* all_boxes, int img_h, int img_w,
-                                   float score_thresh, float nms_thresh, int topk, int32_t* det_count, float* det_boxes,
-                                   float* det_scores, int32_t* det_classes, int32_t* det_rows, void* workspace, long workspace_bytes,
-                                   hipStream_t stream) {
+extern "C" int sw_detect_postprocess(int R, int K, const float* all_scores, const float* all_boxes, int img_h, int img_w,
+                                     float score_thresh, float nms_thresh, int topk, int32_t* det_count, float* det_boxes,
+                                     float* det_scores, int32_t* det_classes, int32_t* det_rows, void* workspace,
+                                     long workspace_bytes, hipStream_t stream) {
+  SW_ENTER();
   if (R > 16384 || (long)K * topk > 16384 || topk < 1) return -6;
   char* ws = (char*)workspace;
   float* maxcoord = (float*)ws;                                    // [1] (+pad)
@@ -1202,7 +1201,7 @@ static int detect_postprocess_impl(int R, int K, const float* all_scores, const 
   SW_CHECK_LAUNCH();
   int np = 64; while (np < R) np <<= 1;
   constexpr int mask_min = 256;
-  const long base = align256(sw_detect_workspace_bytes(K, topk)), mask_need = detect_mask_bytes(R, K);
+  const long base = detect_base_bytes(K, topk), mask_need = detect_mask_bytes(R, K);
   const bool mask = mask_need > 0 && workspace_bytes >= base + mask_need && R >= mask_min;
   char* m = ws + base;
   int* nvalid = mask ? (int*)m : nullptr; m += align256((long)K * 4);
@@ -1235,22 +1234,4 @@ static int detect_postprocess_impl(int R, int K, const float* all_scores, const 
                      cls_count, cls_rows, cls_scores, det_count, det_boxes, det_scores, det_classes, det_rows);
   SW_CHECK_LAUNCH();
   return 0;
-}
-
-extern "C" int sw_detect_postprocess(int R, int K, const float* all_scores, const float* all_boxes, int img_h, int img_w,
-                                     float score_thresh, float nms_thresh, int topk, int32_t* det_count, float* det_boxes,
-                                     float* det_scores, int32_t* det_classes, int32_t* det_rows, void* workspace,
-                                     hipStream_t stream) {
-  SW_ENTER();
-  return detect_postprocess_impl(R, K, all_scores, all_boxes, img_h, img_w, score_thresh, nms_thresh, topk, det_count, det_boxes,
-                                 det_scores, det_classes, det_rows, workspace, 0, stream);
-}
-
-extern "C" int sw_detect_postprocess2(int R, int K, const float* all_scores, const float* all_boxes, int img_h, int img_w,
-                                      float score_thresh, float nms_thresh, int topk, int32_t* det_count, float* det_boxes,
-                                      float* det_scores, int32_t* det_classes, int32_t* det_rows, void* workspace,
-                                      long workspace_bytes, hipStream_t stream) {
-  SW_ENTER();
-  return detect_postprocess_impl(R, K, all_scores, all_boxes, img_h, img_w, score_thresh, nms_thresh, topk, det_count, det_boxes,
-                                 det_scores, det_classes, det_rows, workspace, workspace_bytes, stream);
 }

@@ -1043,8 +1043,8 @@ extern "C" int sw_wsddn_scores_bwd(int R, int K, const float* logits, long ld, c
   return 0;
 }
 
-extern "C" int sw_conv3x3_wgrad_small_acc(int dtype, int nimg, int H, int W, int Cin, int Cout, const void* x, const void* dy,
-                                          const float* cout_scale, float* dw_oihw, int accumulate, hipStream_t stream) {
+extern "C" int sw_conv3x3_wgrad_small(int dtype, int nimg, int H, int W, int Cin, int Cout, const void* x, const void* dy,
+                                      const float* cout_scale, float* dw_oihw, int accumulate, hipStream_t stream) {
   SW_ENTER();
   if (nimg < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (long)nimg * H * W > 4096) return -5;
   const long blocks = ((long)Cout * Cin + 255) / 256;
@@ -1057,9 +1057,4 @@ extern "C" int sw_conv3x3_wgrad_small_acc(int dtype, int nimg, int H, int W, int
   else return -1;
   SW_CHECK_LAUNCH();
   return 0;
-}
-
-extern "C" int sw_conv3x3_wgrad_small(int dtype, int nimg, int H, int W, int Cin, int Cout, const void* x, const void* dy,
-                                      const float* cout_scale, float* dw_oihw, hipStream_t stream) {
-  return sw_conv3x3_wgrad_small_acc(dtype, nimg, H, W, Cin, Cout, x, dy, cout_scale, dw_oihw, 0, stream);
 }

@@ -959,7 +959,7 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Forward, ROW SPARSE TABLE form over a PREPARED TASK LIST (round 6; sw_roi_pool_fwd_ws with a workspace).
+// Forward, ROW SPARSE TABLE form over a PREPARED TASK LIST (round 6; sw_roi_pool_fwd with a workspace).
 //
 // The sparse-table kernel above spends half of a workgroup's cycles outside the scan on large maps (99x165 / 8000 ROIs, phase
 // clocks in profiles/r06_roi_phases.txt: ROI sort 5 %, per-chunk bin tables + owned-pair lists 29 %, barriers behind the chunk
@@ -1508,7 +1508,7 @@ int launch_fwd_sparse(int nimg, int H, int W, int C, long ld, int PH, int PW, fl
                                             S, rows, n_bands, nz, SP_CH, stream);
 }
 
-// prepared-task form (sw_roi_pool_fwd_ws): workspace = [nimg][TK_MAXB][TK_SEG] ints, then [nimg][R * PH] task records of 32 bytes
+// prepared-task form (sw_roi_pool_fwd with a workspace): workspace = [nimg][TK_MAXB][TK_SEG] ints, then [nimg][R * PH] task records of 32 bytes
 inline size_t tasks_seg_bytes(int nimg) { return (((size_t)nimg * TK_MAXB * TK_SEG * 4) + 255) & ~(size_t)255; }
 inline size_t tasks_geo_bytes(int R) { return (((size_t)R * sizeof(RoiGeo)) + 255) & ~(size_t)255; }
 inline size_t tasks_hist_bytes(int nimg, int R) {
@@ -1693,15 +1693,7 @@ extern "C" long sw_roi_pool_fwd_workspace_bytes(int nimg, int R, int PH, int PW)
 extern "C" int sw_roi_pool_fwd(int dtype, int nimg, int H, int W, int C, int PH, int PW, float spatial_scale,
                                const void* feat, const float* rois, int R, const float* row_scale,
                                float row_scale_add, void* out, void* argmax, int argmax_bits, long ld_out,
-                               hipStream_t stream) {
-  return sw_roi_pool_fwd_ws(dtype, nimg, H, W, C, PH, PW, spatial_scale, feat, rois, R, row_scale, row_scale_add, out, argmax,
-                            argmax_bits, ld_out, nullptr, 0, stream);
-}
-
-extern "C" int sw_roi_pool_fwd_ws(int dtype, int nimg, int H, int W, int C, int PH, int PW, float spatial_scale,
-                                  const void* feat, const float* rois, int R, const float* row_scale,
-                                  float row_scale_add, void* out, void* argmax, int argmax_bits, long ld_out,
-                                  void* workspace, long workspace_bytes, hipStream_t stream) {
+                               void* workspace, long workspace_bytes, hipStream_t stream) {
   SW_ENTER();
   if (R <= 0) return 0;
   const long ld = ld_out > 0 ? ld_out : (long)C * PH * PW;

@@ -1314,7 +1314,7 @@ class PseudoLabRPN(nn.Module):
     @torch.no_grad()
     def predict_proposals(self, anchors, logits, deltas, image_sizes):
         """detectron2 rpn.py:478-533 + proposal_utils.py:20-130: per-level top-k (sort, stable: ties -> ascending index), decode, clip, drop
-        empty boxes (sw_rpn_select_pack), NMS per level (sw_detect_postprocess2 with level = class), the best post_nms_topk per image.
+        empty boxes (sw_rpn_select_pack), NMS per level (sw_detect_postprocess with level = class), the best post_nms_topk per image.
         logits (N, At), deltas (N, At, 4) in anchor order.  ONE host read per call: the images' proposal counts and finite flags."""
         N = logits.shape[0]
         dev = logits.device

@@ -4,7 +4,6 @@ torch is used here only for device memory and the current HIP stream; every comp
 hand-written gfx950 kernel.  All tensors must live on the GPU and be contiguous where stated.
 """
 import ctypes
-import os
 
 import torch
 
@@ -13,6 +12,17 @@ from ._lib import SW_BF16, SW_F32, Epilogue, check, lib
 
 def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _floats(vals, n):
+    """HOST float[n] argument (configuration constants passed by value into a launch)"""
+    return (ctypes.c_float * n)(*[float(v) for v in vals])
+
+
+def _workspace256(nbytes, device):
+    """-> (uint8 tensor that owns the memory, pointer to `nbytes` bytes inside it on a 256-byte boundary)"""
+    ws = torch.empty(nbytes + 256, device=device, dtype=torch.uint8)
+    return ws, ctypes.c_void_p((ws.data_ptr() + 255) // 256 * 256)
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -117,8 +127,6 @@ def worker_stream(role, device=None):
     many models had lived in the process before (bench.py's extras).  Sharing a role's stream between models only adds ordering."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    if os.environ.get("SW_FRESH_STREAMS") == "1":                   # development switch: a new pool stream per call (the old behaviour)
-        return torch.cuda.Stream(device=torch.device("cuda", idx))
     got = _WORKER_STREAMS.get(idx)
     if got is None:
         got = _WORKER_STREAMS[idx] = {r: torch.cuda.Stream(device=torch.device("cuda", idx)) for r in _WORKER_ROLES}
@@ -395,8 +403,8 @@ def conv3x3_wgrad(x, dy, dw_oihw, dilation, splitk=1, workspace=None, tag=None, 
     need = int(lib.sw_conv3x3_wgrad_workspace_floats(dt(x), n, H, W, Cin, Cout, splitk))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, device=x.device, dtype=torch.float32)
-    check(_launch(tag, lambda: lib.sw_conv3x3_wgrad_acc(dt(x), n, H, W, Cin, Cout, dilation, _p(x), _p(dy), _p(dw_oihw),
-                                                        _p(workspace), splitk, _p(cout_scale), int(accumulate), _stream())), "sw_conv3x3_wgrad")
+    check(_launch(tag, lambda: lib.sw_conv3x3_wgrad(dt(x), n, H, W, Cin, Cout, dilation, _p(x), _p(dy), _p(dw_oihw),
+                                                    _p(workspace), splitk, _p(cout_scale), int(accumulate), _stream())), "sw_conv3x3_wgrad")
     return dw_oihw
 
 
@@ -405,8 +413,8 @@ def conv3x3_wgrad_small(x, dy, dw_oihw, cout_scale=None, accumulate=False):
     (accumulate: added to dw)"""
     _need_gpu(x, dy, dw_oihw)
     n, H, W, Cin = x.shape
-    check(lib.sw_conv3x3_wgrad_small_acc(dt(x), n, H, W, Cin, dy.shape[3], _p(x), _p(dy), _p(cout_scale), _p(dw_oihw), int(accumulate),
-                                         _stream()), "sw_conv3x3_wgrad_small")
+    check(lib.sw_conv3x3_wgrad_small(dt(x), n, H, W, Cin, dy.shape[3], _p(x), _p(dy), _p(cout_scale), _p(dw_oihw), int(accumulate),
+                                     _stream()), "sw_conv3x3_wgrad_small")
     return dw_oihw
 
 
@@ -452,7 +460,7 @@ def conv3x3_wgrad_grouped(problems, tag=None):
 def conv3x3_wgrad_fold(workspace, nslab, dw_oihw, cout_scale=None, accumulate=False):
     """dw_oihw (Cout, Cin, 3, 3) f32 = (+=, accumulate) cout_scale[co] * ordered sum of `nslab` consecutive [co][tap][ci] slabs"""
     Cout, Cin = dw_oihw.shape[:2]
-    check(lib.sw_conv3x3_wgrad_fold_acc(Cin, Cout, nslab, _p(workspace), _p(dw_oihw), _p(cout_scale), int(accumulate), _stream()),
+    check(lib.sw_conv3x3_wgrad_fold(Cin, Cout, nslab, _p(workspace), _p(dw_oihw), _p(cout_scale), int(accumulate), _stream()),
           "sw_conv3x3_wgrad_fold")
     return dw_oihw
 
@@ -573,8 +581,7 @@ def maxpool_bwd(x, dout, din, stride, relu_mask):
 def preprocess(img_u8_chw, out_hwc, mean, std):
     _need_gpu(img_u8_chw, out_hwc)
     H, W, cpad = out_hwc.shape
-    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
-    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    m, s = _floats(mean, 3), _floats(std, 3)
     check(lib.sw_preprocess(dt(out_hwc), H, W, cpad, _p(img_u8_chw), m, s, _p(out_hwc), _stream()), "sw_preprocess")
     return out_hwc
 
@@ -585,35 +592,29 @@ def preprocess_multi(imgs_u8_chw, out_nhwc, mean, std):
     n, H, W, cpad = out_nhwc.shape
     assert len(imgs_u8_chw) == n and all(im.is_contiguous() and tuple(im.shape) == (3, H, W) for im in imgs_u8_chw)
     ptrs = (ctypes.c_void_p * n)(*[im.data_ptr() for im in imgs_u8_chw])
-    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
-    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    m, s = _floats(mean, 3), _floats(std, 3)
     check(lib.sw_preprocess_multi(dt(out_nhwc), n, H, W, cpad, ptrs, m, s, _p(out_nhwc), _stream()), "sw_preprocess_multi")
     return out_nhwc
 
 
 def roi_pool_fwd_workspace(n, R, PH, PW, device):
-    """scratch for roi_pool_fwd's prepared-task form (sw_roi_pool_fwd_ws); uint8, 256-byte aligned by the allocator"""
+    """scratch for roi_pool_fwd's prepared-task form; uint8, 256-byte aligned by the allocator"""
     return torch.empty(max(16, lib.sw_roi_pool_fwd_workspace_bytes(n, R, PH, PW)), device=device, dtype=torch.uint8)
 
 
 def roi_pool_fwd(feat, rois, out, argmax, spatial_scale, PH, PW, row_scale=None, row_scale_add=0.0, tag=None, workspace="auto"):
     """feat [n][H][W][C], rois [R][5] f32, out [R][C*PH*PW]; argmax same shape, int32 (h*W+w or -1) or int16/uint16
     storage holding uint16 (h*W+w or 0xFFFF; see argmax_to_int32).  workspace: roi_pool_fwd_workspace(...) tensor, "auto" = allocate
-    one here (caching allocator: graph-safe), None = the entry without workspace (sw_roi_pool_fwd)"""
+    one here (caching allocator: graph-safe), None = the forms without prepared tasks"""
     _need_gpu(feat, rois, out, argmax)
     n, H, W, C = feat.shape
     R = rois.shape[0]
     if isinstance(workspace, str):
         workspace = roi_pool_fwd_workspace(n, R, PH, PW, feat.device) if R > 0 else None
-    if workspace is None:
-        check(_launch(tag, lambda: lib.sw_roi_pool_fwd(dt(feat), n, H, W, C, PH, PW, float(spatial_scale), _p(feat), _p(rois), R,
-                                                       _p(row_scale), float(row_scale_add), _p(out), _p(argmax), _argmax_bits(argmax),
-                                                       _roi_pitch(out, argmax), _stream())), "sw_roi_pool_fwd")
-    else:
-        check(_launch(tag, lambda: lib.sw_roi_pool_fwd_ws(dt(feat), n, H, W, C, PH, PW, float(spatial_scale), _p(feat), _p(rois), R,
-                                                          _p(row_scale), float(row_scale_add), _p(out), _p(argmax), _argmax_bits(argmax),
-                                                          _roi_pitch(out, argmax), _p(workspace), workspace.numel(), _stream())),
-              "sw_roi_pool_fwd_ws")
+    check(_launch(tag, lambda: lib.sw_roi_pool_fwd(dt(feat), n, H, W, C, PH, PW, float(spatial_scale), _p(feat), _p(rois), R,
+                                                   _p(row_scale), float(row_scale_add), _p(out), _p(argmax), _argmax_bits(argmax),
+                                                   _roi_pitch(out, argmax), _p(workspace),
+                                                   0 if workspace is None else workspace.numel(), _stream())), "sw_roi_pool_fwd")
     return out, argmax
 
 
@@ -762,7 +763,7 @@ def oicr_refine_loss(logits, V, R, K, cls_col, box_col, boxes, lab_class, lab_we
                      loss_view, dlogits=None, grad_scale=None, workspace=None, n_rounds=1, col_stride=0):
     """n_rounds heads at columns cls_col/box_col + k*col_stride; lab_* [n_rounds][R]; loss_view [n_rounds][2][V];
     grad_scale device float[2*n_rounds]"""
-    rw = (ctypes.c_float * 4)(*[float(v) for v in reg_weights])
+    rw = _floats(reg_weights, 4)
     if workspace is None:
         workspace = torch.empty(n_rounds * 2 * V * R, device=logits.device, dtype=torch.float32)
     check(lib.sw_oicr_refine_loss(V, R, K, n_rounds, _p(logits), logits.stride(0), cls_col, box_col, col_stride, _p(boxes),
@@ -776,7 +777,7 @@ def colsum(X, M, N, out, ld=None, accumulate=False):
     accumulate: out[n] += the sum"""
     need = int(lib.sw_colsum_workspace_floats(dt(X), M, N))
     ws = torch.empty(max(need, 4), device=X.device, dtype=torch.float32)
-    check(lib.sw_colsum_acc(dt(X), M, N, _p(X), X.stride(0) if ld is None else ld, _p(out), _p(ws), int(accumulate), _stream()), "sw_colsum")
+    check(lib.sw_colsum(dt(X), M, N, _p(X), X.stride(0) if ld is None else ld, _p(out), _p(ws), int(accumulate), _stream()), "sw_colsum")
     return out
 
 
@@ -1060,7 +1061,7 @@ def weighted_sum(values, weights, out):
     _need_gpu(out, *values)
     assert all(v.dtype == torch.float32 and v.numel() == 1 for v in values) and out.dtype == torch.float32 and out.numel() >= n + 1
     ptrs = (ctypes.c_void_p * n)(*[v.data_ptr() for v in values])
-    ws = (ctypes.c_float * n)(*[float(w) for w in weights])
+    ws = _floats(weights, n)
     check(lib.sw_weighted_sum(n, ptrs, ws, _p(out), _stream()), "sw_weighted_sum")
     return out
 
@@ -1069,7 +1070,7 @@ def scale_scalars(g, weights, out):
     """out[i] = g * weights[i] (sw_scale_scalars)"""
     n = len(weights)
     _need_gpu(g, out)
-    ws = (ctypes.c_float * n)(*[float(w) for w in weights])
+    ws = _floats(weights, n)
     check(lib.sw_scale_scalars(n, _p(g), ws, _p(out), _stream()), "sw_scale_scalars")
     return out
 
@@ -1137,7 +1138,7 @@ def nchw_to_nhwc(x_nchw_f32, out_nhwc):
 def relu_bwd(ref, grad, out=None):
     """out = ref > 0 ? grad : 0; in place on `grad` when no `out` is given"""
     out = grad if out is None else out
-    check(lib.sw_relu_bwd_out(dt(grad), grad.numel(), _p(ref), _p(grad), _p(out), _stream()), "sw_relu_bwd_out")
+    check(lib.sw_relu_bwd(dt(grad), grad.numel(), _p(ref), _p(grad), _p(out), _stream()), "sw_relu_bwd")
     return out
 
 
@@ -1148,7 +1149,7 @@ def scale_cols(src_f32, colscale, dst, M, N):
 
 
 def oicr_predict(logits, R, K, refine_k, base_col, round_stride, boxes, reg_weights, scale_clamp, all_scores, all_boxes):
-    rw = (ctypes.c_float * 4)(*[float(v) for v in reg_weights])
+    rw = _floats(reg_weights, 4)
     check(lib.sw_oicr_predict(R, K, refine_k, _p(logits), logits.stride(0), base_col, round_stride, _p(boxes), rw,
                               float(scale_clamp), _p(all_scores), _p(all_boxes), _stream()), "sw_oicr_predict")
 
@@ -1165,11 +1166,11 @@ def detect_postprocess(all_scores, all_boxes, img_h, img_w, score_thresh, nms_th
         cnt = torch.zeros(1, device=dev, dtype=torch.int32)
         boxes = torch.zeros(topk, 4, device=dev); scores = torch.zeros(topk, device=dev)
         classes = torch.zeros(topk, device=dev, dtype=torch.int32); rows = torch.zeros(topk, device=dev, dtype=torch.int32)
-    nbytes = int(lib.sw_detect_workspace_bytes2(R, K, topk))
+    nbytes = int(lib.sw_detect_workspace_bytes(R, K, topk))
     ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    check(lib.sw_detect_postprocess2(R, K, _p(all_scores), _p(all_boxes), int(img_h), int(img_w), float(score_thresh),
-                                     float(nms_thresh), int(topk), _p(cnt), _p(boxes), _p(scores), _p(classes), _p(rows), _p(ws),
-                                     nbytes, _stream()), "sw_detect_postprocess2")
+    check(lib.sw_detect_postprocess(R, K, _p(all_scores), _p(all_boxes), int(img_h), int(img_w), float(score_thresh),
+                                    float(nms_thresh), int(topk), _p(cnt), _p(boxes), _p(scores), _p(classes), _p(rows), _p(ws),
+                                    nbytes, _stream()), "sw_detect_postprocess")
     return cnt, boxes, scores, classes, rows
 
 
@@ -1179,7 +1180,7 @@ def preprocess_pad(img_u8_chw, out_hw4, mean, std):
     _need_gpu(img_u8_chw, out_hw4)
     h, w = img_u8_chw.shape[1:]
     H, W = out_hw4.shape[:2]
-    m = (ctypes.c_float * 3)(*[float(v) for v in mean]); s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    m, s = _floats(mean, 3), _floats(std, 3)
     check(lib.sw_preprocess_pad(dt(out_hw4), h, w, H, W, _p(img_u8_chw), m, s, _p(out_hw4), _stream()), "sw_preprocess_pad")
     return out_hw4
 
@@ -1336,7 +1337,7 @@ def roi_assign_levels(boxes_base, row_cnt, box_off_floats):
 def decode_boxes(deltas, boxes, weights, scale_clamp, out):
     """deltas (n, >=4) f32 rows; boxes (n_boxes, 4), row i uses boxes[i % n_boxes]; out (n, 4)"""
     _need_gpu(deltas, boxes, out)
-    rw = (ctypes.c_float * 4)(*[float(v) for v in weights])
+    rw = _floats(weights, 4)
     check(lib.sw_decode_boxes(out.shape[0], boxes.shape[0], _p(deltas), deltas.stride(0), _p(boxes), rw, float(scale_clamp), _p(out),
                               _stream()), "sw_decode_boxes")
     return out
@@ -1346,7 +1347,7 @@ def rpn_select_pack(logits, deltas, anchors, pre_topk, weights, scale_clamp, img
     """RPN proposal selection up to the NMS (sw_rpn_select_pack).  anchors: per level (n_l, 4); img_hw_dev (N, 2) int32 device;
     logits / deltas: either per-level lists ((N, n_l) / (N, n_l, 4) f32, each dense) or ONE pair (N, At) / (N, At, 4) in anchor order
     (ops.rpn_unpack) whose column ranges are the levels.  -> cand_scores (N, L * pre_topk, L + 1), cand_boxes (N, L * pre_topk, 4 L) in
-    sw_detect_postprocess2's form (class = level), finite (N,) int32 (a slice of ints_out when given)"""
+    sw_detect_postprocess's form (class = level), finite (N,) int32 (a slice of ints_out when given)"""
     L = len(anchors)
     dev = anchors[0].device
     n_list = [int(a.shape[0]) for a in anchors]
@@ -1374,7 +1375,7 @@ def rpn_select_pack(logits, deltas, anchors, pre_topk, weights, scale_clamp, img
     sc = torch.empty(N, rows, L + 1, device=dev); bx = torch.empty(N, rows, 4 * L, device=dev)
     fin = ints_out if ints_out is not None else torch.empty(N, device=dev, dtype=torch.int32)
     sel = torch.empty(N * L, pre_topk, device=dev, dtype=torch.int32)
-    rw = (ctypes.c_float * 4)(*[float(v) for v in weights])
+    rw = _floats(weights, 4)
     check(lib.sw_rpn_select_pack(N, L, arr(lp), arr(dp), arr([a.data_ptr() for a in anchors]), n_l, stride, int(pre_topk), rw,
                                  float(scale_clamp), _p(img_hw_dev), _p(sc), _p(bx), _p(fin), _p(sel), _p(ws), nbytes, _stream()),
           "sw_rpn_select_pack")
@@ -1428,7 +1429,7 @@ def roi_label_sample(p_cnt_dev, proposals, gt_boxes, gt_classes_i32, gt_counts, 
 def rpn_loss(logits, deltas, labels_i8, anchors, matched_gt, weights, inv_norm, losses2, dlogits=None, ddeltas=None):
     """logits (n,), deltas (n, 4), labels int8 (n,), anchors (A, 4) repeating over the images, matched_gt (n, 4) -> losses2 (2,)"""
     _need_gpu(logits, deltas, labels_i8, anchors, matched_gt, losses2)
-    rw = (ctypes.c_float * 4)(*[float(v) for v in weights])
+    rw = _floats(weights, 4)
     ws = torch.empty(int(lib.sw_rpn_loss_workspace_floats()), device=logits.device, dtype=torch.float32)
     check(lib.sw_rpn_loss(logits.numel(), anchors.shape[0], _p(logits), _p(deltas), _p(labels_i8), _p(anchors), _p(matched_gt), rw,
                           float(inv_norm), _p(losses2), _p(dlogits), _p(ddeltas), _p(ws), _stream()), "sw_rpn_loss")
@@ -1462,7 +1463,7 @@ def det_loss_per_image(rpn_logits, rpn_deltas, rpn_labels_i8, anchors, rpn_match
     out = torch.empty(N, 5, device=rpn_logits.device, dtype=torch.float32)
     ws = torch.empty(max(int(lib.sw_det_loss_workspace_floats(N, A, int(roi_batch_size))), 1), device=rpn_logits.device,
                      dtype=torch.float32)
-    rw = (ctypes.c_float * 4)(*[float(v) for v in rpn_weights]); bw = (ctypes.c_float * 4)(*[float(v) for v in roi_weights])
+    rw = _floats(rpn_weights, 4); bw = _floats(roi_weights, 4)
     check(lib.sw_det_loss_per_image(N, A, _p(rpn_logits), _p(rpn_deltas), _p(rpn_labels_i8), _p(anchors), _p(rpn_matched), rw,
                                     int(rpn_batch_size), DET_LOSS_TYPES[rpn_loss_type], _p(roi_logits), roi_logits.stride(0), int(K),
                                     _p(roi_classes_i32), _p(roi_boxes), _p(roi_gt_boxes), _p(roi_counts_i32), R, int(roi_batch_size), bw, float(gamma),
@@ -1512,8 +1513,7 @@ def voc_eval(det_off, det_img, det_box, gt_off, gt_box, gt_diff, npos, npos_im, 
         assert t.is_contiguous()
     nbytes = lib.sw_voc_eval_workspace_bytes(K, n_img, N, G)
     assert nbytes > 0, "sw_voc_eval_workspace_bytes"
-    ws = torch.empty(nbytes + 256, device=det_box.device, dtype=torch.uint8)
-    ws_p = ctypes.c_void_p((ws.data_ptr() + 255) // 256 * 256)
+    ws, ws_p = _workspace256(nbytes, det_box.device)
     out = torch.empty(3, K, VOC_THRESHOLDS, device=det_box.device, dtype=torch.float64)
     check(lib.sw_voc_eval(K, n_img, N, G, _p(det_off), _p(det_img), _p(det_box), _p(gt_off), _p(gt_box), _p(gt_diff), _p(npos),
                           _p(npos_im), _p(thr), _p(t11), _p(out), ws_p, _stream()), "sw_voc_eval")
@@ -1562,8 +1562,7 @@ def coco_eval(pair_off, pair_gt, pair_ws, ws_words, det_box, gt_off, gt_box, gt_
     assert out.is_cuda and match.is_cuda and out.dtype == torch.float64 and match.dtype == torch.int64
     assert out.shape == (n_out,) and match.shape == (N, 2) and out.is_contiguous() and match.is_contiguous()
     ws_bytes = COCO_WS_HEADER + 8 * int(ws_words)
-    ws = torch.empty(ws_bytes + 256, device=dev, dtype=torch.uint8)
-    ws_p = ctypes.c_void_p((ws.data_ptr() + 255) // 256 * 256)
+    ws, ws_p = _workspace256(ws_bytes, dev)
     check(lib.sw_coco_eval(K, N, P, _p(pair_off), _p(pair_gt), _p(pair_ws), ws_bytes, int(lds_doubles), _p(det_box), _p(gt_off),
                            _p(gt_box), _p(gt_area), _p(gt_flags), _p(area_rng), _p(iou_thr), _p(rec_thr), _p(max_dets), _p(cat_off),
                            _p(order), _p(det_rank), _p(det_score), _p(npig), _p(match), _p(out), ws_p, _stream()), "sw_coco_eval")

@@ -1,5 +1,6 @@
-"""CPU: the C-ABI library builds for gfx950, loads, and exports every symbol include/soswsod_hip.h declares
-(no compute calls without a GPU); the product path refuses to run without it."""
+"""CPU: the C-ABI library builds for gfx950, loads, and exports every symbol include/soswsod_hip.h declares; every ctypes
+signature and every Python copy of a header constant agrees with the header (no compute calls without a GPU); the product path
+refuses to run without the library."""
 import ctypes
 import os
 import re
@@ -9,10 +10,49 @@ import pytest
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
-def _declared_symbols():
+def _header():
     src = open(os.path.join(ROOT, "include", "soswsod_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(sw_[a-z0-9_]+)\s*\(", src)))
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def _declared_symbols():
+    return sorted(set(re.findall(r"\b(sw_[a-z0-9_]+)\s*\(", _header())))
+
+
+def _prototypes():
+    """name -> (return type, [argument types]) as C spells them, `*` kept, qualifiers and argument names dropped"""
+    src = re.sub(r"typedef\s+struct[^{;]*\{.*?\}[^;]*;", "", _header(), flags=re.S)          # struct bodies hold `;` but no prototype
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+
+    def ctype(decl, named):
+        decl = re.sub(r"\b(const|struct)\b", " ", decl)
+        stars = "*" * decl.count("*")
+        words = decl.replace("*", " ").split()
+        if named and not (stars == "" and words == ["void"]):
+            words = words[:-1]                                                                # the argument's name
+        return " ".join(words) + stars
+
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(sw_[a-z0-9_]+)\s*\(([^;{}()]*)\)\s*;", src):
+        args = [a for a in (x.strip() for x in args.split(",")) if a]
+        args = [] if args == ["void"] else [ctype(a, True) for a in args]
+        assert name not in out, f"{name} declared twice"
+        out[name] = (ctype(ret, False), args)
+    return out
+
+
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "float": ctypes.c_float,
+            "double": ctypes.c_double, "uint64_t": ctypes.c_uint64}
+
+
+def _matches(c_type, ct):
+    if c_type.endswith("*") or c_type == "sw_stream_t":
+        return ct in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(ct, type) and issubclass(ct, ctypes._Pointer))
+    return c_type in _SCALARS and ct is _SCALARS[c_type]
+
+
+def _defines():
+    return {k: int(v) for k, v in re.findall(r"^#define\s+(SW_\w+)\s+(\d+)\s*$", _header(), flags=re.M)}
 
 
 def test_header_symbols_exported_and_bound():
@@ -25,6 +65,40 @@ def test_header_symbols_exported_and_bound():
         assert n in L.SIGNATURES, f"{n} has no ctypes signature"
     assert set(L.SIGNATURES) == set(names)
     assert L.lib.sw_version().startswith(b"soswsod-hip")
+
+
+def test_ctypes_signatures_match_header_prototypes():
+    """argument count, every scalar's width and kind, pointer-ness and the return type of every SIGNATURES row"""
+    import sos_wsod_amd._lib as L
+    protos = _prototypes()
+    assert set(protos) == set(_declared_symbols())                                            # the parser saw every prototype
+    bad = []
+    for name, (ret, args) in sorted(protos.items()):
+        res, argtypes = L.SIGNATURES[name]
+        if not _matches(ret, res):
+            bad.append(f"{name}: returns {ret}, bound as {res.__name__}")
+        if len(args) != len(argtypes):
+            bad.append(f"{name}: {len(args)} arguments in the header, {len(argtypes)} bound")
+            continue
+        bad += [f"{name}: argument {i} is {a}, bound as {t.__name__}" for i, (a, t) in enumerate(zip(args, argtypes))
+                if not _matches(a, t)]
+    assert not bad, "\n".join(bad)
+
+
+def test_python_mirrors_of_header_constants():
+    import sos_wsod_amd._lib as L
+    import sos_wsod_amd.evaluation as E
+    import sos_wsod_amd.ops as ops
+    d = _defines()
+    assert (L.SW_F32, L.SW_BF16) == (d["SW_F32"], d["SW_BF16"])
+    assert L.SGD_MAX_TENSORS == d["SW_SGD_MAX_TENSORS"]
+    assert ops.VOC_THRESHOLDS == d["SW_VOC_THRESHOLDS"] == len(E.IOU_THRESHOLDS)
+    assert E.MAX_CLASSES == d["SW_VOC_MAX_CLASSES"]
+    for name in ("THRESHOLDS", "RECALLS", "AREAS", "MAXDETS", "LDS_DOUBLES", "MAX_CLASSES", "WS_HEADER"):
+        assert getattr(ops, "COCO_" + name) == d["SW_COCO_" + name], name
+    assert (len(E.COCO_IOU_THRS), len(E.COCO_REC_THRS), len(E.COCO_AREA_RNG), len(E.COCO_MAX_DETS)) == \
+        (d["SW_COCO_THRESHOLDS"], d["SW_COCO_RECALLS"], d["SW_COCO_AREAS"], d["SW_COCO_MAXDETS"])
+    assert E.COCO_MAX_DETS[-1] <= d["SW_COCO_MAX_PAIR_DETS"]                                  # the evaluator's per-pair cut fits the kernel's
 
 
 def test_missing_extension_fails_loudly(tmp_path, monkeypatch):

@@ -719,7 +719,7 @@ def test_roi_pool_forward_slab_widths_of_large_maps(ops, dtype, H, W):
 @pytest.mark.parametrize("H,W,R", [(63, 63, 1500), (21, 30, 300), (60, 75, 900), (76, 114, 1200), (99, 165, 1600), (150, 200, 700), (9, 200, 200)])
 def test_roi_pool_forward_row_sparse_table_form_bit_exact(ops, H, W, R, ws):
     """bf16 forward through the row sparse table kernels (csrc/roipool.hip: roi_pool_fwd_tasks_kernel over the task list
-    roi_pool_tasks_kernel prepares — sw_roi_pool_fwd_ws, the hot path — and roi_pool_fwd_sparse_kernel, the entry without workspace;
+    roi_pool_tasks_kernel prepares — sw_roi_pool_fwd with a workspace, the hot path — and roi_pool_fwd_sparse_kernel, the entry without workspace;
     whole-map form up to ~4600 pixels, row-band form beyond) against the C oracle on EVERY bin of every ROI of one 8-channel slab group: values, argmax and the objectness
     prior.  The ROI set holds what the level rule has to survive: ROIs sticking out of the map on every side (windows the right edge
     clips below the ROI's span read one span; on the left they take the pixel loop), ROIs far outside, malformed (end < start), one
@@ -1184,8 +1184,8 @@ def test_detect_postprocess_vs_oracle(ops, R, K):
 
 @pytest.mark.parametrize("case", ["rpn", "classes", "one_class_beyond_lds", "ragged"])
 def test_detect_postprocess_mask_form_equals_single_workgroup_form(ops, case):
-    """sw_detect_postprocess2 (mask form: prep / 64x64 IoU tiles over the chip / one resolving wave per class) against
-    sw_detect_postprocess (one workgroup per class, itself pinned by the oracle above and by tools/fuzz_parity.py): every output bit
+    """sw_detect_postprocess with the full workspace (mask form: prep / 64x64 IoU tiles over the chip / one resolving wave per class) against
+    the same entry with sw_detect_workspace_bytes(0, K, topk) bytes (one workgroup per class, itself pinned by the oracle above and by tools/fuzz_parity.py): every output bit
     for bit — the RPN's use (5 levels as classes, 8741 candidates, best 1000 at IoU 0.7), 20 classes x 2000 proposals at the
     detector's thresholds, ONE class of 5000 candidates (rows beyond the resolver's 4096-row LDS window), classes of 0 / 1 / 65
     candidates."""
@@ -1222,15 +1222,15 @@ def test_detect_postprocess_mask_form_equals_single_workgroup_form(ops, case):
         ctr = torch.rand(R, K, 2, generator=g) * torch.tensor([float(W), float(H)]); wh = torch.rand(R, K, 2, generator=g) * 150 + 4
         boxes = torch.cat([ctr - wh / 2, ctr + wh / 2], -1).reshape(R, 4 * K)
     scores, boxes = scores.cuda().contiguous(), boxes.cuda().contiguous()
-    assert int(lib.sw_detect_workspace_bytes2(R, K, topk)) > int(lib.sw_detect_workspace_bytes(K, topk)) + 1024       # the mask form is on offer
+    assert int(lib.sw_detect_workspace_bytes(R, K, topk)) > int(lib.sw_detect_workspace_bytes(0, K, topk)) + 1024       # the mask form is on offer
     got = ops.detect_postprocess(scores, boxes, H, W, thr, nms_thr, topk)
     dev = scores.device
     cnt = torch.zeros(1, device=dev, dtype=torch.int32)
     b = torch.zeros(topk, 4, device=dev); s_ = torch.zeros(topk, device=dev)
     c_ = torch.zeros(topk, device=dev, dtype=torch.int32); r_ = torch.zeros(topk, device=dev, dtype=torch.int32)
-    ws = torch.empty(int(lib.sw_detect_workspace_bytes(K, topk)), device=dev, dtype=torch.uint8)
+    ws = torch.empty(int(lib.sw_detect_workspace_bytes(0, K, topk)), device=dev, dtype=torch.uint8)
     rc = lib.sw_detect_postprocess(R, K, scores.data_ptr(), boxes.data_ptr(), H, W, thr, nms_thr, topk, cnt.data_ptr(), b.data_ptr(),
-                                   s_.data_ptr(), c_.data_ptr(), r_.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+                                   s_.data_ptr(), c_.data_ptr(), r_.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
     assert rc == 0
     n = int(cnt.item())
     assert n == int(got[0].item()) and n > 0
@@ -1258,7 +1258,7 @@ def test_gemm_epilogue_residual_add(ops, dtype, M, N, K):
 
 
 def test_detect_postprocess_mask_form_randomised(ops):
-    """12 random shapes (R 256 .. 3000, K 1 .. 24, thresholds, box scales, top-k): sw_detect_postprocess2 == sw_detect_postprocess"""
+    """12 random shapes (R 256 .. 3000, K 1 .. 24, thresholds, box scales, top-k): sw_detect_postprocess, mask form == per-class form"""
     from sos_wsod_amd._lib import lib
     rng = np.random.RandomState(5)
     used_mask = 0
@@ -1273,15 +1273,15 @@ def test_detect_postprocess_mask_form_randomised(ops):
         ctr = torch.rand(R, K, 2, generator=g) * torch.tensor([float(W), float(H)]); wh = torch.rand(R, K, 2, generator=g) * scale + 2
         boxes = torch.cat([ctr - wh / 2, ctr + wh / 2], -1).reshape(R, 4 * K)
         scores, boxes = scores.cuda().contiguous(), boxes.cuda().contiguous()
-        used_mask += int(lib.sw_detect_workspace_bytes2(R, K, topk)) > int(lib.sw_detect_workspace_bytes(K, topk)) + 1024
+        used_mask += int(lib.sw_detect_workspace_bytes(R, K, topk)) > int(lib.sw_detect_workspace_bytes(0, K, topk)) + 1024
         got = ops.detect_postprocess(scores, boxes, H, W, thr, nms_thr, topk)
         dev = scores.device
         cnt = torch.zeros(1, device=dev, dtype=torch.int32)
         b = torch.zeros(topk, 4, device=dev); s_ = torch.zeros(topk, device=dev)
         c_ = torch.zeros(topk, device=dev, dtype=torch.int32); r_ = torch.zeros(topk, device=dev, dtype=torch.int32)
-        ws = torch.empty(int(lib.sw_detect_workspace_bytes(K, topk)), device=dev, dtype=torch.uint8)
+        ws = torch.empty(int(lib.sw_detect_workspace_bytes(0, K, topk)), device=dev, dtype=torch.uint8)
         assert lib.sw_detect_postprocess(R, K, scores.data_ptr(), boxes.data_ptr(), H, W, thr, nms_thr, topk, cnt.data_ptr(), b.data_ptr(),
-                                         s_.data_ptr(), c_.data_ptr(), r_.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
+                                         s_.data_ptr(), c_.data_ptr(), r_.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream) == 0
         n = int(cnt.item())
         assert n == int(got[0].item()), (case, R, K, n, int(got[0].item()))
         for x, y in zip(got[1:], (b, s_, c_, r_)):
@@ -1322,7 +1322,7 @@ def test_colsum_workspace_form(ops, dtype, M, N, pad):
 
 
 def test_copy_multi_and_relu_bwd_out(ops):
-    """sw_copy_multi: aligned / unaligned / odd-sized / empty tensors in one launch; sw_relu_bwd_out leaves its gradient input alone"""
+    """sw_copy_multi: aligned / unaligned / odd-sized / empty tensors in one launch; sw_relu_bwd with a separate output leaves its gradient input alone"""
     g = torch.Generator().manual_seed(3)
     srcs = [torch.randint(0, 256, (3, 512, 512), generator=g, dtype=torch.uint8), torch.randn(2000, 4, generator=g),
             torch.randn(2000, generator=g), torch.randn(1037, generator=g), torch.randint(0, 256, (77,), generator=g, dtype=torch.uint8),

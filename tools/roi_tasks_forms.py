@@ -1,4 +1,4 @@
-"""ROIPool forward: the prepared-task form (sw_roi_pool_fwd_ws) against the form without workspace.
+"""ROIPool forward: sw_roi_pool_fwd with a workspace (the prepared-task form) against the same entry without one.
     python tools/roi_tasks_forms.py                     # all shapes: no workspace | prepared tasks
 Each shape runs in its own child process; prints the time and checks that values and argmax equal the no-workspace form's bit for bit."""
 import os, subprocess, sys
