@@ -691,6 +691,25 @@ int sw_coco_eval(int K, long long N, long long P, const int64_t* pair_off, const
                  const double* det_score, const int64_t* npig, unsigned long long* match, double* out, void* workspace,
                  sw_stream_t stream);
 
+/* Proposal recall of one split for every budget at once (replaces the overlap block of uwsod/projects/WSL/tools/proposal_recall.py:
+ * recall_mcg :204-225, the same lines in recall_ss :277-297 and recall_eb :356-376, and the ten passes of its budget loop
+ * :389-399).  CSR over images: image i owns rows [prop_off[i], prop_off[i + 1]) of prop_box [P][4] f64 [xmin, ymin, xmax, ymax]
+ * (16-byte aligned), already in rank order, and rows [gt_off[i], gt_off[i + 1]) of gt_box [G][4] f64 (16-byte aligned).
+ * cuts [n_cut] i32: the budgets, strictly ascending, cuts[0] >= 1 (device memory, so not checked here: the caller's
+ * contract, which the Python wrapper asserts; cuts out of order read nothing out of bounds but give wrong rows); thr [n_thr] f64: the IoU thresholds.  For ground-truth row g
+ * and cut c, over the first min(cuts[c], n_i) proposals of its image: ovmax [G][n_cut] f64 is np.max of the overlaps (a NaN
+ * among them gives NaN) and jmax [G][n_cut] i32 np.argmax (the first index of the maximum, or of the first NaN), an index into the
+ * image's ranked list; rows of other images are not touched.  cnt_yes [n_cut][n_thr] i64 (8-byte aligned; zeroed here) counts the
+ * rows with ovmax >= thr[t]: a NaN never counts.  An image without ground truth contributes nothing; one with ground truth and
+ * no proposals (callers reject it, as np.max of an empty array raises) gets NaN and -1.  Each overlap is the reference's f64
+ * arithmetic with its inclusive `+ 1.0` widths, so every value is bit-identical to the reference's. */
+#define SW_PROPOSAL_RECALL_MAX_CUTS 16
+#define SW_PROPOSAL_RECALL_MAX_THRESHOLDS 16
+#define SW_PROPOSAL_RECALL_LDS_BOXES 1024 /* proposals staged per pass; more are taken in further passes */
+int sw_proposal_recall(int n_img, const int64_t* prop_off, const double* prop_box, const int64_t* gt_off, const double* gt_box,
+                       int n_cut, const int32_t* cuts, int n_thr, const double* thr, double* ovmax, int32_t* jmax,
+                       long long* cnt_yes, sw_stream_t stream);
+
 /* Stage-3 strong augmentation of a planar u8 [3][H][W] image, every pixel operation bit-identical to Pillow's (replaces
  * build_strong_augmentation, unbias/ubteacher/data/detection_utils.py:9-46, applied by DatasetMapperTwoCropSeparate.__call__,
  * unbias/ubteacher/data/dataset_mapper.py:141-149; the blur is unbias/ubteacher/data/transforms/augmentation_impl.py GaussianBlur):

@@ -261,6 +261,9 @@ SIGNATURES = {
     "sw_coco_eval_workspace_bytes": (c_longlong, [c_int, c_longlong, c_int]),
     "sw_coco_eval": (c_int, [c_int, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_int]
                      + [c_void_p] * 18),
+    # ---- proposal recall (csrc/proposal_recall.hip)
+    "sw_proposal_recall": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]),
     "sw_version": (ctypes.c_char_p, []),
 }
 

@@ -1567,3 +1567,38 @@ def coco_eval(pair_off, pair_gt, pair_ws, ws_words, det_box, gt_off, gt_box, gt_
                            _p(gt_box), _p(gt_area), _p(gt_flags), _p(area_rng), _p(iou_thr), _p(rec_thr), _p(max_dets), _p(cat_off),
                            _p(order), _p(det_rank), _p(det_score), _p(npig), _p(match), _p(out), ws_p, _stream()), "sw_coco_eval")
     return out, match
+
+
+PROPOSAL_RECALL_MAX_CUTS, PROPOSAL_RECALL_MAX_THRESHOLDS = 16, 16      # SW_PROPOSAL_RECALL_MAX_CUTS / _MAX_THRESHOLDS
+PROPOSAL_RECALL_LDS_BOXES = 1024                                        # SW_PROPOSAL_RECALL_LDS_BOXES
+
+
+def proposal_recall(prop_off, prop_box, gt_off, gt_box, cuts, thr, ovmax=None, jmax=None):
+    """Best overlap of every ground-truth box with the first cuts[c] ranked proposals of its image, for every cut at once, and the
+    boxes recalled at every threshold (sw_proposal_recall), all inputs on the GPU: prop_off / gt_off [n_img + 1] i64 (CSR over
+    images), prop_box [P, 4] / gt_box [G, 4] f64 xyxy, cuts [n_cut <= 16] i32 strictly ascending and >= 1, thr [n_thr <= 16] f64.
+    ovmax [>= G, n_cut] f64 and jmax [>= G, n_cut] i32 may be passed in (tests fill them with sentinels; only the first G rows of
+    images that have ground truth are written).
+    -> (ovmax, jmax, cnt_yes [n_cut, n_thr] i64) on the GPU."""
+    _need_gpu(prop_off, prop_box, gt_off, gt_box, cuts, thr, ovmax, jmax)
+    n_img, P, G, n_cut, n_thr = prop_off.numel() - 1, prop_box.shape[0], gt_box.shape[0], cuts.numel(), thr.numel()
+    assert prop_off.dtype == torch.int64 and gt_off.dtype == torch.int64 and cuts.dtype == torch.int32
+    assert prop_box.dtype == torch.float64 and gt_box.dtype == torch.float64 and thr.dtype == torch.float64
+    assert n_img >= 0 and gt_off.shape == (n_img + 1,) and prop_off.shape == (n_img + 1,)
+    assert prop_box.shape == (P, 4) and gt_box.shape == (G, 4) and cuts.shape == (n_cut,) and thr.shape == (n_thr,)
+    assert 1 <= n_cut <= PROPOSAL_RECALL_MAX_CUTS and 1 <= n_thr <= PROPOSAL_RECALL_MAX_THRESHOLDS
+    c = cuts.tolist()          # a copy to the host: cuts out of order would give wrong rows, not an error
+    assert c[0] >= 1 and all(a < b for a, b in zip(c, c[1:])), f"cuts {c} must be >= 1 and strictly ascending"
+    dev = prop_box.device
+    if ovmax is None:
+        ovmax = torch.empty(G, n_cut, device=dev, dtype=torch.float64)
+    if jmax is None:
+        jmax = torch.empty(G, n_cut, device=dev, dtype=torch.int32)
+    assert ovmax.dtype == torch.float64 and jmax.dtype == torch.int32
+    assert ovmax.dim() == 2 and ovmax.shape[0] >= G and ovmax.shape[1] == n_cut and jmax.shape == ovmax.shape
+    for t in (prop_off, prop_box, gt_off, gt_box, cuts, thr, ovmax, jmax):
+        assert t.is_contiguous()
+    cnt_yes = torch.empty(n_cut, n_thr, device=dev, dtype=torch.int64)
+    check(lib.sw_proposal_recall(n_img, _p(prop_off), _p(prop_box), _p(gt_off), _p(gt_box), n_cut, _p(cuts), n_thr, _p(thr),
+                                 _p(ovmax), _p(jmax), _p(cnt_yes), _stream()), "sw_proposal_recall")
+    return ovmax, jmax, cnt_yes
