@@ -125,18 +125,15 @@ int sw_conv3x3_wgrad(int dtype, int nimg, int H, int W, int Cin, int Cout, int d
  * geometry of the MFMA loader: sw_conv3x3_wgrad returns -6 there): one thread per (co, ci), plain f32 sums in pixel order. */
 int sw_conv3x3_wgrad_small(int dtype, int nimg, int H, int W, int Cin, int Cout, const void* x, const void* dy,
                            const float* cout_scale, float* dw_oihw, int accumulate, sw_stream_t stream);
-/* The two halves of sw_conv3x3_wgrad on their own: `_slabs` writes this problem's workspace_floats / (Cout*9*Cin) partial
- * slabs at `workspace`; `_fold` adds `nslab` consecutive slabs in fixed order into dW (OIHW), with cout_scale and accumulate as
- * above.  Several problems with the same weight (the views of one iteration, possibly running on different streams, or the (x, dy)
- * pairs written by sw_conv3x3_wgrad_grouped — the RPN head's convolution runs on 5 FPN levels in each of the student's two passes,
- * rpn.py:118-133) put their slabs back to back and share ONE fold: the sum that autograd would otherwise form with one add per
- * parameter. */
-int sw_conv3x3_wgrad_slabs(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x,
-                           const void* dy, float* workspace, int splitk, sw_stream_t stream);
+/* The second half of sw_conv3x3_wgrad on its own: adds `nslab` consecutive slabs (Cout*9*Cin floats each, as sw_conv3x3_wgrad's
+ * K-splits write them) in fixed order into dW (OIHW), with cout_scale and accumulate as above.  Several problems with the same weight
+ * (the (x, dy) pairs written by sw_conv3x3_wgrad_grouped: the views of one iteration, or the RPN head's convolution on 5 FPN levels in
+ * each of the student's two passes, rpn.py:118-133) put their slabs back to back and share ONE fold: the sum that autograd would
+ * otherwise form with one add per parameter. */
 int sw_conv3x3_wgrad_fold(int Cin, int Cout, int nslab, const float* workspace, float* dw_oihw, const float* cout_scale,
                           int accumulate, sw_stream_t stream);
-/* ALL weight gradients of a backward pass in ONE launch: problem i writes the slabs sw_conv3x3_wgrad_slabs(..., splitk =
- * nsplit) would write (sw_conv3x3_wgrad_workspace_floats(...) floats at `slabs`), computed by resident workgroups walking the
+/* ALL weight gradients of a backward pass in ONE launch: problem i writes the slabs of sw_conv3x3_wgrad(..., splitk = nsplit)
+ * (sw_conv3x3_wgrad_workspace_floats(...) floats at `slabs`), computed by resident workgroups walking the
  * (problem, split, tile) list — instead of one launch of 128x128 tiles per layer and view, each cut into many K-splits to fill the
  * chip.  bf16 lists whose every problem has Cin % 64 == 0, Cout % 64 == 0, dilation 1 or 2, H >= 8 and >= 8 strip rows per split run
  * the direct weight-gradient kernel (conv_wgrad_direct.hip: an input row staged once for all nine taps; the splits are ranges of
@@ -377,15 +374,11 @@ int sw_copy_multi(int n, const sw_copy_desc* copies, sw_stream_t stream);
  * workspace NULL (or N / ld not a multiple of 16 bytes): zero fill (unless accumulating) + one f32 atomic per column and row chunk. */
 long sw_colsum_workspace_floats(int dtype, int M, int N);
 int sw_colsum(int dtype, int M, int N, const void* X, long ld, float* out, float* workspace, int accumulate, sw_stream_t stream);
-/* halves of the workspace form: `_partial` writes sw_colsum_workspace_floats(dtype, M, N) / N partial rows at `workspace`,
- * `_fold` adds n_partial_rows consecutive rows (of one or several matrices) in fixed order */
-int sw_colsum_partial(int dtype, int M, int N, const void* X, long ld, float* workspace, sw_stream_t stream);
-int sw_colsum_fold(int N, int n_partial_rows, const float* workspace, float* out, sw_stream_t stream);
-/* n `_partial` calls in ONE launch (every bias gradient of a backward pass: conv layers x view batches); `parts` is a HOST array;
- * problem i writes sw_colsum_workspace_floats(dtype, M, N) / N partial rows at its workspace */
+/* the two halves of the workspace form for n matrices in ONE launch each (every bias gradient of a backward pass: conv layers x view
+ * batches); `parts` is a HOST array; problem i writes sw_colsum_workspace_floats(dtype, M, N) / N partial rows at its workspace */
 typedef struct { int M, N; const void* X; long ld; float* workspace; } sw_colsum_part_desc;
 int sw_colsum_partial_multi(int dtype, int n, const sw_colsum_part_desc* parts, sw_stream_t stream);
-/* n folds in ONE launch; `folds` is a HOST array */
+/* n folds in ONE launch, each adding n_partial_rows consecutive rows (of one or several matrices) in fixed order; `folds` is a HOST array */
 typedef struct { int N, n_partial_rows; const float* workspace; float* out; } sw_colsum_fold_desc;
 int sw_colsum_fold_multi(int n, const sw_colsum_fold_desc* folds, sw_stream_t stream);
 /* rows x cols copy/convert f32 -> dtype with independent leading dimensions (weight staging). */
@@ -411,8 +404,6 @@ int sw_relu_bwd(int dtype, long n, const void* ref, const void* grad, void* out,
 /* out[m][n] = in[m][n] * colscale[n] (f32 -> dtype): applies each loss term's cotangent to its logit columns. */
 int sw_scale_cols(int dtype, int M, int N, const float* in, long ld_in, const float* colscale, void* out,
                   long ld_out, sw_stream_t stream);
-/* dst(f32) = src(dtype) */
-int sw_to_f32(int dtype, long n, const void* src, float* dst, sw_stream_t stream);
 int sw_fill_zero(void* p, long bytes, sw_stream_t stream);
 /* keep[i] = hash(seed, offset+i) >= p   (Bernoulli keep mask for F.dropout, box_head.py:90) */
 int sw_dropout_mask(uint8_t* keep, long n, uint64_t seed, uint64_t offset, float p, sw_stream_t stream);
@@ -528,10 +519,6 @@ int sw_roi_align_bwd_fx(int dtype, int H, int W, int C, int PH, int PW, float sp
                         long ld, const float* rois, const int32_t* sel, int n_sel, const int32_t* n_sel_dev, const float* gout_absmax,
                         long long* acc_i64, sw_stream_t stream);
 int sw_fx_to_float(int out_dtype, long n, const long long* acc_i64, const float* absmax, void* out, sw_stream_t stream);
-/* Box2BoxTransform.apply_deltas (box_regression.py:76-116): out[i] = decode(deltas[i], boxes[i % n_boxes]); deltas row pitch
- * ld_deltas floats; weights4: HOST float[4]; dw, dh clamped to scale_clamp. */
-int sw_decode_boxes(long n, long n_boxes, const float* deltas, long ld_deltas, const float* boxes, const float* weights4,
-                    float scale_clamp, float* out, sw_stream_t stream);
 /* ---- Stage-3 detector, index side (csrc/proposals.hip): the reference's torch sort / nonzero / randperm logic as device code.
  * RPN proposal selection (detectron2/detectron2/modeling/proposal_generator/proposal_utils.py:22-130 find_top_rpn_proposals, up to its
  * batched_nms): for every image and level the pre_topk highest objectness logits (= sort(descending, stable)[:k]: ties -> ascending

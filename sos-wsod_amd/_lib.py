@@ -157,11 +157,7 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "sw_colsum": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p]),
     "sw_colsum_workspace_floats": (c_long, [c_int, c_int, c_int]),
-    "sw_colsum_partial": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p]),
-    "sw_colsum_fold": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sw_conv3x3_wgrad_small": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "sw_conv3x3_wgrad_slabs": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                       c_void_p]),
     "sw_conv3x3_wgrad_fold": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "sw_conv3x3_wgrad_fold_multi": (c_int, [c_int, ctypes.POINTER(WgradFold), c_void_p]),
     "sw_conv3x3_multi": (c_int, [c_int, c_int, ctypes.POINTER(ConvProblem), c_void_p]),
@@ -176,7 +172,6 @@ SIGNATURES = {
     "sw_nchw_to_nhwc": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sw_relu_bwd": (c_int, [c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sw_scale_cols": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p]),
-    "sw_to_f32": (c_int, [c_int, c_long, c_void_p, c_void_p, c_void_p]),
     "sw_fill_zero": (c_int, [c_void_p, c_long, c_void_p]),
     "sw_dropout_mask": (c_int, [c_void_p, c_long, c_u64, c_u64, c_float, c_void_p]),
     "sw_sgd_momentum_step": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_int, c_float,
@@ -232,7 +227,6 @@ SIGNATURES = {
                                   c_void_p]),
     "sw_roi_assign_levels": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_long), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),
-    "sw_decode_boxes": (c_int, [c_long, c_long, c_void_p, c_long, c_void_p, _F4, c_float, c_void_p, c_void_p]),
     "sw_rpn_select_workspace_bytes": (c_long, [c_int, c_int, ctypes.POINTER(c_int)]),
     "sw_rpn_select_pack": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
                                    ctypes.POINTER(c_int), c_long, c_int, _F4, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -52,14 +52,6 @@ class PlainBlock(nn.Module):
         return self
 
 
-def _wgrad_splitk(cout, cin, npix):
-    """K-splits of a conv weight gradient: tiles x splits just under one resident wave of workgroups (256 CUs x 2 at 64 KiB
-    LDS each = 512 slots) was the optimum for every conv3..conv5 shape (tools/probes/wgrad_sweep.py: 3 / 7 / 14 / 28 splits); one
-    more split starts a second, mostly empty wave (+30 %)"""
-    tiles = ((cout + 127) // 128) * ((9 * cin + 127) // 128)
-    return max(1, min(32, 512 // tiles, max(1, npix // 1024)))
-
-
 _WGRAD_PLAN_CACHE = {}
 
 
@@ -256,14 +248,13 @@ class _VGGFunction(torch.autograd.Function):
         main = torch.cuda.current_stream()
         side = module.side_stream() if len(live) > 1 else None
         # ---- plan: per trainable conv one slab workspace / one partial-row workspace shared by all view batches.
-        # grouped: the weight gradients of ALL layers and view batches run as ONE launch after the data-gradient chains
-        # (sw_conv3x3_wgrad_grouped: 256x256 tiles, every CU busy); else one 128x128-tile launch per layer and view inside the chains
-        grouped = module.grouped_wgrad
+        # The weight gradients of ALL layers and view batches run as ONE launch after the data-gradient chains
+        # (sw_conv3x3_wgrad_grouped: 256x256 tiles, every CU busy)
         # fp32 mode with bf16x3: the weight gradients as bf16 problems over SIX stacked copies of the batch (the three-piece splits of dY
         # and X along the image dimension, sw_split_bf16x3 along_rows: [a1;a1;a2;a1;a2;a3] against [b1;b2;b1;b3;b2;b1] — the sum over
         # images is the sum of the six products) when every trainable convolution qualifies
         x3w = False
-        if module.fp32x3 and dtype == torch.float32 and grouped:
+        if module.fp32x3 and dtype == torch.float32:
             x3w, pj = True, len(params)
             for sj in range(len(module.blocks) - 1, -1, -1):
                 for cj in range(module.blocks[sj].num_conv - 1, -1, -1):
@@ -274,24 +265,22 @@ class _VGGFunction(torch.autograd.Function):
         bk = 64 if wdt == torch.bfloat16 else 32
         deferred = []
         module._colsum_deferred = []
-        target = module.wgrad_target_ktiles
-        direct_ns = None                        # (pidx, view batch) -> splits, when the direct weight-gradient kernel takes the list
-        if grouped and target <= 0:             # pick the K-tiles per item for THIS set of (layer, view batch) problems
-            shapes, probs6, keys = [], [], []
-            pj = len(params)
-            for sj in range(len(module.blocks) - 1, -1, -1):
-                bj = module.blocks[sj]
-                for cj in range(bj.num_conv - 1, -1, -1):
-                    pj -= 2
-                    if params[pj].requires_grad:
-                        for i in live:
-                            xin = infos[i][sj][0][cj][0]
-                            shapes.append((nmul * xin.shape[0] * xin.shape[1] * xin.shape[2], bj.out_channels, 9 * xin.shape[3]))
-                            probs6.append((nmul * xin.shape[0], xin.shape[1], xin.shape[2], xin.shape[3], bj.out_channels, bj.dilation))
-                            keys.append((pj, i))
-            if _wgrad_direct_covers(probs6, wdt):
-                direct_ns = dict(zip(keys, _wgrad_direct_splits(probs6)))
-            target = _wgrad_grouped_target(shapes, bk)
+        # the K-tiles per item for THIS set of (layer, view batch) problems
+        shapes, probs6, keys = [], [], []
+        pj = len(params)
+        for sj in range(len(module.blocks) - 1, -1, -1):
+            bj = module.blocks[sj]
+            for cj in range(bj.num_conv - 1, -1, -1):
+                pj -= 2
+                if params[pj].requires_grad:
+                    for i in live:
+                        xin = infos[i][sj][0][cj][0]
+                        shapes.append((nmul * xin.shape[0] * xin.shape[1] * xin.shape[2], bj.out_channels, 9 * xin.shape[3]))
+                        probs6.append((nmul * xin.shape[0], xin.shape[1], xin.shape[2], xin.shape[3], bj.out_channels, bj.dilation))
+                        keys.append((pj, i))
+        # (pidx, view batch) -> splits, when the direct weight-gradient kernel takes the list
+        direct_ns = dict(zip(keys, _wgrad_direct_splits(probs6))) if _wgrad_direct_covers(probs6, wdt) else None
+        target = _wgrad_grouped_target(shapes, bk)
         plan = {}            # pidx -> dict(ws, rows, per-batch offsets, totals, dw, db)
         pidx = len(params)
         for si in range(len(module.blocks) - 1, -1, -1):
@@ -306,8 +295,7 @@ class _VGGFunction(torch.autograd.Function):
                         x_in = infos[i][si][0][ci][0]
                         n, H, W, cin = x_in.shape
                         splits[i] = (direct_ns[(pidx, i)] if direct_ns is not None
-                                     else _wgrad_grouped_splits(nmul * n * H * W, bk, target) if grouped
-                                     else _wgrad_splitk(cout, cin, n * H * W))
+                                     else _wgrad_grouped_splits(nmul * n * H * W, bk, target))
                         slab_off[i], row_off[i] = nslab, nrow
                         nslab += ops.conv3x3_wgrad_nslab_shape(wdt, nmul * n, H, W, cin, cout, splits[i])
                         nrow += ops.colsum_nrows(dtype, n * H * W, cout)
@@ -330,7 +318,7 @@ class _VGGFunction(torch.autograd.Function):
                 if st is not main:
                     g.record_stream(st)
                 _VGGFunction._backward_one(module, infos[i], params, g, dtype, plan, i, first_trainable,
-                                           deferred if grouped else None, None if st is main else main, x3w)
+                                           deferred, None if st is main else main, x3w)
             infos[i] = None
         if side is not None:
             main.wait_stream(side)
@@ -369,25 +357,21 @@ class _VGGFunction(torch.autograd.Function):
                 pl = plan.get(pidx)
                 if pl is not None:
                     npix = n * H * W
-                    if deferred is None:
-                        ops.conv3x3_wgrad_slabs(x_in, dz, pl["ws"][pl["slab_off"][i]:], blk.dilation, splitk=pl["splits"][i])
-                    else:                       # the grouped launch reads (x_in, dz) later, on the main stream
-                        xw, dw_ = x_in, dz
-                        if x3w:                 # six stacked bf16 copies of the batch (see backward)
-                            cout = blk.out_channels
-                            xw = ops.split_bf16x3(x_in.view(npix, cin), 1, along_rows=True,
-                                                  out=torch.empty(6 * npix, cin, device=g.device, dtype=torch.bfloat16)).view(6 * n, H, W, cin)
-                            dw_ = ops.split_bf16x3(dz.view(npix, cout), 0, along_rows=True,
-                                                   out=torch.empty(6 * npix, cout, device=g.device, dtype=torch.bfloat16)).view(6 * n, H, W, cout)
-                        if consumer_stream is not None:
-                            xw.record_stream(consumer_stream); dw_.record_stream(consumer_stream)
-                            dz.record_stream(consumer_stream)
-                        deferred.append((xw, dw_, pl["ws"][pl["slab_off"][i]:], blk.dilation, pl["splits"][i]))
-                    if deferred is None:
-                        ops.colsum_partial(dz.view(npix, blk.out_channels), npix, blk.out_channels, pl["rows"][pl["row_off"][i]:])
-                    else:       # bias partial rows of every layer x view batch: ONE launch behind the chains (18 launches before, each
-                        #             in front of a data-gradient convolution on its stream's critical path)
-                        module._colsum_deferred.append((dz.view(npix, blk.out_channels), pl["rows"][pl["row_off"][i]:]))
+                    # the grouped launch reads (x_in, dz) later, on the main stream
+                    xw, dw_ = x_in, dz
+                    if x3w:                 # six stacked bf16 copies of the batch (see backward)
+                        cout = blk.out_channels
+                        xw = ops.split_bf16x3(x_in.view(npix, cin), 1, along_rows=True,
+                                              out=torch.empty(6 * npix, cin, device=g.device, dtype=torch.bfloat16)).view(6 * n, H, W, cin)
+                        dw_ = ops.split_bf16x3(dz.view(npix, cout), 0, along_rows=True,
+                                               out=torch.empty(6 * npix, cout, device=g.device, dtype=torch.bfloat16)).view(6 * n, H, W, cout)
+                    if consumer_stream is not None:
+                        xw.record_stream(consumer_stream); dw_.record_stream(consumer_stream)
+                        dz.record_stream(consumer_stream)
+                    deferred.append((xw, dw_, pl["ws"][pl["slab_off"][i]:], blk.dilation, pl["splits"][i]))
+                    # bias partial rows of every layer x view batch: ONE launch behind the chains (18 launches before, each in front
+                    # of a data-gradient convolution on its stream's critical path)
+                    module._colsum_deferred.append((dz.view(npix, blk.out_channels), pl["rows"][pl["row_off"][i]:]))
                 if (si, ci) == first_trainable:
                     return
                 # data gradient: conv with flipped/transposed weights; ReLU mask of the producer fused when the
@@ -421,8 +405,6 @@ class VGG16(nn.Module):
         self.num_classes = num_classes
         self.compute_dtype = compute_dtype
         self.dual_stream = True           # alternate the view batches of forward_views between two HIP streams
-        self.grouped_wgrad = os.environ.get("SW_WGRAD_GROUPED", "1") != "0"      # development switch: per-layer launches
-        self.wgrad_target_ktiles = int(os.environ.get("SW_WGRAD_KTILES", "0"))   # 0: chosen per shape set (_wgrad_grouped_target)
         self._side = None
         self._wk_cache = {}
         self._wk3_cache = {}

@@ -486,26 +486,7 @@ __global__ void fx_to_float_kernel(long n, const long long* __restrict__ acc, co
     Elem<T>::store(out + i, bad ? __uint_as_float(0x7FC00000u) : (float)((double)acc[i] * inv));
 }
 
-// ------------------------------------------------------------------------------------------- box decoding, RPN losses
-// Box2BoxTransform.apply_deltas (detectron2/modeling/box_regression.py:76-116): deltas [n][4], boxes [n][4] (row r of boxes is
-// r % n_boxes: the anchors repeat over the images) -> out [n][4]
-__global__ void decode_boxes_kernel(long n, long n_boxes, const float* __restrict__ deltas, long ld_d, const float* __restrict__ boxes,
-                                    float wx, float wy, float ww, float wh, float clamp, float* __restrict__ out) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float* b = boxes + (i % n_boxes) * 4;
-    const float* d = deltas + i * ld_d;
-    const float w = __fsub_rn(b[2], b[0]), h = __fsub_rn(b[3], b[1]);
-    const float cx = __fadd_rn(b[0], __fmul_rn(0.5f, w)), cy = __fadd_rn(b[1], __fmul_rn(0.5f, h));
-    const float dx = __fdiv_rn(d[0], wx), dy = __fdiv_rn(d[1], wy);
-    const float dw = fminf(__fdiv_rn(d[2], ww), clamp), dh = fminf(__fdiv_rn(d[3], wh), clamp);
-    const float px = __fadd_rn(__fmul_rn(dx, w), cx), py = __fadd_rn(__fmul_rn(dy, h), cy);
-    const float pw = __fmul_rn(expf(dw), w), ph = __fmul_rn(expf(dh), h);
-    float* o = out + i * 4;
-    o[0] = __fsub_rn(px, __fmul_rn(0.5f, pw)); o[1] = __fsub_rn(py, __fmul_rn(0.5f, ph));
-    o[2] = __fadd_rn(px, __fmul_rn(0.5f, pw)); o[3] = __fadd_rn(py, __fmul_rn(0.5f, ph));
-  }
-}
-
+// ------------------------------------------------------------------------------------------- RPN losses
 // RPN losses (detectron2/modeling/proposal_generator/rpn.py:362-420, box_regression.py:229-260): over all N * A anchors,
 //   objectness: sum over label >= 0 of BCE-with-logits(x, label);   localisation: sum over label == 1 of |delta - get_deltas(anchor, gt)|
 // both x inv_norm (1 / (batch_size_per_image * N)).  One partial pair per workgroup into `partial` (ordered fold by the second
@@ -1001,17 +982,6 @@ extern "C" int sw_fx_to_float(int out_dtype, long n, const long long* acc_i64, c
   DISPATCH_T(out_dtype,
     hipLaunchKernelGGL(fx_to_float_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, n, acc_i64, absmax, (unsigned short*)out),
     hipLaunchKernelGGL(fx_to_float_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, n, acc_i64, absmax, (float*)out));
-  SW_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int sw_decode_boxes(long n, long n_boxes, const float* deltas, long ld_deltas, const float* boxes,
-                               const float* weights4, float scale_clamp, float* out, hipStream_t stream) {
-  SW_ENTER();
-  if (n <= 0) return 0;
-  if (n_boxes <= 0 || ld_deltas < 4) return -5;
-  hipLaunchKernelGGL(decode_boxes_kernel, dim3(grid_for_n(n)), dim3(256), 0, stream, n, n_boxes, deltas, ld_deltas, boxes,
-                     weights4[0], weights4[1], weights4[2], weights4[3], scale_clamp, out);
   SW_CHECK_LAUNCH();
   return 0;
 }

@@ -300,12 +300,6 @@ __global__ void convert_2d_vec4_kernel(int rows, int cols4, const float* __restr
   }
 }
 
-template <typename T>
-__global__ void to_f32_kernel(long n, const T* __restrict__ src, float* __restrict__ dst) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    dst[i] = Elem<T>::load(src + i);
-}
-
 // ---------------------------------------------------------------- column sums: out[n] = sum_m X[m][n]
 // grid = (column slabs of 64, row chunks); each workgroup folds its rows (4 row-lanes x 64 columns, coalesced
 // 128/256-byte row segments) and adds ONE f32 atomic per column into the zero-filled output.
@@ -1030,16 +1024,6 @@ extern "C" int sw_split_bf16x3(int rows, int cols, const float* src, long ld_src
   return 0;
 }
 
-extern "C" int sw_to_f32(int dtype, long n, const void* src, float* dst, hipStream_t stream) {
-  SW_ENTER();
-  if (n <= 0) return 0;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(to_f32_kernel<unsigned short>, dim3(grid_for(n)), dim3(256), 0, stream, n, (const unsigned short*)src, dst),
-    hipLaunchKernelGGL(to_f32_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, n, (const float*)src, dst));
-  SW_CHECK_LAUNCH();
-  return 0;
-}
-
 extern "C" int sw_nchw_to_nhwc(int dtype, int N, int C, int H, int W, int cpad, const float* in, void* out,
                                hipStream_t stream) {
   SW_ENTER();
@@ -1108,7 +1092,7 @@ extern "C" long sw_colsum_workspace_floats(int dtype, int M, int N) {
 
 // the two halves of the workspace form on their own: several matrices (the views of a backbone pass running on different
 // streams) write their partial rows into ONE workspace back to back, a single fold then sums all of them in fixed order
-extern "C" int sw_colsum_partial(int dtype, int M, int N, const void* X, long ld, float* workspace, hipStream_t stream) {
+static int colsum_partial(int dtype, int M, int N, const void* X, long ld, float* workspace, hipStream_t stream) {
   SW_ENTER();
   if (dtype != SW_BF16 && dtype != SW_F32) return -1;
   const int vec = dtype == SW_BF16 ? 8 : 4;
@@ -1151,14 +1135,6 @@ extern "C" int sw_colsum_partial_multi(int dtype, int n, const sw_colsum_part_de
   return 0;
 }
 
-extern "C" int sw_colsum_fold(int N, int n_partial_rows, const float* workspace, float* out, hipStream_t stream) {
-  SW_ENTER();
-  if (N <= 0 || n_partial_rows < 1) return -5;
-  hipLaunchKernelGGL(colsum_fold_kernel, dim3((N + 15) / 16), dim3(256), 0, stream, N, n_partial_rows, workspace, out, 0);
-  SW_CHECK_LAUNCH();
-  return 0;
-}
-
 extern "C" int sw_colsum_fold_multi(int n, const sw_colsum_fold_desc* folds, hipStream_t stream) {
   SW_ENTER();
   for (int base = 0; base < n; base += CFOLD_MAX) {
@@ -1187,7 +1163,7 @@ extern "C" int sw_colsum(int dtype, int M, int N, const void* X, long ld, float*
   const int vec = dtype == SW_BF16 ? 8 : 4;
   const bool ws_form = workspace && M > 0 && (N % vec) == 0 && (ld % vec) == 0 && (((uintptr_t)X) & 15) == 0;
   if (ws_form) {
-    const int rc = sw_colsum_partial(dtype, M, N, X, ld, workspace, stream);
+    const int rc = colsum_partial(dtype, M, N, X, ld, workspace, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(colsum_fold_kernel, dim3((N + 15) / 16), dim3(256), 0, stream, N, (int)(sw_colsum_workspace_floats(dtype, M, N) / N),
                        workspace, out, accumulate);

@@ -1410,8 +1410,8 @@ extern "C" long sw_conv3x3_wgrad_workspace_floats(int dtype, int nimg, int H, in
 // Every K-split stores its partial [co][tap][ci] tile into its own slab of the workspace with plain coalesced stores;
 // a second kernel adds the slabs in fixed order and permutes to OIHW.  (f32 atomics were measured 3-5x slower here:
 // the splits of one tile finish together and collide on the same addresses; this form is also deterministic.)
-extern "C" int sw_conv3x3_wgrad_slabs(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x,
-                                      const void* dy, float* workspace, int splitk, hipStream_t stream) {
+static int conv3x3_wgrad_slabs(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x,
+                               const void* dy, float* workspace, int splitk, hipStream_t stream) {
   SW_ENTER();
   const int epc = dtype == SW_BF16 ? 8 : 4;
   if (dtype != SW_BF16 && dtype != SW_F32) return -1;
@@ -1663,7 +1663,7 @@ extern "C" int sw_conv3x3_wgrad_fold_multi(int n, const sw_wgrad_fold* folds, hi
 extern "C" int sw_conv3x3_wgrad(int dtype, int nimg, int H, int W, int Cin, int Cout, int dilation, const void* x,
                                 const void* dy, float* dw_oihw, float* workspace, int splitk, const float* cout_scale,
                                 int accumulate, hipStream_t stream) {
-  const int rc = sw_conv3x3_wgrad_slabs(dtype, nimg, H, W, Cin, Cout, dilation, x, dy, workspace, splitk, stream);
+  const int rc = conv3x3_wgrad_slabs(dtype, nimg, H, W, Cin, Cout, dilation, x, dy, workspace, splitk, stream);
   if (rc) return rc;
   const long nelem = (long)Cout * 9 * Cin;
   const int nslab = (int)(sw_conv3x3_wgrad_workspace_floats(dtype, nimg, H, W, Cin, Cout, splitk) / nelem);

@@ -45,8 +45,6 @@ GT_LOGIT = math.log((1.0 - 1e-10) / (1 - (1.0 - 1e-10)))        # proposal_utils
 #   _GRAD_PREMASKED   on the producer of that input: the gradient it receives is already masked, its own relu_bwd is skipped.
 # The two are set in pairs by the module that owns both layers (bottleneck chain of a stage, RPN head, box head -> predictor).
 _RELU, _MASK_INPUT_GRAD, _GRAD_PREMASKED = 1, 2, 4
-MASKS_IN_PRODUCERS = os.environ.get("SW_S3_MASKS_IN_PRODUCERS", "1") != "0"    # off: every layer masks its own incoming gradient (relu_bwd), the flag pairs are ignored
-GROUP_LINEAR_WGRADS = True   # _LinearFn layers used several times per backward queue their weight gradients for one grouped launch (ops.grad_scope)
 FUSED_BLOCKS = True      # BottleneckBlock as one autograd node (_BottleneckFn); False: layer by layer (the form the fused one is tested against)
 
 
@@ -58,7 +56,6 @@ def _pad8(n):
     return (n + 7) // 8 * 8
 
 
-_ALIGN_BWD_FX = os.environ.get("SW_ROI_ALIGN_BWD_FX", "1") == "1"     # development switch: "0" = the f32-atomic ROIAlign backward
 
 class _Staged:
     """what one layer reads from the model's stage plan: w (+ wd: 3x3 data-gradient layout), scale / shift (FrozenBN) or packed bias"""
@@ -129,7 +126,7 @@ class _LinearFn(ops.CountedFunction):
         out_f = sum(splits)
         cd = x.dtype
         ld = staged.shape[0]
-        flags = int(relu) if MASKS_IN_PRODUCERS else (int(relu) & _RELU)
+        flags = int(relu)
         relu = bool(flags & _RELU)
         ydt = torch.float32 if out_f32 else cd
         assert not (relu and out_f32) and ld == (out_f + 7) // 8 * 8 and staged.dtype == cd
@@ -151,7 +148,7 @@ class _LinearFn(ops.CountedFunction):
         ctx.mask_in, ctx.premasked = bool(flags & _MASK_INPUT_GRAD), bool(flags & _GRAD_PREMASKED)
         ctx.shapes = [tuple(p.shape) for p in params]
         ctx.wkey = id(params[0]) if params else None
-        if GROUP_LINEAR_WGRADS and params and any(ctx.needs_input_grad[8:8 + len(splits)]):
+        if params and any(ctx.needs_input_grad[8:8 + len(splits)]):
             ops.count_use(("lin", ctx.wkey))
         ctx.bkey = id(params[len(splits)]) if len(params) > len(splits) else None
         return y
@@ -236,7 +233,7 @@ class _Conv3x3Fn(ops.CountedFunction):
         n, H, W, cin = x.shape
         cout = w.shape[0]
         cd = x.dtype
-        flags = int(relu) if MASKS_IN_PRODUCERS else (int(relu) & _RELU)
+        flags = int(relu)
         relu = bool(flags & _RELU)
         ctx.premasked = bool(flags & _GRAD_PREMASKED)
         out = torch.empty(n, H, W, cout, device=x.device, dtype=cd)
@@ -495,7 +492,7 @@ class _BottleneckFn(ops.CountedFunction):
         ctx.save_for_backward(x2, h1, h2, out, s1.w, s2.wd, s3.w, None if sc is None else _staged_of(sc).w,
                               s1.scale, s2.scale, s3.scale, None if sc is None else _staged_of(sc).scale)
         ctx.geom = (maps, in_maps, offs, cin, mid, cout, c1.stride, single)
-        ctx.flags = (bool(blk.mask_input_grad) and c1.stride == 1, bool(blk.grad_premasked)) if MASKS_IN_PRODUCERS else (False, False)
+        ctx.flags = (bool(blk.mask_input_grad) and c1.stride == 1, bool(blk.grad_premasked))
         ctx.keys = tuple(id(w) for w in weights) + (None,) * (4 - len(weights))
         if ctx.needs_input_grad[3]:
             for _ in maps:
@@ -589,7 +586,7 @@ class _Conv3x3LevelsFn(ops.CountedFunction):
     @staticmethod
     def forward(ctx, L, relu, *ts):
         xs, sws, swds, bvs, ws, bs = (ts[i * L:(i + 1) * L] for i in range(6))
-        flags = int(relu) if MASKS_IN_PRODUCERS else (int(relu) & _RELU)
+        flags = int(relu)
         relu = bool(flags & _RELU)
         cd = xs[0].dtype
         outs, probs = [], []
@@ -710,19 +707,16 @@ class _RoIAlignFn(torch.autograd.Function):
             if not need:
                 grads.append(None)
                 continue
-            if _ALIGN_BWD_FX and R:
-                # deterministic (round 6): 64-bit fixed-point accumulation, one conversion into the map's dtype (csrc/detector.hip
-                # roi_align_bwd_fx_kernel) — the float-atomic form below left the iteration irreproducible in the last bits
-                if amax is None:
-                    amax = ops.absmax(g)
-                acc = ops.fill_zero(torch.empty(shp, device=g.device, dtype=torch.int64))
-                ops.roi_align_bwd_fx(g, ctx.rois, ctx.sel[l], acc, sc, amax, n_sel_dev=ctx.sel_cnt[l:l + 1])
-                grads.append(ops.fx_to_float(acc, amax, torch.empty(shp, device=g.device, dtype=ctx.dtype)))
+            if not R:
+                grads.append(ops.fill_zero(torch.empty(shp, device=g.device, dtype=ctx.dtype)))
                 continue
-            d = ops.fill_zero(torch.empty(shp, device=g.device, dtype=torch.float32))
-            if R:
-                ops.roi_align_bwd(g, ctx.rois, ctx.sel[l], d, sc, n_sel_dev=ctx.sel_cnt[l:l + 1])
-            grads.append(d if ctx.dtype == torch.float32 else ops.convert_flat(d, ctx.dtype))
+            # deterministic (round 6): 64-bit fixed-point accumulation, one conversion into the map's dtype (csrc/detector.hip
+            # roi_align_bwd_fx_kernel) — a float-atomic accumulation left the iteration irreproducible in the last bits
+            if amax is None:
+                amax = ops.absmax(g)
+            acc = ops.fill_zero(torch.empty(shp, device=g.device, dtype=torch.int64))
+            ops.roi_align_bwd_fx(g, ctx.rois, ctx.sel[l], acc, sc, amax, n_sel_dev=ctx.sel_cnt[l:l + 1])
+            grads.append(ops.fx_to_float(acc, amax, torch.empty(shp, device=g.device, dtype=ctx.dtype)))
         return (None, None, None, None) + tuple(grads)
 
 
@@ -1227,17 +1221,12 @@ class Speculation:
         if sealed is not None:
             sealed[0].synchronize()
             ok = int(sealed[1][0]) == 0
-            if not ok and os.environ.get("SW_S3_SPEC_DEBUG"):
-                print("speculation miss: have", sealed[2].tolist(), "want", sealed[3].tolist(), flush=True)
         elif not self.items:
             ok = True
         else:
             got = torch.cat([t for t, _ in self.items]) if len(self.items) > 1 else self.items[0][0]
             want = [v for _, vs in self.items for v in vs]
-            have = got.tolist()
-            ok = have == want
-            if not ok and os.environ.get("SW_S3_SPEC_DEBUG"):
-                print("speculation miss: have", have, "want", want, flush=True)
+            ok = got.tolist() == want
         if not agreed and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             dev = self.items[0][0].device if (self.items and dist.get_backend() == "nccl") else "cpu"
             flag = torch.tensor([0 if ok else 1], dtype=torch.int32, device=dev)

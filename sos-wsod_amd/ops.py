@@ -419,7 +419,7 @@ def conv3x3_wgrad_small(x, dy, dw_oihw, cout_scale=None, accumulate=False):
 
 
 def conv3x3_wgrad_nslab(x, cout, splitk):
-    """slabs that conv3x3_wgrad_slabs(x, dy -> cout channels, splitk) writes"""
+    """slabs that a weight-gradient problem (x, dy -> cout channels, splitk) of conv3x3_wgrad_grouped writes"""
     n, H, W, Cin = x.shape
     return int(lib.sw_conv3x3_wgrad_workspace_floats(dt(x), n, H, W, Cin, cout, splitk)) // (cout * 9 * Cin)
 
@@ -428,14 +428,6 @@ def conv3x3_wgrad_nslab_shape(dtype, n, H, W, Cin, cout, splitk):
     """conv3x3_wgrad_nslab for a batch given by its shape and torch dtype"""
     code = SW_BF16 if dtype == torch.bfloat16 else SW_F32
     return int(lib.sw_conv3x3_wgrad_workspace_floats(code, n, H, W, Cin, cout, splitk)) // (cout * 9 * Cin)
-
-
-def conv3x3_wgrad_slabs(x, dy, workspace, dilation, splitk=1):
-    """split-K partial weight gradients of one (x, dy) pair into `workspace` (no fold): see sw_conv3x3_wgrad_slabs"""
-    _need_gpu(x, dy, workspace)
-    n, H, W, Cin = x.shape
-    check(lib.sw_conv3x3_wgrad_slabs(dt(x), n, H, W, Cin, dy.shape[3], dilation, _p(x), _p(dy), _p(workspace), splitk,
-                                     _stream()), "sw_conv3x3_wgrad_slabs")
 
 
 def conv3x3_wgrad_grouped(problems, tag=None):
@@ -529,17 +521,12 @@ def colsum_fold_multi(folds):
 
 
 def colsum_nrows(X_dtype, M, N):
-    """partial rows that colsum_partial writes for an M x N matrix"""
+    """partial rows that a colsum_partial_multi problem writes for an M x N matrix"""
     return int(lib.sw_colsum_workspace_floats(dt(X_dtype), M, N)) // N
 
 
-def colsum_partial(X, M, N, workspace, ld=None):
-    check(lib.sw_colsum_partial(dt(X), M, N, _p(X), X.stride(0) if ld is None else ld, _p(workspace), _stream()),
-          "sw_colsum_partial")
-
-
 def colsum_partial_multi(parts):
-    """parts: list of (X 2-D view (M, N) with unit inner stride, workspace f32) — every colsum_partial of a backward pass in ONE launch"""
+    """parts: list of (X 2-D view (M, N) with unit inner stride, workspace f32) — the partial rows of every bias gradient of a backward pass in ONE launch"""
     from ._lib import ColsumPart
     n = len(parts)
     if n == 0:
@@ -551,11 +538,6 @@ def colsum_partial_multi(parts):
         q.M, q.N = X.shape
         q.X, q.ld, q.workspace = X.data_ptr(), X.stride(0), ws.data_ptr()
     check(lib.sw_colsum_partial_multi(dt(parts[0][0]), n, arr, _stream()), "sw_colsum_partial_multi")
-
-
-def colsum_fold(workspace, n_rows, out):
-    check(lib.sw_colsum_fold(out.numel(), n_rows, _p(workspace), _p(out), _stream()), "sw_colsum_fold")
-    return out
 
 
 def conv_weight_prep(w_oihw, wk, mode, cin_pad=None):
@@ -816,11 +798,6 @@ def convert_2d_t(src_f32, dst, rows, cols):
     """dst[c][r] = src[r][c] in dst's dtype (rows, cols multiples of 64)"""
     check(lib.sw_convert_2d_t(dt(dst), rows, cols, _p(src_f32), src_f32.stride(0), _p(dst), dst.stride(0), _stream()),
           "sw_convert_2d_t")
-    return dst
-
-
-def to_f32(src, dst):
-    check(lib.sw_to_f32(dt(src), src.numel(), _p(src), _p(dst), _stream()), "sw_to_f32")
     return dst
 
 
@@ -1332,15 +1309,6 @@ def roi_assign_levels(boxes_base, row_cnt, box_off_floats):
     rc = (ctypes.c_int * n)(*[int(v) for v in row_cnt]); bo = (ctypes.c_long * n)(*[int(v) for v in box_off_floats])
     check(lib.sw_roi_assign_levels(n, rc, bo, _p(boxes_base), _p(rois), _p(lv), _p(sel), _p(cnt), _stream()), "sw_roi_assign_levels")
     return rois, lv, sel, cnt
-
-
-def decode_boxes(deltas, boxes, weights, scale_clamp, out):
-    """deltas (n, >=4) f32 rows; boxes (n_boxes, 4), row i uses boxes[i % n_boxes]; out (n, 4)"""
-    _need_gpu(deltas, boxes, out)
-    rw = _floats(weights, 4)
-    check(lib.sw_decode_boxes(out.shape[0], boxes.shape[0], _p(deltas), deltas.stride(0), _p(boxes), rw, float(scale_clamp), _p(out),
-                              _stream()), "sw_decode_boxes")
-    return out
 
 
 def rpn_select_pack(logits, deltas, anchors, pre_topk, weights, scale_clamp, img_hw_dev, ints_out=None):

@@ -15,7 +15,6 @@ from typing import Dict, Optional
 import weakref
 
 import copy
-import os
 import torch
 
 from . import ops
@@ -274,17 +273,15 @@ class SemiSupStep:
         self.burn_up_step, self.teacher_update_iter, self.ema_keep_rate = burn_up_step, teacher_update_iter, ema_keep_rate
         self.bbox_threshold, self.unsup_loss_weight = bbox_threshold, unsup_loss_weight
         self.burn_up_with_strong_aug, self.has_multi_label = burn_up_with_strong_aug, has_multi_label
-        # speculate: the iteration's count read-backs are assumed and confirmed once (run_step; frcnn.Speculation).  SW_S3_SPECULATE=0
-        # turns it off.  With the reads gone the GPU side decides the iteration, so the teacher's pass goes on a second stream beside the
+        # speculate: the iteration's count read-backs are assumed and confirmed once (run_step; frcnn.Speculation).
+        # With the reads gone the GPU side decides the iteration, so the teacher's pass goes on a second stream beside the
         # student's backbones and labelled-batch heads (lockstep form only: that is the call that can take the pseudo labels late) and
         # its backbone replays as a hipGraph — each measured WITHOUT gain while the reads were in (16.0-16.9 vs 15.7-16.3 ms: the
         # issuing thread kept waiting at them), together 16.0 -> 13.1 ms once they were stubbed out.  overlap_teacher=None follows
-        # `speculate`; SW_S3_TEACHER_STREAM=0/1 and SW_S3_BACKBONE_GRAPH=0/1 override.
-        self.speculate = bool(speculate) and os.environ.get("SW_S3_SPECULATE", "1") != "0"
+        # `speculate`; SW_S3_BACKBONE_GRAPH=0/1 overrides the backbone graph.
+        self.speculate = bool(speculate)
         self.spec_misses, self._spec_pause = 0, 0
-        ov = self.speculate if overlap_teacher is None else bool(overlap_teacher)
-        env = os.environ.get("SW_S3_TEACHER_STREAM")
-        self.overlap_teacher = (ov if env is None else env == "1") and self.lockstep
+        self.overlap_teacher = (self.speculate if overlap_teacher is None else bool(overlap_teacher)) and self.lockstep
         tcore = getattr(model_teacher, "module", model_teacher)
         if self.speculate and hasattr(tcore, "graph_nograd_backbone"):
             tcore.graph_nograd_backbone = True

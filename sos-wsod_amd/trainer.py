@@ -54,7 +54,7 @@ class Trainer:
     every iteration (train_loop.py:274 -> comm.gather), i.e. one host sync per step."""
 
     def __init__(self, model, optimizer, data_iter=None, iter_size=1, scheduler=None, ddp=None, find_unused=False,
-                 check_finite_every=20, grad_compress=None, metrics_period=20, bucket_cap_mb=None, start_iter=0,
+                 check_finite_every=20, grad_compress=None, metrics_period=20, bucket_cap_mb=128, start_iter=0,
                  use_graph=None, overlap_update=None):
         self.raw_model = model
         self.optimizer, self.scheduler = optimizer, scheduler
@@ -66,7 +66,7 @@ class Trainer:
         self.storage = EventStorage(self.iter)
         self._finite_flag = None            # (iteration, device bool) of the last queued check
         self._grad_seed = None
-        # hipGraph replay of the whole step (forward + backward + optimizer) for recurring input signatures: see _StepGraphs
+        # hipGraph replay of the whole step (forward + backward + optimizer) for recurring input signatures: see _StepGraphs, _GraphCache
         if use_graph is None:
             use_graph = os.environ.get("SW_STEP_GRAPH", "0") == "1"
         self._graphs = None
@@ -94,11 +94,10 @@ class Trainer:
                                       use_graph=self._want_graph)
             self.overlap_update = True
         elif use_ddp:
-            if os.environ.get("SW_DDP_GRAD_IN_BUCKET", "1") == "1":
-                # ops.grad_target users: fc / conv weights and biases (the 20 predictor tensors are row slices of ONE packed gradient
-                # matrix; the reducer copies those into its bucket)
-                self._bucket_views = [p for n, p in model.named_parameters()
-                                      if p.requires_grad and ("backbone." in n or ".box_head." in n)]
+            # ops.grad_target users: fc / conv weights and biases (the 20 predictor tensors are row slices of ONE packed gradient
+            # matrix; the reducer copies those into its bucket)
+            self._bucket_views = [p for n, p in model.named_parameters()
+                                  if p.requires_grad and ("backbone." in n or ".box_head." in n)]
             dev = next(model.parameters()).device
             ids = [dev.index] if dev.type == "cuda" else None
             # broadcast_buffers=False as the reference (train_net_multi.py:76-78); every trainable parameter is used
@@ -107,10 +106,7 @@ class Trainer:
             # three backward nodes release predictors + fc7, then fc6, and the backbone node comes last.  A parameter is never
             # split, so fc1.weight (411 MB) is a bucket of its own whatever the cap; its all-reduce starts when the fc6
             # weight-gradient GEMM has finished and overlaps fc6's data gradient, the ROIPool backward and the whole conv
-            # backward; bucket_cap_mb (default SW_DDP_BUCKET_MB or 128) only groups the small tensors (predictors + fc7
-            # 68 MB, the convs 59 MB) into few launches.
-            if bucket_cap_mb is None:
-                bucket_cap_mb = float(os.environ.get("SW_DDP_BUCKET_MB", "128"))
+            # backward; bucket_cap_mb only groups the small tensors (predictors + fc7 68 MB, the convs 59 MB) into few launches.
             self.model = torch.nn.parallel.DistributedDataParallel(model, device_ids=ids, broadcast_buffers=False,
                                                                    find_unused_parameters=find_unused,
                                                                    gradient_as_bucket_view=True, bucket_cap_mb=bucket_cap_mb)
@@ -274,22 +270,6 @@ class Trainer:
                 for k, r in enumerate(aux.get("rounds", [])):
                     self.storage.put_scalar(f"roi_head/num_pgt_r{k}", r["pgt_count"].detach().clone())
 
-    @staticmethod
-    def _graphs_stage(static, data, owner):
-        """copy a step's inputs into a captured graph's static input tensors (one launch) and stage the labels"""
-        pairs, slow = [], []
-        for s_, x in zip(static, data):
-            for k in _StepGraphs.VIEW_KEYS:
-                for src, dst in ((x["image" + k], s_["image" + k]),
-                                 (x["proposals" + k].proposal_boxes.tensor, s_["proposals" + k].proposal_boxes.tensor),
-                                 (x["proposals" + k].objectness_logits, s_["proposals" + k].objectness_logits)):
-                    (pairs if src.dtype == dst.dtype and src.is_contiguous() else slow).append((src, dst))
-        from . import ops
-        ops.copy_multi(pairs)
-        for src, dst in slow:
-            dst.copy_(src, non_blocking=True)
-        owner.heads.stage_labels([x["instances1"] for x in data], owner.labels)
-
     def finish(self):
         """call after the last step: surfaces a pending non-finite flag"""
         self._raise_if_nonfinite()
@@ -376,8 +356,6 @@ class _NativeDDP:
         from . import ops as _ops
         self.upd = _ops.worker_stream("upd", self.dev)
         self.main = _ops.worker_stream("main", self.dev) if use_graph else None
-        self._dbg_sync = os.environ.get("SW_DDP_DEBUG_SYNC", "0") == "1"          # development switches
-        self._dbg_upd_main = os.environ.get("SW_DDP_UPD_MAIN", "0") == "1"
         n_pan = int(os.environ.get("SW_DDP_FC1_PANELS", "0"))
         # row panels of fc1.weight's gradient are all-reduced from inside the eager S2; a rank that REPLAYS its stage graph would issue
         # one all-reduce of the whole bucket instead — ranks pick eager / replay by their own input signature, so with stage graphs
@@ -386,10 +364,7 @@ class _NativeDDP:
         self.panels = n_pan if (n_pan > 1 and not use_graph and trainer.iter_size == 1) else 0
         self._panel_work = []
         self.use_graph = bool(use_graph)
-        self.graphs = OrderedDict()
-        self.seen = {}
-        self.pool = None
-        self.replays = self.captures = 0
+        self.cache = _GraphCache()                                 # signature -> (four stage graphs, static inputs, outputs)
         self.labels = torch.zeros(4096, dtype=torch.float32, device=self.dev) if use_graph else None
         if use_graph and hasattr(optimizer, "sync_hyper"):
             optimizer.device_hyper = True
@@ -452,9 +427,7 @@ class _NativeDDP:
 
     def _update(self, i, after=None):
         b = self.buckets[i]
-        if self._dbg_sync:
-            torch.cuda.synchronize()
-        with torch.cuda.stream(torch.cuda.current_stream() if self._dbg_upd_main else self.upd):
+        with torch.cuda.stream(self.upd):
             for job in b.work:
                 self._wait(job)
             if after is not None:
@@ -502,11 +475,11 @@ class _NativeDDP:
         self.heads._fc6_panels = (self.panels, self._panel_cb) if (self.panels and hit is None) else None
         if hit is not None:
             g1, g2, g3, g4, static, loss_dict, total = hit
-            tr._graphs_stage(static, data, self)
+            _stage_inputs(static, data, self.heads, self.labels)
             if hasattr(self.opt, "sync_hyper"):
                 self.opt.sync_hyper()
             stages = (g1.replay, g2.replay, g3.replay, g4.replay)
-            self.replays += 1
+            self.cache.replays += 1
         else:
             stages = (lambda: self._s1(data), self._s2, self._s3, self._s4)
         stepping = tr.iter % tr.iter_size == 0                      # train_net_multi.py:149 (first step at iteration 0)
@@ -537,25 +510,17 @@ class _NativeDDP:
         return loss_dict, total
 
     # ------------------------------------------------------------------ stage graphs
+    replays = property(lambda self: self.cache.replays)
+    captures = property(lambda self: self.cache.captures)
+
     def _graph_for(self, data):
-        sig = _StepGraphs._signature(self, data)
-        if sig is None:
+        sig = _step_signature(self.model, self.opt, data, lr_in_signature=False)
+        return None if sig is None else self.cache.lookup(sig, lambda: self._capture(data))
+
+    def _capture(self, data):
+        if not _momentum_ready(self.model, self.opt):               # the update must not create state between the stages
             return None
-        hit = self.graphs.get(sig)
-        if hit is not None:
-            self.graphs.move_to_end(sig)
-            return hit
-        n = self.seen.get(sig, 0) + 1
-        self.seen[sig] = n
-        if n < 2:
-            return None
-        for p in self.model.parameters():                           # the update must not create state between the stages
-            if p.requires_grad and "momentum_buffer" not in self.opt.state.get(p, {}):
-                return None
-        while len(self.graphs) >= _StepGraphs.MAX_GRAPHS:
-            old, _ = self.graphs.popitem(last=False)
-            self.seen[old] = 0
-        static = _StepGraphs._clone_inputs(data)
+        static = _clone_inputs(data)
         self.heads.stage_labels([x["instances1"] for x in data], self.labels)
         if hasattr(self.opt, "sync_hyper"):
             self.opt.sync_hyper()
@@ -567,10 +532,13 @@ class _NativeDDP:
         try:
             with ops.capture_guard():
                 for g, fn in zip(gs, fns):
-                    with torch.cuda.graph(g, pool=self.pool, stream=stream):
+                    # thread-local capture mode: the process group's watchdog thread polls the events of earlier all-reduces at any
+                    # time; under a global-mode capture that call fails ("operation not permitted when stream is capturing"),
+                    # the watchdog throws and the process aborts — now and then, when a poll falls into these few milliseconds
+                    with torch.cuda.graph(g, pool=self.cache.pool, stream=stream, capture_error_mode="thread_local"):
                         fn()
-                    if self.pool is None:
-                        self.pool = g.pool()
+                    if self.cache.pool is None:
+                        self.cache.pool = g.pool()
         finally:
             self.heads._prestaged_labels = None
         loss_dict, total = self._live[0], self._live[1]
@@ -578,14 +546,109 @@ class _NativeDDP:
         for b in self.buckets:                                      # the captures only recorded the kernels: no gradient was produced
             for p in b.params:
                 p.grad = None
+        return (gs[0], gs[1], gs[2], gs[3], static, loss_dict, total)
+
+
+VIEW_KEYS = ("1", "1_flip", "2", "2_flip")
+
+
+def _step_signature(model, optimizer, data, lr_in_signature):
+    """what a captured step is valid for (_StepGraphs docstring), or None: inputs that are not on the device"""
+    sig = []
+    for x in data:
+        for k in VIEW_KEYS:
+            im, p = x["image" + k], x["proposals" + k]
+            if not (im.is_cuda and p.proposal_boxes.tensor.is_cuda and p.objectness_logits.is_cuda):
+                return None
+            sig.append((tuple(im.shape), len(p)))
+        g = x["instances1"].gt_classes
+        sig.append(int(torch.unique(g.detach().cpu()).numel()))
+    if lr_in_signature:                      # a foreign optimizer: its hyper-parameters are frozen into the capture
+        opt = tuple((float(g["lr"]), float(g["weight_decay"]), float(g.get("momentum", 0.0))) for g in optimizer.param_groups)
+    else:
+        opt = tuple(float(g.get("momentum", 0.0)) for g in optimizer.param_groups)
+    return (tuple(sig), opt, model.training)
+
+
+def _clone_inputs(data):
+    """a step's device inputs as the static tensors of a capture"""
+    from .structures import Boxes, Instances
+    out = []
+    for x in data:
+        d = {}
+        for k, v in x.items():
+            if k.startswith("image") and isinstance(v, torch.Tensor):
+                d[k] = v.clone()
+            elif k.startswith("proposals"):
+                p = Instances(v.image_size)
+                p.proposal_boxes = Boxes(v.proposal_boxes.tensor.clone())
+                p.objectness_logits = v.objectness_logits.clone()
+                d[k] = p
+            else:
+                d[k] = v                        # instances*: host-side labels, restaged per step (stage_labels)
+        out.append(d)
+    return out
+
+
+def _stage_inputs(static, data, heads, labels):
+    """copy a step's inputs into a captured graph's static input tensors and stage the labels"""
+    pairs, slow = [], []
+    for s, x in zip(static, data):
+        for k in VIEW_KEYS:
+            for src, dst in ((x["image" + k], s["image" + k]),
+                             (x["proposals" + k].proposal_boxes.tensor, s["proposals" + k].proposal_boxes.tensor),
+                             (x["proposals" + k].objectness_logits, s["proposals" + k].objectness_logits)):
+                (pairs if src.dtype == dst.dtype and src.is_contiguous() else slow).append((src, dst))
+    from . import ops
+    ops.copy_multi(pairs)                       # one launch for the whole batch (12 tensors per image)
+    for src, dst in slow:
+        dst.copy_(src, non_blocking=True)
+    heads.stage_labels([x["instances1"] for x in data], labels)
+
+
+def _momentum_ready(model, optimizer):
+    """a captured optimizer update must not create state: every trainable parameter has its momentum buffer"""
+    return all("momentum_buffer" in optimizer.state.get(p, {}) for p in model.parameters() if p.requires_grad)
+
+
+class _GraphCache:
+    """signature -> captured step, for both users of step graphs (_StepGraphs: one graph; _NativeDDP: four stage graphs).  A signature
+    is captured the second time it is seen.  At MAX_GRAPHS the least recently used capture is dropped (its memory returns to the
+    shared capture `pool`) and has to recur twice again: with more live size buckets than graphs the steps run eagerly instead of
+    re-capturing (and evicting) every time."""
+
+    MAX_GRAPHS = 16
+    MAX_SEEN = 4096
+
+    def __init__(self):
+        self.seen = {}
+        self.graphs = OrderedDict()           # least recently used first
+        self.pool = None
+        self.replays = self.captures = self.evictions = 0
+
+    def lookup(self, sig, capture):
+        """the capture for `sig`: the stored one, or capture()'s on second sight; None on first sight, or when capture() declines by
+        returning None (nothing is evicted for a capture that does not happen).  The caller counts `replays`."""
+        hit = self.graphs.get(sig)
+        if hit is not None:
+            self.graphs.move_to_end(sig)
+            return hit
+        n = self.seen.get(sig, 0) + 1
+        self.seen[sig] = n
+        if n < 2:
+            if len(self.seen) > self.MAX_SEEN:
+                self.seen.clear()
+            return None
+        hit = capture()
+        if hit is None:
+            return None
+        while len(self.graphs) >= self.MAX_GRAPHS:
+            old, _ = self.graphs.popitem(last=False)
+            self.seen[old] = 0
+            self.evictions += 1
         self.captures += 1
-        hit = (gs[0], gs[1], gs[2], gs[3], static, loss_dict, total)
         self.graphs[sig] = hit
         return hit
-
-    # attributes _StepGraphs._signature reads
-    VIEW_KEYS = ("1", "1_flip", "2", "2_flip")
-    lr_in_signature = False
 
 
 class _StepGraphs:
@@ -599,140 +662,67 @@ class _StepGraphs:
     argument of the update).  Learning rates and weight decays are NOT part of it: a HipSGD under a graph-enabled trainer keeps
     them in a device buffer the update kernel reads (HipSGD.device_hyper, refreshed by sync_hyper() before a replay when the
     scheduler moved them), so warm-up and LR milestones neither invalidate the captured graphs nor fill the signature table.
-    A signature is captured the second time it is seen; other steps run eagerly.  At MAX_GRAPHS the least recently replayed
-    graph is dropped (its memory returns to the shared capture pool).  What varies from step to step travels through device memory the graph reads: the images and proposals are copied
+    A signature is captured the second time it is seen; other steps run eagerly (_GraphCache).  What varies from step to step travels through device memory the graph reads: the images and proposals are copied
     into the graph's static input tensors, the image-level labels into a static label buffer (OICRPlusHeads.stage_labels), and
     the dropout stream position is a device counter the graph itself advances (sw_counter_add).  One image-size bucket of a
     real training run = one graph; a run whose every image has its own size simply never replays."""
-
-    MAX_GRAPHS = 16
 
     def __init__(self, trainer):
         self.tr = trainer
         self.model = trainer.raw_model
         self.heads = self.model.roi_heads
         self.dev = next(self.model.parameters()).device
-        self.seen = {}
-        self.graphs = OrderedDict()           # signature -> captured step, least recently used first
-        self.pool = None
+        self.cache = _GraphCache()
         self.last_step_replayed = False
-        self.evictions = 0
         self.lr_in_signature = not hasattr(trainer.optimizer, "sync_hyper")
         if not self.lr_in_signature:
             trainer.optimizer.device_hyper = True
         self.labels = torch.zeros(4096, dtype=torch.float32, device=self.dev)
         from . import ops as _ops
         self.stream = _ops.worker_stream("main", self.dev)
-        self.replays = self.captures = 0
         self.enabled = True                  # False: every step runs eagerly (on the same stream) — measurements, debugging
 
-    VIEW_KEYS = ("1", "1_flip", "2", "2_flip")
-
-    def _signature(self, data):
-        sig = []
-        for x in data:
-            for k in self.VIEW_KEYS:
-                im, p = x["image" + k], x["proposals" + k]
-                if not (im.is_cuda and p.proposal_boxes.tensor.is_cuda and p.objectness_logits.is_cuda):
-                    return None
-                sig.append((tuple(im.shape), len(p)))
-            g = x["instances1"].gt_classes
-            sig.append(int(torch.unique(g.detach().cpu()).numel()))
-        if self.lr_in_signature:             # a foreign optimizer: its hyper-parameters are frozen into the capture
-            opt = tuple((float(g["lr"]), float(g["weight_decay"]), float(g.get("momentum", 0.0))) for g in self.tr.optimizer.param_groups)
-        else:
-            opt = tuple(float(g.get("momentum", 0.0)) for g in self.tr.optimizer.param_groups)
-        return (tuple(sig), opt, self.model.training)
-
-    @staticmethod
-    def _clone_inputs(data):
-        from .structures import Boxes, Instances
-        out = []
-        for x in data:
-            d = {}
-            for k, v in x.items():
-                if k.startswith("image") and isinstance(v, torch.Tensor):
-                    d[k] = v.clone()
-                elif k.startswith("proposals"):
-                    p = Instances(v.image_size)
-                    p.proposal_boxes = Boxes(v.proposal_boxes.tensor.clone())
-                    p.objectness_logits = v.objectness_logits.clone()
-                    d[k] = p
-                else:
-                    d[k] = v                        # instances*: host-side labels, restaged per step (stage_labels)
-            out.append(d)
-        return out
-
-    def _stage(self, static, data):
-        pairs, slow = [], []
-        for s, x in zip(static, data):
-            for k in self.VIEW_KEYS:
-                for src, dst in ((x["image" + k], s["image" + k]),
-                                 (x["proposals" + k].proposal_boxes.tensor, s["proposals" + k].proposal_boxes.tensor),
-                                 (x["proposals" + k].objectness_logits, s["proposals" + k].objectness_logits)):
-                    (pairs if src.dtype == dst.dtype and src.is_contiguous() else slow).append((src, dst))
-        from . import ops
-        ops.copy_multi(pairs)                       # one launch for the whole batch (12 tensors per image)
-        for src, dst in slow:
-            dst.copy_(src, non_blocking=True)
-        self.heads.stage_labels([x["instances1"] for x in data], self.labels)
+    replays = property(lambda self: self.cache.replays)
+    captures = property(lambda self: self.cache.captures)
+    evictions = property(lambda self: self.cache.evictions)
 
     def step(self, data):
         """-> (loss_dict, total) after replaying (or capturing + replaying) this step's graph, or None: run eagerly"""
         self.last_step_replayed = False
         if not self.enabled:
             return None
-        sig = self._signature(data)
-        if sig is None:
-            return None
-        hit = self.graphs.get(sig)
+        sig = _step_signature(self.model, self.tr.optimizer, data, self.lr_in_signature)
+        hit = None if sig is None else self.cache.lookup(sig, lambda: self._capture(data))
         if hit is None:
-            n = self.seen.get(sig, 0) + 1
-            self.seen[sig] = n
-            if n < 2:
-                if len(self.seen) > 4096:
-                    self.seen.clear()
-                return None
-            while len(self.graphs) >= self.MAX_GRAPHS:            # least recently replayed signature makes room
-                old_sig, _ = self.graphs.popitem(last=False)
-                self.seen[old_sig] = 0                            # it has to recur twice again: with more live size buckets than graphs
-                self.evictions += 1                               # the steps run eagerly instead of re-capturing (and evicting) every time
-            hit = self._capture(sig, data)
-            if hit is None:
-                return None
-        self.graphs.move_to_end(sig)
+            return None
         graph, static, loss_dict, losses = hit
         try:
-            self._stage(static, data)
+            _stage_inputs(static, data, self.heads, self.labels)
             if not self.lr_in_signature:
                 self.tr.optimizer.sync_hyper()                    # in stream order before the replay reads the buffer
             graph.replay()
         finally:
             self.heads._prestaged_labels = None
-        self.replays += 1
+        self.cache.replays += 1
         self.last_step_replayed = True
         return loss_dict, losses
 
-    def _capture(self, sig, data):
+    def _capture(self, data):
         tr = self.tr
-        for p in self.model.parameters():                      # the captured optimizer must not create state
-            if p.requires_grad and "momentum_buffer" not in tr.optimizer.state.get(p, {}):
-                return None
+        if not _momentum_ready(self.model, tr.optimizer):      # the captured optimizer must not create state
+            return None
         if not self.lr_in_signature:
             tr.optimizer.sync_hyper()                          # today's values, OUTSIDE the capture (the captured update only reads the buffer)
-        static = self._clone_inputs(data)
+        static = _clone_inputs(data)
         self.heads.stage_labels([x["instances1"] for x in data], self.labels)
         torch.cuda.synchronize()
         from . import ops
         graph = torch.cuda.CUDAGraph()
         try:
-            with ops.capture_guard(), torch.cuda.graph(graph, pool=self.pool, stream=self.stream):
+            with ops.capture_guard(), torch.cuda.graph(graph, pool=self.cache.pool, stream=self.stream):
                 loss_dict, losses = tr._forward_backward_update(static)
         finally:
             self.heads._prestaged_labels = None
-        if self.pool is None:
-            self.pool = graph.pool()
-        self.captures += 1
-        hit = (graph, static, loss_dict, losses)
-        self.graphs[sig] = hit
-        return hit
+        if self.cache.pool is None:
+            self.cache.pool = graph.pool()
+        return (graph, static, loss_dict, losses)

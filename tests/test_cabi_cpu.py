@@ -67,6 +67,16 @@ def test_header_symbols_exported_and_bound():
     assert L.lib.sw_version().startswith(b"soswsod-hip")
 
 
+def test_entries_without_callers_are_gone():
+    """the five entries whose Python wrappers had no caller left: neither declared nor exported (the bodies gemm.hip and elementwise.hip
+    still call are internal functions there)"""
+    import sos_wsod_amd._lib as L
+    lib = ctypes.CDLL(L.LIB_PATH)
+    for n in ("sw_conv3x3_wgrad_slabs", "sw_colsum_partial", "sw_colsum_fold", "sw_to_f32", "sw_decode_boxes"):
+        assert n not in _declared_symbols() and n not in L.SIGNATURES, n
+        assert not hasattr(lib, n), f"{n} is still exported"
+
+
 def test_ctypes_signatures_match_header_prototypes():
     """argument count, every scalar's width and kind, pointer-ness and the return type of every SIGNATURES row"""
     import sos_wsod_amd._lib as L

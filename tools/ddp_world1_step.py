@@ -31,7 +31,7 @@ def main():
     for i in range(n):
         tr.run_step(batches[i % 2])
     torch.cuda.synchronize()
-    print(f"{'DDP over RCCL world 1' if ddp else 'single process'}, {'graphs' if os.environ.get('USE_GRAPH', '0') == '1' else 'eager'}, upd_main={os.environ.get('SW_DDP_UPD_MAIN', '0')}: {(time.perf_counter() - t0) / n * 1e3:.3f} ms/step", file=sys.stderr)
+    print(f"{'DDP over RCCL world 1' if ddp else 'single process'}, {'graphs' if os.environ.get('USE_GRAPH', '0') == '1' else 'eager'}: {(time.perf_counter() - t0) / n * 1e3:.3f} ms/step", file=sys.stderr)
     tr.finish()
     if ddp:
         dist.destroy_process_group()

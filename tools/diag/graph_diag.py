@@ -20,7 +20,7 @@ torch.cuda.synchronize()
 print("OK", tr._graphs.captures, tr._graphs.replays)
 '''
 for name, args, env in [("bench-size", "512 512 2000 1 4096", {}), ("small", "96 128 80 1 256", {}), ("small-single-stream", "96 128 80 0 256", {}),
-                        ("small-no-grouped", "96 128 80 1 256", {"SW_WGRAD_GROUPED": "0"}), ("mid", "256 256 500 1 1024", {}),
+                        ("mid", "256 256 500 1 1024", {}),
                         ("small-bigdan", "96 128 80 1 4096", {}), ("big-smalldan", "512 512 2000 1 256", {})]:
     r = subprocess.run([sys.executable, "-c", "ROOT=%r\n" % ROOT + CHILD] + args.split(), env=dict(os.environ, **env), capture_output=True, text=True)
     tail = (r.stdout.strip().splitlines() or [""])[-1]

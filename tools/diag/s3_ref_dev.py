@@ -1,6 +1,5 @@
 """Stage-3 step on the stage3_step fixture (the reference's own run): 3 fresh student / teacher pairs x 3 iterations — is the trajectory
-bitwise reproducible (round 6: fixed-point ROIAlign backward), and how far is every logged loss from the reference's value?
-SW_ROI_ALIGN_BWD_FX=0 shows the float-atomic form's spread."""
+bitwise reproducible (round 6: fixed-point ROIAlign backward), and how far is every logged loss from the reference's value?"""
 import os, sys, numpy as np, torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -5,7 +5,7 @@ import torch
 import sos_wsod_amd.frcnn as F
 import stage3_step as S
 # usage: s3_toggle.py FLAG_NAME   — the Stage-3 iteration with a module switch of frcnn.py on / off, alternating, same process
-name = sys.argv[1] if len(sys.argv) > 1 else "MASKS_IN_PRODUCERS"
+name = sys.argv[1] if len(sys.argv) > 1 else "FUSED_BLOCKS"
 for rep in range(3):
     for flag in (True, False):
         setattr(F, name, flag)

@@ -3,11 +3,16 @@
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import sos_wsod_amd.ops as ops
-from sos_wsod_amd.backbone_vgg import _wgrad_grouped_splits, _wgrad_splitk
+from sos_wsod_amd.backbone_vgg import _wgrad_grouped_splits
 dt, dev = torch.bfloat16, "cuda"
 LAYERS = [("conv3_1", 128, 128, 128, 256, 1), ("conv3_2", 128, 128, 256, 256, 1), ("conv3_3", 128, 128, 256, 256, 1),
           ("conv4_1", 64, 64, 256, 512, 1), ("conv4_2", 64, 64, 512, 512, 1), ("conv4_3", 64, 64, 512, 512, 1),
           ("conv5_1", 63, 63, 512, 512, 2), ("conv5_2", 63, 63, 512, 512, 2), ("conv5_3", 63, 63, 512, 512, 2)]
+def _wgrad_splitk(cout, cin, npix):
+    """K-splits of a per-layer conv weight gradient: tiles x splits just under one resident wave of workgroups (256 CUs x 2 at 64 KiB
+    LDS each = 512 slots) was the optimum for every conv3..conv5 shape (3 / 7 / 14 / 28 splits)"""
+    tiles = ((cout + 127) // 128) * ((9 * cin + 127) // 128)
+    return max(1, min(32, 512 // tiles, max(1, npix // 1024)))
 def timeit(fn, n=10):
     for _ in range(2): fn()
     torch.cuda.synchronize(); a = torch.cuda.Event(enable_timing=True); b = torch.cuda.Event(enable_timing=True)
