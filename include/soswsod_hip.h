@@ -319,6 +319,22 @@ int sw_detect_postprocess(int R, int K, const float* all_scores, const float* al
                           float score_thresh, float nms_thresh, int topk, int32_t* det_count, float* det_boxes,
                           float* det_scores, int32_t* det_classes, int32_t* det_rows, void* workspace,
                           long workspace_bytes, sw_stream_t stream);
+/* sw_tta_merge: the merge of Stage-3 test-time augmentation for one image in one launch, without workspace or host read (reference:
+ * GeneralizedRCNNWithTTA._get_augmented_boxes / _merge_detections, detectron2/detectron2/modeling/test_time_augmentation.py:218-259,
+ * with fast_rcnn_inference_single_image, detectron2/detectron2/modeling/roi_heads/fast_rcnn.py:118-179, at score_thresh 1e-8).
+ * Inputs: the V views' PADDED detections boxes [V][T][4] f32 (16-byte aligned), scores [V][T], classes [V][T] i32, DEVICE counts [V]
+ * (row (v, s) counts iff s < counts[v]; nothing beyond a count influences the result), DEVICE view_tab [V][6] f32 = {flip (0 / 1), view
+ * width, x and y ratio view -> loader image, x and y ratio loader image -> dataset image (1 when the shapes are equal)}, the dataset
+ * image's (img_h, img_w).  Per row in float32, one rounding per step: un-flip (x -> width - x, corners re-sorted by min / max), times the
+ * first ratios, times the second; rows with a non-finite box or score are dropped; clip to the image; keep score > 1e-8 (empty boxes
+ * stay, a class outside [0, K) goes); per-class NMS (IoU > nms_thresh on boxes offset by class * (max_coord + 1), 0 / 0 suppresses
+ * nothing).  Order: inside a class score descending then union index (v * T + s) ascending; the output the survivors by score
+ * descending then union index ascending, the first topk.  Outputs det_count[1], then det_boxes [topk][4], det_scores, det_classes and
+ * det_src (union index); only the first det_count rows are written.  A counts[v] outside [0, T] gives det_count = -1 and writes nothing
+ * else.  Limits: V * T <= 2048, 1 <= K <= 1024, topk >= 1 (else -6). */
+int sw_tta_merge(int V, int T, int K, const float* boxes, const float* scores, const int32_t* classes, const int32_t* counts,
+                 const float* view_tab, int img_h, int img_w, float nms_thresh, int topk, int32_t* det_count, float* det_boxes,
+                 float* det_scores, int32_t* det_classes, int32_t* det_src, sw_stream_t stream);
 
 /* ---- small utilities ------------------------------------------------------------------------------------ */
 /* dst[c][r] = src[r][c] (rows x cols elements of `dtype`, row pitches in elements, multiples of 16 bytes).  The weight-gradient

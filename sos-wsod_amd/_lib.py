@@ -155,6 +155,8 @@ SIGNATURES = {
     "sw_detect_workspace_bytes": (c_long, [c_int, c_int, c_int]),
     "sw_detect_postprocess": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "sw_tta_merge": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sw_colsum": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p]),
     "sw_colsum_workspace_floats": (c_long, [c_int, c_int, c_int]),
     "sw_conv3x3_wgrad_small": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -95,7 +95,7 @@ def get_cfg() -> CfgNode:
     C.SEED = -1
     C.VIS_PERIOD = 0
     C.MODEL = CN(dict(
-        DEVICE="cuda", META_ARCHITECTURE="GeneralizedRCNN", WEIGHTS="", LOAD_PROPOSALS=False, MASK_ON=False,
+        DEVICE="cuda", META_ARCHITECTURE="GeneralizedRCNN", WEIGHTS="", LOAD_PROPOSALS=False, MASK_ON=False, KEYPOINT_ON=False,
         PIXEL_MEAN=[103.530, 116.280, 123.675], PIXEL_STD=[1.0, 1.0, 1.0],
         BACKBONE=dict(NAME="build_resnet_backbone", FREEZE_AT=2),
         PROPOSAL_GENERATOR=dict(NAME="RPN", MIN_SIZE=0),
@@ -116,7 +116,8 @@ def get_cfg() -> CfgNode:
                        WEIGHT_DECAY=0.0001, WEIGHT_DECAY_NORM=0.0, GAMMA=0.1, STEPS=(30000,), WARMUP_FACTOR=1.0 / 1000,
                        WARMUP_ITERS=1000, WARMUP_METHOD="linear", CHECKPOINT_PERIOD=5000, IMS_PER_BATCH=16,
                        REFERENCE_WORLD_SIZE=0, BIAS_LR_FACTOR=1.0, WEIGHT_DECAY_BIAS=0.0001))
-    C.TEST = CN(dict(EVAL_PERIOD=0, DETECTIONS_PER_IMAGE=100, AUG=dict(ENABLED=False)))
+    C.TEST = CN(dict(EVAL_PERIOD=0, DETECTIONS_PER_IMAGE=100,
+                     AUG=dict(ENABLED=False, MIN_SIZES=(400, 500, 600, 700, 800, 900, 1000, 1100, 1200), MAX_SIZE=4000, FLIP=True)))
     C.OUTPUT_DIR = "./output"
     return C
 

@@ -1011,6 +1011,187 @@ __global__ __launch_bounds__(1024) void det_merge_kernel(int K, int topk, float 
   if (tid == 0) det_count[0] = n;
 }
 
+// ------------------------------------------------------------------------------------------- Stage-3 TTA merge
+// GeneralizedRCNNWithTTA._get_augmented_boxes + _merge_detections (detectron2/modeling/test_time_augmentation.py:218-259) with
+// fast_rcnn_inference_single_image (roi_heads/fast_rcnn.py:118-179) at score_thresh 1e-8, for ONE image in ONE workgroup: the views'
+// padded detections -> inverse transforms -> drop non-finite -> clip -> score > 1e-8 -> per-class NMS on class-offset boxes -> top-k.
+//   row (v, s), s < counts[v], union index v * T + s;  view_tab[v] = {flip, view width, rx, ry (view -> loader image), px, py (loader image
+//   -> dataset image; 1 when the shapes are equal: x * 1.0f is x)}.
+//   un-flip: x -> W - x with the two x corners re-sorted by min / max (fvcore Transform.apply_box through the four corners), then * rx, ry,
+//   then * px, py: float32, one rounding per step (tta.ViewTransform.inverse_box, tta._scale_xyxy).
+//   A class outside [0, K) never gets a score column that survives `scores[:, :-1]` in the reference (K is the background column): dropped.
+// Order, where the reference's unstable sorts leave it open: inside a class score descending, then union index ascending; the final list
+// the survivors by score descending, then union index ascending, cut at topk (det_class_nms_kernel / det_merge_kernel's rule).
+// One sort key carries class | score bits | union index (10 + 32 + 11 bits: K <= 1024, V * T <= 2048), so ONE bitonic sort yields every class
+// segment in score order; the waves take the classes round-robin and resolve a segment in chunks of 64 sorted candidates (the chunk's
+// 64 x 64 matrix by ballots, the serial walk on wave-uniform masks, later candidates against the chunk's kept boxes out of registers: the
+// scheme of det_class_nms_kernel with a wave in the place of the workgroup, no barrier inside).  Survivors get a (score, union index)
+// key in place, a second sort orders them, the first topk are written (the box recomputed from its row: the LDS copy carries the class
+// offset).  A counts[v] outside [0, T] poisons the call: det_count = -1, nothing else written, nothing read beyond the arrays.
+constexpr int TTA_NMAX = 2048, TTA_KMAX = 1024;
+struct TtaRow { float b[4]; float score; int cls; bool keep; };
+__device__ __forceinline__ TtaRow tta_row(int i, int T, int K, const float* __restrict__ boxes, const float* __restrict__ scores,
+                                          const int* __restrict__ classes, const float* __restrict__ view_tab, float imw, float imh) {
+  TtaRow r;
+  const int v = i / T;
+  const float* t = view_tab + 6 * v;
+  const float4 bv = *(const float4*)(boxes + 4L * i);
+  float x0 = bv.x, y0 = bv.y, x1 = bv.z, y1 = bv.w;
+  r.score = scores[i]; r.cls = classes[i];
+  const bool fin_in = isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1) && isfinite(r.score);   // (fminf / fmaxf drop a NaN)
+  if (t[0] != 0.f) {
+    const float a = __fsub_rn(t[1], x0), b = __fsub_rn(t[1], x1);
+    x0 = fminf(a, b); x1 = fmaxf(a, b);
+  }
+  x0 = __fmul_rn(__fmul_rn(x0, t[2]), t[4]); x1 = __fmul_rn(__fmul_rn(x1, t[2]), t[4]);
+  y0 = __fmul_rn(__fmul_rn(y0, t[3]), t[5]); y1 = __fmul_rn(__fmul_rn(y1, t[3]), t[5]);
+  const bool fin = fin_in && isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1);
+  r.b[0] = clipf(x0, imw); r.b[1] = clipf(y0, imh); r.b[2] = clipf(x1, imw); r.b[3] = clipf(y1, imh);
+  r.keep = fin && r.score > 1e-8f && r.cls >= 0 && r.cls < K;
+  return r;
+}
+
+__global__ __launch_bounds__(1024) void tta_merge_kernel(int V, int T, int K, float nms_thresh, int topk, float imw, float imh,
+                                                         const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                         const int* __restrict__ classes, const int* __restrict__ counts,
+                                                         const float* __restrict__ view_tab, int* __restrict__ det_count,
+                                                         float* __restrict__ det_boxes, float* __restrict__ det_scores,
+                                                         int* __restrict__ det_classes, int* __restrict__ det_src) {
+  __shared__ unsigned long long keys[TTA_NMAX];                     // 16 KB
+  __shared__ float4 sb[TTA_NMAX];                                   // 32 KB: class-offset boxes by sorted position
+  __shared__ unsigned char sup[TTA_NMAX];
+  __shared__ unsigned short seg_lo[TTA_KMAX], seg_hi[TTA_KMAX];     // class -> [lo, hi) sorted positions
+  __shared__ int s_bad, s_valid, s_keep;
+  __shared__ unsigned int s_max;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int N = V * T;
+  const bool pos_thresh = nms_thresh >= 0.f;
+  if (tid == 0) { s_bad = 0; s_valid = 0; s_keep = 0; s_max = 0u; }
+  for (int c = tid; c < K; c += blockDim.x) { seg_lo[c] = 0; seg_hi[c] = 0; }
+  __syncthreads();
+  for (int v = tid; v < V; v += blockDim.x)
+    if (counts[v] < 0 || counts[v] > T) s_bad = 1;
+  __syncthreads();
+  if (s_bad) {                                                      // uniform
+    if (tid == 0) det_count[0] = -1;
+    return;
+  }
+  // candidates: compacted in any order (the keys are unique, the sort orders them); max coordinate of the kept clipped boxes
+  float m = 0.f;
+  for (int i0 = 0; i0 < N; i0 += blockDim.x) {
+    const int i = i0 + tid;
+    bool ok = false;
+    TtaRow r;
+    if (i < N && i - (i / T) * T < counts[i / T]) {
+      r = tta_row(i, T, K, boxes, scores, classes, view_tab, imw, imh);
+      ok = r.keep;
+    }
+    const unsigned long long bm = __ballot(ok);
+    int base = 0;
+    if (lane == 0 && bm) base = atomicAdd(&s_valid, __popcll(bm));
+    base = __shfl(base, 0);
+    if (ok) {
+      keys[base + __popcll(bm & ((1ull << lane) - 1))] =
+          ((unsigned long long)r.cls << 43) | ((unsigned long long)(~orderable(r.score)) << 11) | (unsigned long long)i;
+      m = fmaxf(m, fmaxf(fmaxf(r.b[0], r.b[2]), fmaxf(r.b[1], r.b[3])));
+    }
+  }
+  m = wave_reduce_max(m);
+  if (lane == 0) atomicMax(&s_max, __float_as_uint(m));              // clipped coordinates are >= 0: the bit order is the numeric order
+  __syncthreads();
+  const int nv = s_valid;
+  if (nv == 0) {                                                    // uniform
+    if (tid == 0) det_count[0] = 0;
+    return;
+  }
+  const int NP = next_pow2(nv);
+  for (int i = nv + tid; i < NP; i += blockDim.x) keys[i] = ~0ull;
+  __syncthreads();
+  bitonic_sort<true>(keys, NP);
+  const float maxp1 = __fadd_rn(__uint_as_float(s_max), 1.0f);
+  for (int u = tid; u < nv; u += blockDim.x) {
+    const unsigned long long key = keys[u];
+    const int c = (int)(key >> 43), i = (int)(key & 2047u);
+    const TtaRow r = tta_row(i, T, K, boxes, scores, classes, view_tab, imw, imh);
+    const float off = __fmul_rn((float)c, maxp1);
+    sb[u] = make_float4(__fadd_rn(r.b[0], off), __fadd_rn(r.b[1], off), __fadd_rn(r.b[2], off), __fadd_rn(r.b[3], off));
+    sup[u] = 0;
+    if (u == 0 || (int)(keys[u - 1] >> 43) != c) seg_lo[c] = (unsigned short)u;
+    if (u == nv - 1 || (int)(keys[u + 1] >> 43) != c) seg_hi[c] = (unsigned short)(u + 1);
+  }
+  __syncthreads();
+  int my_keep = 0;
+  for (int c = wave; c < K; c += (int)(blockDim.x >> 6)) {
+    const int lo = seg_lo[c], hi = seg_hi[c];                         // wave-uniform
+    for (int c0 = lo; c0 < hi; c0 += 64) {
+      const int cn = min(64, hi - c0);
+      const bool in = lane < cn;
+      const float4 bv = sb[c0 + (in ? lane : 0)];
+      float b[4] = {bv.x, bv.y, bv.z, bv.w};
+      unsigned long long alive = __ballot(in && !sup[c0 + lane]);
+      unsigned long long myrow = 0ull;
+      for (unsigned long long rem = alive; rem; rem &= rem - 1) {   // rows of the live candidates only: a dead one suppresses nothing
+        const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(rem));
+        float a[4] = {__int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.x), i)),
+                      __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.y), i)),
+                      __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.z), i)),
+                      __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.w), i))};
+        const unsigned long long rm = __ballot(in && lane > i && (pos_thresh ? iou_nms_above(a, b, nms_thresh) : iou_nms(a, b) > nms_thresh));
+        if (lane == i) myrow = rm;
+      }
+      unsigned long long kept = 0;
+      const int row_lo = (int)(unsigned int)myrow, row_hi = (int)(unsigned int)(myrow >> 32);
+      while (alive) {
+        const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(alive));
+        const unsigned long long ri = (unsigned long long)(unsigned int)__builtin_amdgcn_readlane(row_lo, i) |
+                                      ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane(row_hi, i) << 32);
+        kept |= 1ull << i;
+        alive &= ~(ri | (1ull << i));
+      }
+      if (in) {                                                     // survivors: make_key's (score desc, union index asc) form
+        const unsigned long long key = keys[c0 + lane];
+        keys[c0 + lane] = ((kept >> lane) & 1ull) ? (((key >> 11) & 0xFFFFFFFFull) << 32) | (key & 2047ull) : ~0ull;
+      }
+      my_keep += __popcll(kept);
+      const unsigned int klo = __builtin_amdgcn_readfirstlane((unsigned int)kept), khi = __builtin_amdgcn_readfirstlane((unsigned int)(kept >> 32));
+      for (int u0 = c0 + 64; u0 < hi; u0 += 64) {                    // later candidates of the class against this chunk's kept boxes
+        const int u = u0 + lane;
+        const bool live = u < hi && !sup[u];
+        if (!__ballot(live)) continue;
+        const float4 lv = sb[live ? u : c0];
+        float q[4] = {lv.x, lv.y, lv.z, lv.w};
+        bool hit = false;
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
+          for (unsigned int km = half ? khi : klo; km; km &= km - 1) {
+            const int k = __builtin_amdgcn_readfirstlane(__builtin_ctz(km)) + 32 * half;
+            float a[4] = {__int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.x), k)),
+                          __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.y), k)),
+                          __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.z), k)),
+                          __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.w), k))};
+            hit = hit || (pos_thresh ? iou_nms_above(a, q, nms_thresh) : iou_nms(a, q) > nms_thresh);
+          }
+        if (live && hit) sup[u] = 1;
+      }
+      // the wave reads its own sup[] writes in the next chunk: the LDS serves one wave's requests in issue order
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  if (lane == 0 && my_keep) atomicAdd(&s_keep, my_keep);
+  __syncthreads();
+  bitonic_sort<true>(keys, NP);
+  const int n = min(s_keep, topk);
+  for (int t = tid; t < n; t += blockDim.x) {
+    const unsigned long long key = keys[t];
+    const int i = (int)(key & 2047u);
+    const TtaRow r = tta_row(i, T, K, boxes, scores, classes, view_tab, imw, imh);
+    det_boxes[4 * t + 0] = r.b[0]; det_boxes[4 * t + 1] = r.b[1]; det_boxes[4 * t + 2] = r.b[2]; det_boxes[4 * t + 3] = r.b[3];
+    det_scores[t] = r.score; det_classes[t] = r.cls; det_src[t] = i;
+  }
+  if (tid == 0) det_count[0] = n;
+}
+
 }  // namespace
 
 extern "C" long sw_wsddn_workspace_floats(int V, int R, int K) {
@@ -1232,6 +1413,18 @@ extern "C" int sw_detect_postprocess(int R, int K, const float* all_scores, cons
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(det_merge_kernel, dim3(1), dim3(1024), lds2, stream, K, topk, (float)img_w, (float)img_h, all_boxes,
                      cls_count, cls_rows, cls_scores, det_count, det_boxes, det_scores, det_classes, det_rows);
+  SW_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sw_tta_merge(int V, int T, int K, const float* boxes, const float* scores, const int32_t* classes, const int32_t* counts,
+                            const float* view_tab, int img_h, int img_w, float nms_thresh, int topk, int32_t* det_count,
+                            float* det_boxes, float* det_scores, int32_t* det_classes, int32_t* det_src, hipStream_t stream) {
+  SW_ENTER();
+  if (V < 0 || T < 0 || (long)V * T > TTA_NMAX || K < 1 || K > TTA_KMAX || topk < 1) return -6;
+  if (V == 0 || T == 0) return (int)hipMemsetAsync(det_count, 0, 4, stream);
+  hipLaunchKernelGGL(tta_merge_kernel, dim3(1), dim3(1024), 0, stream, V, T, K, nms_thresh, topk, (float)img_w, (float)img_h, boxes,
+                     scores, classes, counts, view_tab, det_count, det_boxes, det_scores, det_classes, det_src);
   SW_CHECK_LAUNCH();
   return 0;
 }

@@ -1414,6 +1414,26 @@ class FastRCNNFocaltLossOutputLayers(nn.Module):
                                self.cls_score.bias, self.bbox_pred.bias)
 
 
+class PaddedDetections:
+    """A (V, T) block for the inference form of StandardROIHeadsPseudoLab with `padded_detections` set to it: image after image the
+    heads' detections land in row v = 0, 1, ... (boxes (V, T, 4), scores (V, T), classes (V, T) int32, device counts (V,) int32) — the
+    input layout of ops.tta_merge, filled without a copy.  Rows beyond a count stay zero."""
+
+    def __init__(self, V, T, device):
+        self.boxes = torch.zeros(V, T, 4, device=device); self.scores = torch.zeros(V, T, device=device)
+        self.classes = torch.zeros(V, T, dtype=torch.int32, device=device)
+        self.counts = torch.zeros(V, dtype=torch.int32, device=device)
+        self._rows = torch.empty(T, dtype=torch.int32, device=device)           # proposal indices: not kept
+        self.filled = 0
+
+    def next_out(self):
+        v = self.filled
+        if v >= self.counts.shape[0]:
+            raise IndexError("PaddedDetections: more images than rows")
+        self.filled += 1
+        return self.counts[v:v + 1], self.boxes[v], self.scores[v], self.classes[v], self._rows
+
+
 class StandardROIHeadsPseudoLab(nn.Module):
     """unbias/ubteacher/modeling/roi_heads/roi_heads.py:377-546"""
 
@@ -1427,6 +1447,7 @@ class StandardROIHeadsPseudoLab(nn.Module):
         self.loss, self.gamma = loss, (1.5 if loss == "FocalLoss" else 0.0)
         self.box_loss_type = box_loss_type
         self.keep_loss_inputs = False                 # set by TwoStagePseudoLabGeneralizedRCNN.image_losses for its one forward
+        self.padded_detections = False                # True / a PaddedDetections block: set and restored by tta.GeneralizedRCNNWithTTA
         self.box_head = FastRCNNConvFCHead()
         self.box_predictor = FastRCNNFocaltLossOutputLayers(1024, num_classes)
         self.num_classes, self.sampler = num_classes, sampler
@@ -1536,6 +1557,26 @@ class StandardROIHeadsPseudoLab(nn.Module):
             h, w = p.image_size
             sc = torch.empty(n, K + 1, device=lg.device); bx = torch.empty(n, 4 * K, device=lg.device)
             r = Instances((h, w))
+            pad = self.padded_detections
+            if pad is not False:
+                # all topk rows and the DEVICE count, no read-back (tta.GeneralizedRCNNWithTTA: the rows beyond the count are zero, the
+                # merge kernel never looks at them); a PaddedDetections block receives the rows in place, image after image
+                out = None if pad is True else pad.next_out()
+                if n:
+                    ops.oicr_predict(lg[off:off + n], n, K, 1, 0, 5 * K + 1, p.proposal_boxes.tensor.float().contiguous(), bp.bbox_weights,
+                                     SCALE_CLAMP, sc, bx)
+                    out = ops.detect_postprocess(sc, bx, int(h), int(w), bp.test_score_thresh, bp.test_nms_thresh, bp.test_topk_per_image, out=out)
+                elif out is None:
+                    T = bp.test_topk_per_image
+                    out = (torch.zeros(1, dtype=torch.int32, device=lg.device), torch.zeros(T, 4, device=lg.device), torch.zeros(T, device=lg.device),
+                           torch.zeros(T, dtype=torch.int32, device=lg.device))
+                else:
+                    out[0].zero_()
+                r.pred_boxes = Boxes(out[1]); r.scores = out[2]; r.pred_classes = out[3]           # (classes stay int32)
+                r._sw_count = out[0]
+                pred.append(r)
+                off += n
+                continue
             if n:
                 ops.oicr_predict(lg[off:off + n], n, K, 1, 0, 5 * K + 1, p.proposal_boxes.tensor.float().contiguous(), bp.bbox_weights,
                                  SCALE_CLAMP, sc, bx)

@@ -1151,6 +1151,51 @@ def detect_postprocess(all_scores, all_boxes, img_h, img_w, score_thresh, nms_th
     return cnt, boxes, scores, classes, rows
 
 
+TTA_MERGE_MAX_ROWS, TTA_MERGE_MAX_CLASSES = 2048, 1024
+
+
+def tta_merge(boxes, scores, classes, counts, view_tab, img_h, img_w, nms_thresh, topk, num_classes, out=None):
+    """sw_tta_merge: the views' padded detections boxes (V, T, 4) f32, scores (V, T) f32, classes (V, T) i32, device counts (V,) i32 and
+    view_tab (V, 6) f32 = rows of (flip, view width, rx, ry, px, py) -> (count[1] i32, boxes [topk,4], scores [topk], classes [topk] i32,
+    src [topk] i32 = union index v * T + slot) device tensors, no host read.  out: optional preallocated (count, boxes, scores, classes,
+    src) — only the first count[0] rows are written (without `out` the rest is zero).  count[0] == -1: a count outside [0, T]
+    (tta_merge_count raises on it).  V * T > 2048 or num_classes > 1024: ValueError."""
+    _need_gpu(boxes, scores, classes, counts, view_tab)
+    V, T = scores.shape
+    K = int(num_classes)
+    if V * T > TTA_MERGE_MAX_ROWS or not 1 <= K <= TTA_MERGE_MAX_CLASSES or topk < 1:
+        raise ValueError(f"tta_merge: V * T = {V * T} (limit {TTA_MERGE_MAX_ROWS}), num_classes = {K} (1 .. {TTA_MERGE_MAX_CLASSES}), "
+                         f"topk = {topk} (>= 1)")
+    if (tuple(boxes.shape) != (V, T, 4) or tuple(classes.shape) != (V, T) or tuple(counts.shape) != (V,) or tuple(view_tab.shape) != (V, 6)
+            or boxes.dtype != torch.float32 or scores.dtype != torch.float32 or view_tab.dtype != torch.float32
+            or classes.dtype != torch.int32 or counts.dtype != torch.int32
+            or not all(t.is_contiguous() for t in (boxes, scores, classes, counts, view_tab)) or boxes.data_ptr() % 16):
+        raise ValueError("tta_merge: contiguous boxes (V, T, 4) f32 (16-byte aligned), scores (V, T) f32, classes (V, T) i32, counts (V,) i32, "
+                         "view_tab (V, 6) f32 expected")
+    dev = scores.device
+    if out is not None:
+        cnt, dboxes, dscores, dclasses, src = out
+        _need_gpu(*out)
+    else:
+        cnt = torch.zeros(1, device=dev, dtype=torch.int32)
+        dboxes = torch.zeros(topk, 4, device=dev); dscores = torch.zeros(topk, device=dev)
+        dclasses = torch.zeros(topk, device=dev, dtype=torch.int32); src = torch.zeros(topk, device=dev, dtype=torch.int32)
+    rc = lib.sw_tta_merge(V, T, K, _p(boxes), _p(scores), _p(classes), _p(counts), _p(view_tab), int(img_h), int(img_w),
+                          float(nms_thresh), int(topk), _p(cnt), _p(dboxes), _p(dscores), _p(dclasses), _p(src), _stream())
+    if rc == -6:
+        raise ValueError("sw_tta_merge: V * T <= 2048, 1 <= num_classes <= 1024, topk >= 1")
+    check(rc, "sw_tta_merge")
+    return cnt, dboxes, dscores, dclasses, src
+
+
+def tta_merge_count(cnt):
+    """the one host read of a tta_merge call: its detection count; raises on the poisoned count (-1: a view's count outside [0, T])"""
+    n = int(cnt.item())
+    if n < 0:
+        raise ValueError("tta_merge: a view's detection count lies outside [0, T]")
+    return n
+
+
 # ------------------------------------------------------------------------------------------------ Stage-3 detector (csrc/detector.hip)
 def preprocess_pad(img_u8_chw, out_hw4, mean, std):
     """u8 (3, h, w) -> out (H, W, 4) = (img - mean) / std, zero padding (bottom / right) and zero 4th channel"""

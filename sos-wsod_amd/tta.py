@@ -1,4 +1,5 @@
-"""Test-time augmentation with score / box averaging (SURVEY §8f row 2;
+"""Test-time augmentation.  Stage 3 (GeneralizedRCNNWithTTA, at the end of this file): the union of the views' detections and a
+second NMS, detectron2/detectron2/modeling/test_time_augmentation.py.  Stage 1 (GeneralizedRCNNWithTTAAVG): score / box averaging (SURVEY §8f row 2;
 uwsod/projects/WSL/wsl/modeling/test_time_augmentation_avg.py:199-427, boxes only — the path has no mask head).
 
 For every augmented view (resize to a TEST.AUG min size, optional horizontal flip) the detector runs WITHOUT its
@@ -67,7 +68,9 @@ def _offset_xyxy(b: torch.Tensor, dx: float, dy: float) -> torch.Tensor:
 
 
 class DeviceTTAMapper:
-    """dataset dict -> list of (augmented dict, ViewTransform) for TEST.AUG.{MIN_SIZES, MAX_SIZE, FLIP}"""
+    """dataset dict -> list of (augmented dict, ViewTransform) for TEST.AUG.{MIN_SIZES, MAX_SIZE, FLIP}.  The views are made from the
+    tensor in the dict (the loader's already resized image); "height" / "width" stay the dataset's.  Without "proposals" in the dict
+    (Stage 3) the views carry none."""
 
     def __init__(self, min_sizes=(480, 576, 688, 864, 1000, 1200), max_size=4000, flip=True, proposal_topk=None, min_box_size=0):
         self.min_sizes, self.max_size, self.flip = tuple(min_sizes), max_size, flip
@@ -85,13 +88,16 @@ class DeviceTTAMapper:
     def __call__(self, d):
         img = d["image"]                                     # (3, h, w) uint8
         h, w = img.shape[-2:]
-        prop = d["proposals"]
+        prop = d.get("proposals")
         out = []
         for size in self.min_sizes:
             nh, nw = self._shortest_edge(h, w, size, self.max_size)
             r, r_flip = resize_bilinear_u8(img, (nh, nw), with_flip=True)
             for flip in ((False, True) if self.flip else (False,)):
                 t = ViewTransform((h, w), (nh, nw), flip)
+                if prop is None:                             # DatasetMapperTTA (test_time_augmentation.py:28-98): the detector proposes itself
+                    out.append(({"image": r_flip if flip else r, "height": d.get("height", h), "width": d.get("width", w)}, t))
+                    continue
                 # transform_proposals (test_time_augmentation_avg.py:29-71): map, clip to the view, drop empty boxes, top-k.
                 # (The reference filters per view and later stacks the views' (R, 4K) outputs: views that drop different
                 # proposals fail there; here too the merge requires equal counts.)
@@ -175,3 +181,122 @@ class GeneralizedRCNNWithTTAAVG(torch.nn.Module):
         res.scores = dscores[:n_det]
         res.pred_classes = dclasses[:n_det].to(torch.int64)
         return {"instances": res}
+
+
+# ------------------------------------------------------------------------------------------------ Stage 3: union of the views' detections
+def view_table(tfms, loader_hw, orig_hw, device):
+    """ops.tta_merge's per-view table (V, 6) f32: flip, view width, the ratios view -> loader image (ViewTransform.inverse_box) and loader
+    image -> dataset image (the inverse of DatasetMapperTTA's `pre_tfm`; 1 when the shapes are equal) as the float32 values the tensor
+    forms multiply by"""
+    rows = []
+    for t in tfms:
+        assert t.crop_xy is None and tuple(t.orig_hw) == tuple(loader_hw)
+        rows.append([float(t.flip), float(t.new_hw[1]), t.orig_hw[1] / t.new_hw[1], t.orig_hw[0] / t.new_hw[0],
+                     orig_hw[1] / loader_hw[1] if tuple(orig_hw) != tuple(loader_hw) else 1.0,
+                     orig_hw[0] / loader_hw[0] if tuple(orig_hw) != tuple(loader_hw) else 1.0])
+    return torch.tensor(rows, dtype=torch.float32).reshape(len(rows), 6).to(device)
+
+
+def _cfg_get(node, key, default):
+    return node.get(key, default) if hasattr(node, "get") else getattr(node, key, default)
+
+
+class GeneralizedRCNNWithTTA(torch.nn.Module):
+    """detectron2/detectron2/modeling/test_time_augmentation.py:101-259, boxes only (unbias/train_net_test_tta.py with
+    unbias/configs/code_release/voc07_tta_test.yaml): every view (TEST.AUG.MIN_SIZES x flip, in the mapper's order, batches of
+    `batch_size` — a batch pads its views to a common size, so the batching is part of the result) goes through
+    `model.inference(do_postprocess=False)`; the union of the views' post-NMS detections, mapped back to the dataset image, goes through
+    a second per-class NMS at score > 1e-8 and the top TEST.DETECTIONS_PER_IMAGE are kept.
+
+    The ROI heads run with `padded_detections` set to a frcnn.PaddedDetections block: every view leaves its topk padded rows and its
+    DEVICE count in the block, ONE ops.tta_merge launch merges it, and the wrapper itself reads the device once per image (the final
+    count; the RPN's one read of its proposal counts per view batch is the detector's own).
+    `tta_mapper(dict) -> [(view dict, ViewTransform)]`."""
+
+    def __init__(self, cfg, model, tta_mapper=None, batch_size=3):
+        super().__init__()
+        if isinstance(model, torch.nn.parallel.DistributedDataParallel):
+            model = model.module
+        M, T = cfg.MODEL, cfg.TEST
+        if _cfg_get(M, "KEYPOINT_ON", False):
+            raise ValueError("GeneralizedRCNNWithTTA: MODEL.KEYPOINT_ON is not supported (the reference refuses it too)")
+        if _cfg_get(M, "MASK_ON", False):
+            raise ValueError("GeneralizedRCNNWithTTA: MODEL.MASK_ON is not supported (this path has no mask head)")
+        if _cfg_get(M, "LOAD_PROPOSALS", False):
+            raise ValueError("GeneralizedRCNNWithTTA: MODEL.LOAD_PROPOSALS is not supported (the reference refuses it too; the Stage-1 "
+                             "variant for precomputed proposals is GeneralizedRCNNWithTTAAVG)")
+        if not (hasattr(model, "inference") and hasattr(getattr(model, "roi_heads", None), "padded_detections")):
+            raise TypeError(f"GeneralizedRCNNWithTTA needs a detector whose ROI heads have the `padded_detections` form, got {type(model).__name__}")
+        A = _cfg_get(T, "AUG", {})
+        self.model = model
+        self.num_classes = int(M.ROI_HEADS.NUM_CLASSES)
+        self.nms_thresh = float(_cfg_get(M.ROI_HEADS, "NMS_THRESH_TEST", 0.5))
+        self.topk = int(_cfg_get(T, "DETECTIONS_PER_IMAGE", 100))
+        if tta_mapper is None:
+            tta_mapper = DeviceTTAMapper(tuple(_cfg_get(A, "MIN_SIZES", (400, 500, 600, 700, 800, 900, 1000, 1100, 1200))),
+                                         int(_cfg_get(A, "MAX_SIZE", 4000)), bool(_cfg_get(A, "FLIP", True)))
+        self.tta_mapper = tta_mapper
+        self.batch_size = int(batch_size)
+        if self.batch_size < 1:
+            raise ValueError("GeneralizedRCNNWithTTA: batch_size >= 1")
+        self._tabs = {}                                         # (views' geometry, dataset (h, w)) -> device view table
+        self.train(model.training)                              # a fresh Module is in training mode: evaluation.inference_on_dataset restores
+        #                                                         the mode it found, which must be the detector's, not the wrapper's default
+
+    @torch.no_grad()
+    def __call__(self, batched_inputs: List[dict]):
+        return [self._inference_one_image(x) for x in batched_inputs]
+
+    def _view_table(self, tfms, loader_hw, orig, device):
+        key = (tuple((t.new_hw, t.flip) for t in tfms), tuple(loader_hw), tuple(orig), str(device))
+        tab = self._tabs.get(key)
+        if tab is None:
+            if len(self._tabs) >= 256:
+                self._tabs.clear()
+            tab = self._tabs[key] = view_table(tfms, loader_hw, orig, device)        # (a host-to-device copy: once per geometry)
+        return tab
+
+    def merge_inputs(self, inp):
+        """-> (frcnn.PaddedDetections block of the views' detections, view table, dataset (h, w)): what the one merge launch reads"""
+        from .frcnn import PaddedDetections
+        assert not self.model.training
+        img = inp["image"].to(self.model.device)
+        h, w = (int(v) for v in img.shape[-2:])
+        orig = (int(inp.get("height", h)), int(inp.get("width", w)))
+        views = self.tta_mapper({"image": img, "height": orig[0], "width": orig[1]})
+        heads = self.model.roi_heads
+        T = heads.box_predictor.test_topk_per_image
+        block = PaddedDetections(len(views), T, img.device)
+        old = heads.padded_detections
+        heads.padded_detections = block
+        try:
+            for i in range(0, len(views), self.batch_size):
+                self.model.inference([v for v, _ in views[i:i + self.batch_size]], do_postprocess=False)
+        finally:
+            heads.padded_detections = old
+        assert block.filled == len(views)
+        return block, self._view_table([t for _, t in views], (h, w), orig, img.device), orig
+
+    def _inference_one_image(self, inp):
+        from . import ops
+        block, tab, orig = self.merge_inputs(inp)
+        cnt, boxes, scores, classes, src = ops.tta_merge(block.boxes, block.scores, block.classes, block.counts, tab, orig[0], orig[1],
+                                                          self.nms_thresh, self.topk, self.num_classes)
+        n = ops.tta_merge_count(cnt)                            # the one device -> host read of this image
+        res = Instances(orig)
+        res.pred_boxes = Boxes(boxes[:n])
+        res.scores = scores[:n]
+        res.pred_classes = classes[:n].to(torch.int64)
+        res._sw_src = src[:n]
+        return {"instances": res}
+
+
+def test_with_TTA(cfg, model, data_loader, evaluator):
+    """unbias/train_net_test_tta.py:101-115 (Trainer.test_with_TTA) for one loader / evaluator pair: evaluation.inference_on_dataset over
+    the TTA wrapper, the result keys suffixed with "_TTA" """
+    from .evaluation import inference_on_dataset
+    res = inference_on_dataset(GeneralizedRCNNWithTTA(cfg, model), data_loader, evaluator)
+    return {k + "_TTA": v for k, v in res.items()}
+
+
+test_with_TTA.__test__ = False                                  # (the reference's name; not a pytest test)
