@@ -17,6 +17,12 @@ inline int grid_for_n(long n, int block = 256) {
   return (int)(g < 1 ? 1 : (g > 1048576 ? 1048576 : g));
 }
 
+// max(v, 0) and a running maximum as torch evaluates them (F.relu = clamp_min, max_pool2d's `val > max || isnan(val)`): NaN
+// propagates (fmaxf returns the other operand: a diverged activation would vanish at the first join), -0 stays -0, and a maximum
+// that starts at -inf can return -inf.  For every other input the result is fmaxf's.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+__device__ __forceinline__ float max_keep_nan(float m, float v) { return (v > m || v != v) ? v : m; }
+
 // ------------------------------------------------------------------------------------------- input: normalise + pad
 // img u8 [3][h][w] -> out [H][W][4] = (img - mean) / std inside the image, 0 in the padding and in channel 3
 // (detectron2/modeling/meta_arch/rcnn.py:220-228 + structures/image_list.py:60-124)
@@ -81,7 +87,7 @@ __global__ __launch_bounds__(256) void stem_conv7_kernel(int N, int H, int W, in
   if (Y < OH && X < OW) {
     T* o = out + (((long)n * OH + Y) * OW + X) * 64 + g * 16;
 #pragma unroll
-    for (int c = 0; c < 16; ++c) Elem<T>::store(o + c, fmaxf(fmaf(acc[c], scale[g * 16 + c], bias[g * 16 + c]), 0.f));
+    for (int c = 0; c < 16; ++c) Elem<T>::store(o + c, relu_keep_nan(fmaf(acc[c], scale[g * 16 + c], bias[g * 16 + c])));
   }
 }
 
@@ -93,14 +99,14 @@ __global__ void maxpool3x3s2_kernel(int N, int H, int W, int C, int OH, int OW, 
     const int c = (int)(i % C); long r = i / C;
     const int ox = (int)(r % OW); r /= OW;
     const int oy = (int)(r % OH); const int b = (int)(r / OH);
-    float m = -FLT_MAX;
+    float m = -INFINITY;
     for (int ky = 0; ky < 3; ++ky) {
       const int y = oy * 2 - 1 + ky;
       if (y < 0 || y >= H) continue;
       for (int kx = 0; kx < 3; ++kx) {
         const int x = ox * 2 - 1 + kx;
         if (x < 0 || x >= W) continue;
-        m = fmaxf(m, Elem<T>::load(in + (((long)b * H + y) * W + x) * C + c));
+        m = max_keep_nan(m, Elem<T>::load(in + (((long)b * H + y) * W + x) * C + c));
       }
     }
     Elem<T>::store(out + i, m);
@@ -119,7 +125,7 @@ __global__ void maxpool3x3s2_vec_kernel(int N, int H, int W, int C, int OH, int 
     const int oy = (int)(r % OH); const int b = (int)(r / OH);
     float m[V];
 #pragma unroll
-    for (int k = 0; k < V; ++k) m[k] = -FLT_MAX;
+    for (int k = 0; k < V; ++k) m[k] = -INFINITY;
     for (int ky = 0; ky < 3; ++ky) {
       const int y = oy * 2 - 1 + ky;
       if (y < 0 || y >= H) continue;
@@ -130,12 +136,12 @@ __global__ void maxpool3x3s2_vec_kernel(int N, int H, int W, int C, int OH, int 
         if (sizeof(T) == 2) {
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            m[2 * k] = fmaxf(m[2 * k], __uint_as_float(q[k] << 16));
-            m[2 * k + 1] = fmaxf(m[2 * k + 1], __uint_as_float(q[k] & 0xFFFF0000u));
+            m[2 * k] = max_keep_nan(m[2 * k], __uint_as_float(q[k] << 16));
+            m[2 * k + 1] = max_keep_nan(m[2 * k + 1], __uint_as_float(q[k] & 0xFFFF0000u));
           }
         } else {
 #pragma unroll
-          for (int k = 0; k < 4; ++k) m[k] = fmaxf(m[k], __uint_as_float(q[k]));
+          for (int k = 0; k < 4; ++k) m[k] = max_keep_nan(m[k], __uint_as_float(q[k]));
         }
       }
     }
@@ -182,7 +188,7 @@ template <typename T>
 __global__ void add_relu_kernel(long n, const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, int relu) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     float v = Elem<T>::load(a + i) + Elem<T>::load(b + i);
-    if (relu) v = fmaxf(v, 0.f);
+    if (relu) v = relu_keep_nan(v);
     Elem<T>::store(out + i, v);
   }
 }
