@@ -267,7 +267,7 @@ __device__ __forceinline__ void conv3x3_direct_body(const DirectArgs& g, const u
             const int x = tx0 + i2 * 16 + kq * 4 + e;
             if (y < g.H && x < g.W && co < g.Cout) {
               float v = fin[i2][j][e] + bv;
-              if (g.relu) v = fmaxf(v, 0.f);
+              if (g.relu) v = relu_keep_nan(v);
               const long o = (((long)img * g.H + y) * g.W + x) * g.Cout + co;
               if (reff && !(reff[o] > 0.f)) v = 0.f;
               outf[o] = v;
@@ -286,7 +286,7 @@ __device__ __forceinline__ void conv3x3_direct_body(const DirectArgs& g, const u
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float v = fin[i2][j][e] + bv;
-          if (g.relu) v = fmaxf(v, 0.f);
+          if (g.relu) v = relu_keep_nan(v);
           const int pl = i2 * 16 + kq * 4 + e;
           S[pl * TN + (col ^ ((pl & (TN / 8 - 1)) << 3))] = f32_to_bf16_bits(v);
         }
@@ -329,7 +329,7 @@ __device__ __forceinline__ void conv3x3_direct_body(const DirectArgs& g, const u
           const int y = ty0 + 2 * wave + (pl >> 5), x = tx0 + (pl & 31);
           if (y < g.H && x < g.W && co < g.Cout) {
             float v = acc[i][j][e] + bv;
-            if (g.relu) v = fmaxf(v, 0.f);
+            if (g.relu) v = relu_keep_nan(v);
             const long o = (((long)img * g.H + y) * g.W + x) * g.Cout + co;
             if (reff && !(reff[o] > 0.f)) v = 0.f;
             outf[o] = v;
@@ -349,7 +349,7 @@ __device__ __forceinline__ void conv3x3_direct_body(const DirectArgs& g, const u
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float v = acc[i][j][e] + bv;
-        if (g.relu) v = fmaxf(v, 0.f);
+        if (g.relu) v = relu_keep_nan(v);
         const int pl = i * 16 + kq * 4 + e;                 // C/D map: row = (lane>>4)*4 + e, col = lane&15
         S[pl * TN + (col ^ ((pl & (TN / 8 - 1)) << 3))] = f32_to_bf16_bits(v);      // 16-byte groups XOR-swizzled by the row
       }
@@ -376,8 +376,8 @@ __device__ __forceinline__ void conv3x3_direct_body(const DirectArgs& g, const u
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const float lo = __uint_as_float(v[q] << 16), hi = __uint_as_float(v[q] & 0xFFFF0000u);
-            a[2 * q] = t == 0 ? lo : fmaxf(a[2 * q], lo);
-            a[2 * q + 1] = t == 0 ? hi : fmaxf(a[2 * q + 1], hi);
+            a[2 * q] = t == 0 ? lo : max_keep_nan(a[2 * q], lo);
+            a[2 * q + 1] = t == 0 ? hi : max_keep_nan(a[2 * q + 1], hi);
           }
         }
         u32x4 o;
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(256) void conv3x3_first_kernel(int nimg, int H, int
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float v = acc[i][j][e] + bv[j];
-          if (relu) v = fmaxf(v, 0.f);
+          if (relu) v = relu_keep_nan(v);
           const int pl = i * 16 + kq * 4 + e, col = j * 16 + l15;
           S[pl * 64 + (col ^ ((pl & 7) << 3))] = f32_to_bf16_bits(v);
         }

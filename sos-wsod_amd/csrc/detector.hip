@@ -17,12 +17,6 @@ inline int grid_for_n(long n, int block = 256) {
   return (int)(g < 1 ? 1 : (g > 1048576 ? 1048576 : g));
 }
 
-// max(v, 0) and a running maximum as torch evaluates them (F.relu = clamp_min, max_pool2d's `val > max || isnan(val)`): NaN
-// propagates (fmaxf returns the other operand: a diverged activation would vanish at the first join), -0 stays -0, and a maximum
-// that starts at -inf can return -inf.  For every other input the result is fmaxf's.
-__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
-__device__ __forceinline__ float max_keep_nan(float m, float v) { return (v > m || v != v) ? v : m; }
-
 // ------------------------------------------------------------------------------------------- input: normalise + pad
 // img u8 [3][h][w] -> out [H][W][4] = (img - mean) / std inside the image, 0 in the padding and in channel 3
 // (detectron2/modeling/meta_arch/rcnn.py:220-228 + structures/image_list.py:60-124)

@@ -56,15 +56,16 @@ __global__ void maxpool_fwd_kernel(int nimg, int H, int W, int C, int stride, in
     const int oy = (int)(t % OH); const int n = (int)(t / OH);
     const T* b = in + (((long)n * H + oy * stride) * W + ox * stride) * C + c;
     float m = Elem<T>::load(b);
-    m = fmaxf(m, Elem<T>::load(b + C));
-    m = fmaxf(m, Elem<T>::load(b + (long)W * C));
-    m = fmaxf(m, Elem<T>::load(b + (long)W * C + C));
+    m = max_keep_nan(m, Elem<T>::load(b + C));
+    m = max_keep_nan(m, Elem<T>::load(b + (long)W * C));
+    m = max_keep_nan(m, Elem<T>::load(b + (long)W * C + C));
     Elem<T>::store(out + i, m);
   }
 }
 
 // gather form: every input element collects from the (<= 4) windows that contain it and whose first
-// maximum (scan order (0,0),(0,1),(1,0),(1,1), strict >) is this element — torch MaxPool2d backward.
+// maximum (scan order (0,0),(0,1),(1,0),(1,1), `v > m || v != v`: a NaN wins, the last one stays) is this element — torch
+// MaxPool2d backward.
 template <typename T>
 __global__ void maxpool_bwd_kernel(int nimg, int H, int W, int C, int stride, int OH, int OW, const T* __restrict__ in,
                                    const T* __restrict__ dout, T* __restrict__ din, int relu_mask) {
@@ -87,9 +88,9 @@ __global__ void maxpool_bwd_kernel(int nimg, int H, int W, int C, int stride, in
           const int y0 = oy * stride, x0 = ox * stride;
           const T* b = in + (((long)n * H + y0) * W + x0) * C + c;
           float m = Elem<T>::load(b); int am = 0;
-          float v = Elem<T>::load(b + C); if (v > m) { m = v; am = 1; }
-          v = Elem<T>::load(b + (long)W * C); if (v > m) { m = v; am = 2; }
-          v = Elem<T>::load(b + (long)W * C + C); if (v > m) { m = v; am = 3; }
+          float v = Elem<T>::load(b + C); if (v > m || v != v) { m = v; am = 1; }
+          v = Elem<T>::load(b + (long)W * C); if (v > m || v != v) { m = v; am = 2; }
+          v = Elem<T>::load(b + (long)W * C + C); if (v > m || v != v) { m = v; am = 3; }
           if (am == (y - y0) * 2 + (x - x0)) g += Elem<T>::load(dout + (((long)n * OH + oy) * OW + ox) * C + c);
         }
       }
@@ -140,13 +141,13 @@ __global__ void maxpool_fwd_vec_kernel(int nimg, int H, int W, int C, int stride
     vload(b, a);
     vload(b + C, v);
 #pragma unroll
-    for (int q = 0; q < N; ++q) a[q] = fmaxf(a[q], v[q]);
+    for (int q = 0; q < N; ++q) a[q] = max_keep_nan(a[q], v[q]);
     vload(b + (long)W * C, v);
 #pragma unroll
-    for (int q = 0; q < N; ++q) a[q] = fmaxf(a[q], v[q]);
+    for (int q = 0; q < N; ++q) a[q] = max_keep_nan(a[q], v[q]);
     vload(b + (long)W * C + C, v);
 #pragma unroll
-    for (int q = 0; q < N; ++q) a[q] = fmaxf(a[q], v[q]);
+    for (int q = 0; q < N; ++q) a[q] = max_keep_nan(a[q], v[q]);
     vstore(out + ((((long)n * OH + oy) * OW + ox) * C + cv * N), a);
   }
 }
@@ -180,9 +181,9 @@ __global__ void maxpool_bwd_s2_kernel(int nimg, int H, int W, int C, int OH, int
 #pragma unroll
       for (int q = 0; q < N; ++q) {
         float m = v[0][q]; int am = 0;
-        if (v[1][q] > m) { m = v[1][q]; am = 1; }
-        if (v[2][q] > m) { m = v[2][q]; am = 2; }
-        if (v[3][q] > m) { m = v[3][q]; am = 3; }
+        if (v[1][q] > m || v[1][q] != v[1][q]) { m = v[1][q]; am = 1; }
+        if (v[2][q] > m || v[2][q] != v[2][q]) { m = v[2][q]; am = 2; }
+        if (v[3][q] > m || v[3][q] != v[3][q]) { m = v[3][q]; am = 3; }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           float gk = am == k ? 0.f + d[q] : 0.f;
@@ -228,13 +229,13 @@ __global__ void maxpool_bwd_vec_kernel(int nimg, int H, int W, int C, int stride
         for (int q = 0; q < N; ++q) am[q] = 0;
         vload(b + C, v);
 #pragma unroll
-        for (int q = 0; q < N; ++q) if (v[q] > m[q]) { m[q] = v[q]; am[q] = 1; }
+        for (int q = 0; q < N; ++q) if (v[q] > m[q] || v[q] != v[q]) { m[q] = v[q]; am[q] = 1; }
         vload(b + (long)W * C, v);
 #pragma unroll
-        for (int q = 0; q < N; ++q) if (v[q] > m[q]) { m[q] = v[q]; am[q] = 2; }
+        for (int q = 0; q < N; ++q) if (v[q] > m[q] || v[q] != v[q]) { m[q] = v[q]; am[q] = 2; }
         vload(b + (long)W * C + C, v);
 #pragma unroll
-        for (int q = 0; q < N; ++q) if (v[q] > m[q]) { m[q] = v[q]; am[q] = 3; }
+        for (int q = 0; q < N; ++q) if (v[q] > m[q] || v[q] != v[q]) { m[q] = v[q]; am[q] = 3; }
         vload(dout + (((long)n * OH + oy) * OW + ox) * C + cv * N, d);
         const int me = (y - y0) * 2 + (x - x0);
 #pragma unroll

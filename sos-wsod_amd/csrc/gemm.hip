@@ -587,7 +587,7 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
               x += bcol[t];
               if (g.res && ok) x += g.res_bf16 ? bf16_bits_to_f32(((const unsigned short*)g.res)[(long)m * g.ldres + n])
                                                : ((const float*)g.res)[(long)m * g.ldres + n];
-              if (g.relu) x = fmaxf(x, 0.f);
+              if (g.relu) x = relu_keep_nan(x);
               if (g.drop && ok) x = g.drop[(long)m * g.ldd + n] ? x * g.drop_scale : 0.f;
               if (g.drop_p > 0.f && ok) {                          // identical Bernoulli stream to dropout_mask_kernel (elementwise.hip)
                 unsigned long long z = drop_base + (unsigned long long)((long)m * g.N + n);
@@ -735,7 +735,7 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
         if (res_staged) v += bf16_bits_to_f32(stile[lrow * WTN + j * TS + r]);
         else if (g.res && ok) v += g.res_bf16 ? bf16_bits_to_f32(((const unsigned short*)g.res)[(long)m * g.ldres + n])
                                               : ((const float*)g.res)[(long)m * g.ldres + n];
-        if (g.relu) v = fmaxf(v, 0.f);
+        if (g.relu) v = relu_keep_nan(v);
         if (g.drop && ok) v = g.drop[(long)m * g.ldd + n] ? v * g.drop_scale : 0.f;
         if (g.drop_p > 0.f && ok) {                        // identical Bernoulli stream to dropout_mask_kernel (elementwise.hip)
           unsigned long long z = drop_base + (unsigned long long)((long)m * g.N + n);
@@ -1041,7 +1041,7 @@ __global__ __launch_bounds__(256) void splitk_fold_ep_kernel(FoldEp f) {
     }
     if (f.relu) {
 #pragma unroll
-      for (int t = 0; t < 4; ++t) x[t] = fmaxf(x[t], 0.f); }
+      for (int t = 0; t < 4; ++t) x[t] = relu_keep_nan(x[t]); }
     if (f.ref) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
