@@ -11,7 +11,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, staging
 from .registry import BACKBONE_REGISTRY
 from .structures import ShapeSpec
 
@@ -406,8 +406,8 @@ class VGG16(nn.Module):
         self.compute_dtype = compute_dtype
         self.dual_stream = True           # alternate the view batches of forward_views between two HIP streams
         self._side = None
-        self._wk_cache = {}
-        self._wk3_cache = {}
+        self._stage = staging.StageCache()          # (id(weight), mode) -> the compute-dtype kernel-layout copy
+        self._stage_x3 = staging.StageCache()       # ... -> its three-piece bf16 split (fp32x3; derived, rebuilt after every update)
         # fp32 mode: the convolutions with >= 64 channels on both sides as six-product bf16x3 convolutions (the heads' fc GEMMs: roi_heads_oicrplus
         # fp32x3).  SW_FP32X3_CONV=0 keeps them on the exact-f32 MFMA (A/B timing)
         self.fp32x3 = (compute_dtype == torch.float32 and os.environ.get("SW_FP32X3", "0") == "1"
@@ -445,24 +445,21 @@ class VGG16(nn.Module):
     def staged_weight(self, w, mode, cin_pad, dtype):
         """compute-dtype kernel-layout copy of an OIHW master weight (mode 0: forward [co][tap][ci], mode 1: data
         gradient [ci][8-tap][co]); rebuilt only when the parameter changed (the two backbone calls of an iteration and
-        the backward share one copy).  The buffers are persistent and registered in ops.STAGING, so that HipSGD's fused
+        the backward share one copy).  The buffers are persistent and registered with the optimizer, so that HipSGD's fused
         step rewrites them from the updated weights and this method finds them current (no staging kernels per step)."""
-        key = (ops.param_key(w), mode, cin_pad, dtype)
-        slot = (id(w), mode)
-        hit = self._wk_cache.get(slot)
-        if hit is not None and hit[0] == key:
-            return hit[1]
         cout, cin = w.shape[:2]
         shape = (cout, 9, cin_pad) if mode == 0 else (cin, 9, cout)
-        if hit is not None and tuple(hit[1].shape) == shape and hit[1].dtype == dtype and hit[1].device == w.device:
-            wk = hit[1]
-        else:
-            wk = torch.zeros(shape, device=w.device, dtype=dtype)
-        ops.conv_weight_prep(w.detach(), wk, mode, cin_pad if mode == 0 else None)
-        self._wk_cache[slot] = (key, wk)
-        if w.requires_grad:
-            self._register_staging(w, dtype)
-        return wk
+        slot, built = self._stage.lookup((id(w), mode), (w,), (shape,), dtype, w.device, alloc=torch.zeros,      # (zeros: the padding channels)
+                                         build=lambda b: ops.conv_weight_prep(w.detach(), b[0], mode, cin_pad if mode == 0 else None))
+        if built and w.requires_grad:
+            # ONE entry per conv weight carrying the forward and the dgrad copy (the fused SGD rewrites both in its one pass): assembled
+            # from the slots that exist, so registered again when the second mode is staged later than the first
+            both = [self._stage.get((id(w), m)) for m in (0, 1)]
+            both = [s if s is not None and s.bufs[0].dtype == dtype else None for s in both]
+            b0, b1 = (None if s is None else s.bufs[0] for s in both)
+            staging.register(w, 2, dtype, stage0=b0, stage1=b1, d0=cout, d1=cin, d2=cin if b0 is None else b0.shape[2],
+                             slots=[(s, 0) for s in both if s is not None])
+        return slot.bufs[0]
 
     def x3_layer(self, dtype, cin, cout):
         """fp32 mode with MODEL.AMD.FP32_GEMM "bf16x3" (SW_FP32X3=1): this convolution runs as a six-product bf16 convolution"""
@@ -471,33 +468,9 @@ class VGG16(nn.Module):
     def staged_weight_x3(self, w, mode, cin_pad):
         """the three-piece bf16 copy ([b1|b2|b1|b3|b2|b1] along the reduction channels) of the f32 kernel-layout weight staged_weight
         holds: mode 0 [co][tap][6 ci], mode 1 [ci][tap][6 co]; rebuilt when the parameter changed"""
-        key = (ops.param_key(w), mode, cin_pad)
-        slot = (id(w), mode)
-        hit = self._wk3_cache.get(slot)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        wk = self.staged_weight(w, mode, cin_pad, torch.float32)
-        rows, cols = wk.shape[0] * 9, wk.shape[2]
-        buf = hit[1] if hit is not None and tuple(hit[1].shape) == (wk.shape[0], 9, 6 * cols) else \
-            torch.empty(wk.shape[0], 9, 6 * cols, device=wk.device, dtype=torch.bfloat16)
-        ops.split_bf16x3(wk.view(rows, cols), 1, out=buf.view(rows, 6 * cols))
-        self._wk3_cache[slot] = (key, buf)
-        return buf
-
-    def _register_staging(self, w, dtype):
-        cout, cin = w.shape[:2]
-        s0, s1 = self._wk_cache.get((id(w), 0)), self._wk_cache.get((id(w), 1))
-        s0 = s0 if s0 is not None and s0[0][3] == dtype else None
-        s1 = s1 if s1 is not None and s1[0][3] == dtype else None
-
-        def stamp(pk, wid=id(w), cache=self._wk_cache):               # (captures the cache dict, not the module: ops.register_staging)
-            for mode in (0, 1):
-                h = cache.get((wid, mode))
-                if h is not None and h[0][3] == dtype:
-                    cache[(wid, mode)] = ((pk, mode, h[0][2], dtype), h[1])
-
-        ops.register_staging(w, 2, dtype, stage0=None if s0 is None else s0[1], stage1=None if s1 is None else s1[1],
-                             d0=cout, d1=cin, d2=(s0[0][2] if s0 is not None else cin), stamp=stamp)
+        n, k = (w.shape[0], cin_pad) if mode == 0 else (w.shape[1], w.shape[0])
+        return self._stage_x3.lookup((id(w), mode), (w,), ((n, 9, 6 * k),), torch.bfloat16, w.device, lambda b: ops.split_bf16x3(
+            self.staged_weight(w, mode, cin_pad, torch.float32).view(9 * n, k), 1, out=b[0].view(9 * n, 6 * k)))[0].bufs[0]
 
     def stage_all_weights(self, with_dgrad):
         """build every compute-dtype weight copy on the CURRENT stream (call before forking side streams)"""

@@ -5,7 +5,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, staging
 from .registry import ROI_BOX_HEAD_REGISTRY
 from .structures import ShapeSpec
 
@@ -25,6 +25,7 @@ class DiscriminativeAdaptionNeck(nn.Module):
         assert len(conv_dims) == 0, "NUM_CONV 0 on this path (voc07_oicr_plus.yaml:26)"
         assert len(fc_dims) == 2, "the fused head kernels are laid out for fc6+fc7 (DAN_DIM of length 2)"
         self.compute_dtype = compute_dtype
+        self._stage = staging.StageCache()
         self._output_size = (input_shape.channels, input_shape.height, input_shape.width)
         d_in = int(np.prod(self._output_size))
         self.fcs = []
@@ -59,13 +60,8 @@ class DiscriminativeAdaptionNeck(nn.Module):
             d_out, d_in = fc.weight.shape
             # the compute-dtype copy is kept until the parameter changes (it was rebuilt on every call: 616 MB of traffic per view
             # at inference for fc6 + fc7)
-            key = (ops.param_key(fc.weight), self.compute_dtype, x.device)
-            hit = self.__dict__.setdefault("_fwd_stage", {}).get(i)
-            if hit is None or hit[0] != key:
-                w = torch.empty(d_out, d_in, device=x.device, dtype=self.compute_dtype)
-                ops.convert_2d(fc.weight.detach(), w, d_out, d_in)
-                self.__dict__["_fwd_stage"][i] = hit = (key, w)
-            w = hit[1]
+            w = self._stage.lookup(i, (fc.weight,), ((d_out, d_in),), self.compute_dtype, x.device,
+                                   lambda b, fc=fc: ops.convert_2d(fc.weight.detach(), b[0], *fc.weight.shape))[0].bufs[0]
             out = torch.empty(x.shape[0], d_out, device=x.device, dtype=self.compute_dtype)
             m = None if drop_masks is None else drop_masks[i]
             ops.gemm(x, w, out, x.shape[0], d_out, d_in,

@@ -8,7 +8,7 @@ Mirrors `DetectionCheckpointer` (uwsod/detectron2/checkpoint/detection_checkpoin
 
 The model's parameter names and shapes are the reference's, so a reference checkpoint loads key for key.
 Loading copies INTO the existing parameter storage: the predictor weights stay row slices of their flat master, and every
-compute-dtype weight copy is invalidated through the parameter version / optimizer epoch (`ops.param_key`).
+compute-dtype weight copy is invalidated through the parameter version / optimizer epoch (`staging.param_key`).
 """
 import logging
 import os
@@ -19,7 +19,7 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 import torch
 
-from . import ops
+from . import staging
 
 IncompatibleKeys = namedtuple("IncompatibleKeys", ["missing_keys", "unexpected_keys", "incorrect_shapes"])
 
@@ -143,7 +143,7 @@ class DetectionCheckpointer:
                 incorrect.append((k, tuple(sd[k].shape), tuple(model_sd[k].shape)))
                 sd.pop(k)
         res = self.model.load_state_dict(sd, strict=False)
-        ops.invalidate_all_staged(); ops.BUFFER_EPOCH += 1      # every cached compute-dtype weight copy is stale now
+        staging.invalidate_all(); staging.buffers_written()      # every cached compute-dtype weight copy is stale now
         missing = [k for k in res.missing_keys if k not in ("pixel_mean", "pixel_std")]     # initialised from the config anyway
         if missing:
             self.logger.warning("missing keys: %s", missing)

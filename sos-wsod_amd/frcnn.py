@@ -27,7 +27,7 @@ from typing import Dict, List
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, staging
 from .registry import META_ARCH_REGISTRY
 from .structures import Boxes, Instances
 
@@ -75,8 +75,8 @@ def _staged_of(module):
 
 class WeightStage:
     """Compute-dtype copies of every weight of one detector, rewritten by ONE launch (ops.StagePlan / sw_stage_weights_multi) when a
-    parameter or a FrozenBN buffer changed: optimizer step (version counters / ops.PARAM_EPOCH), teacher EMA (ops.PARAM_EPOCH and
-    ops.BUFFER_EPOCH), load_state_dict.  Replaces, per layer and per forward call, the fold `weight * scale`, the dtype conversion
+    parameter or a FrozenBN buffer changed: optimizer step (version counters / staging.params_written), teacher EMA (params_written and
+    buffers_written), load_state_dict.  Replaces, per layer and per forward call, the fold `weight * scale`, the dtype conversion
     and the layout change (and their autograd nodes: the layers' backward multiplies by `scale` itself)."""
 
     def __init__(self, model, compute_dtype):
@@ -96,7 +96,7 @@ class WeightStage:
         return self.plan.dtype == compute_dtype and all(e[0].data_ptr() == p for e, p in zip(self.plan._keep, self.plan.ptrs))
 
     def refresh(self):
-        key = (ops.PARAM_EPOCH, ops.BUFFER_EPOCH, tuple(t._version for t in self.sources))
+        key = (staging.epochs()[:2], tuple(t._version for t in self.sources))
         if key != self.key:
             self.plan.run()
             self.key = key
@@ -803,7 +803,7 @@ class FrozenBatchNorm2d(nn.Module):
         """(scale, shift) of y = x * scale + shift; cached: the statistics are frozen buffers (rebuilt when one of them was written,
         e.g. by load_state_dict or the teacher's EMA, which bump the tensors' version counters)"""
         key = (self.weight._version, self.bias._version, self.running_mean._version, self.running_var._version, self.weight.device,
-               ops.BUFFER_EPOCH)           # (BUFFER_EPOCH: the teacher EMA writes the buffers behind torch's version counters)
+               staging.epochs()[1])        # (buffer writes: the teacher EMA writes the buffers behind torch's version counters)
         hit = self.__dict__.get("_fold")
         if hit is None or hit[0] != key:
             scale = self.weight * torch.rsqrt(self.running_var + 1e-5)

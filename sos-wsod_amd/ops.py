@@ -84,32 +84,6 @@ class KernelTimer:
 
 
 TIMER = None
-PARAM_EPOCH = 0        # bumped whenever a kernel writes parameters behind torch's version counters ("something changed": HipSGD, EMA, ...)
-BUFFER_EPOCH = 0       # bumped by kernels that write module BUFFERS behind torch's version counters (the Stage-3 teacher EMA)
-INVALIDATE_EPOCH = 0   # bumped when EVERY cached compute-dtype copy is stale (checkpoint load, teacher EMA, re-homed parameter storage)
-
-
-def invalidate_all_staged():
-    """every cached compute-dtype weight copy is stale (parameters were written wholesale behind the version counters)"""
-    global PARAM_EPOCH, INVALIDATE_EPOCH
-    PARAM_EPOCH += 1
-    INVALIDATE_EPOCH += 1
-
-
-def mark_updated(p):
-    """a kernel (HipSGD) has just rewritten THIS parameter behind torch's version counter: its own cached copies are stale unless
-    the kernel rewrote them too and stamps them with the new key.  Per parameter: under the data-parallel trainer the update runs
-    bucket by bucket, several calls per step — a global counter made every call invalidate the stamps of the buckets before it, and
-    all but the last bucket's weights were re-staged in the next forward (12 staging launches and 0.3 ms per step)."""
-    p.__dict__["_sw_epoch"] = PARAM_EPOCH
-
-
-def param_key(p):
-    """cache key of a parameter's current value (compute-dtype weight copies are rebuilt only when it changes): storage, torch's
-    version counter, the epoch of the last wholesale invalidation and of the parameter's own last kernel update"""
-    return (p.data_ptr(), p._version, INVALIDATE_EPOCH, p.__dict__.get("_sw_epoch", 0))
-
-
 GRAD_SCOPE = None      # the active grad_scope (or None)
 
 
@@ -249,31 +223,6 @@ def grad_target(param, shape, dev):
             and view.dtype == torch.float32 and view.is_contiguous()):
         return view.detach()          # a tensor object of its own on the bucket's storage: autograd adopts a gradient only if nobody else holds it
     return torch.empty(*shape, device=dev, dtype=torch.float32)
-
-
-# Weight staging registry: id(parameter) -> dict(kind, dtype, stage0, stage1, d0, d1, d2, ld0, stamp).  Modules register the
-# persistent compute-dtype copies of their weights here; HipSGD's fused step (sw_sgd_multi) then rewrites those copies from
-# the freshly updated values and calls stamp(key) so that the module's cache sees them as current.
-STAGING = {}
-
-
-def register_staging(p, kind, dtype, stage0=None, stage1=None, d0=0, d1=0, d2=0, ld0=0, ld1=0, stamp=None):
-    """The registry must not keep a model alive: the parameter is held weakly and its entry (with the staged copies) leaves when the
-    parameter dies — a strong reference here leaked every deleted model's fc6 weight and its two bf16 copies (0.8 GB per VGG16
-    detector; bench.py builds and drops six).  `stamp` closures must not capture their module either."""
-    import weakref
-    key = id(p)
-    fresh = key not in STAGING or STAGING[key]["param"]() is not p
-    STAGING[key] = dict(param=weakref.ref(p), kind=kind, dtype=dtype, stage0=stage0, stage1=stage1, d0=d0, d1=d1, d2=d2, ld0=ld0,
-                        ld1=ld1, stamp=stamp)
-    if fresh:
-        weakref.finalize(p, _drop_staging, key)
-
-
-def _drop_staging(key):
-    ent = STAGING.get(key)
-    if ent is not None and ent["param"]() is None:             # (an id reused by a live parameter keeps its entry)
-        STAGING.pop(key, None)
 
 
 def _launch(tag, fn):
@@ -663,7 +612,7 @@ def wsddn_mil(logits, V, R, K, cls_col, det_col, gt_onehot, scores, loss_view, d
 
 
 def sgd_multi(entries, momentum, grad_scale=1.0):
-    """entries: list of dict(param, grad, buf, lr, weight_decay, first, staging=None|STAGING entry, hyper=None|device tensor
+    """entries: list of dict(param, grad, buf, lr, weight_decay, first, staging=None|staging.entry_of(param), hyper=None|device tensor
     {lr, weight_decay} read by the kernel instead of the two floats).  One launch per 24."""
     from ._lib import SgdTensor
     n = len(entries)

@@ -11,31 +11,24 @@ gradient of softmax(dim=1) * softmax(dim=0)), so caller-side losses built from t
 their logits (attribute `_sw_logits`), which lets `losses` / `inference` run the FUSED kernels; a caller that dropped the
 attribute on the way (`.detach()`, slicing, `torch.cat` over images) still gets the same values: the OICR functions re-join
 `scores | deltas`, the WSDDN loss falls back to the reference's own expression on the scores.
-The compute-dtype copy of a layer's weights is cached on the layer until a parameter changes (ops.param_key)."""
+The compute-dtype copy of a layer's weights is cached on the layer until a parameter changes (staging.StageCache)."""
 import torch
 
-from . import ops
+from . import ops, staging
 
 
 class _HipLinear(torch.autograd.Function):
     """y (N, out) f32 = x (N, in) @ W^T + b through the MFMA GEMM; explicit backward"""
 
     @staticmethod
-    def forward(ctx, x, w, b, compute_dtype, staged=None):
+    def forward(ctx, x, w, b, compute_dtype, ws):
         ops._need_gpu(x, w)
         N, D = x.shape
         out_f = w.shape[0]
         xs = x.detach().contiguous()
         if xs.dtype != compute_dtype:
             xs = xs.to(compute_dtype)
-        ld = (out_f + 7) // 8 * 8                                            # 16-byte K pieces for the data-gradient GEMM
-        if staged is not None and staged[0] is not None:
-            ws = staged[0]                                                   # the layer's cached copy (still current)
-        else:
-            ws = torch.zeros(ld, D, device=x.device, dtype=compute_dtype)    # rows beyond out_f stay zero
-            ops.convert_2d(w.detach().float().contiguous(), ws, out_f, D)
-            if staged is not None:
-                staged[0] = ws
+        ld = ws.shape[0]                        # the layer's cached compute-dtype copy of w (_linear_cached): out_f rounded up to 8, pad rows zero
         y = torch.empty(N, ld, device=x.device, dtype=torch.float32)[:, :out_f]
         ops.gemm(xs, ws, y, N, out_f, D, ep=ops.make_epilogue(bias=None if b is None else b.detach().float().contiguous(),
                                                               out_dtype=torch.float32))
@@ -91,12 +84,16 @@ def _linear_cached(layer, names, x, compute_dtype):
     """x @ cat(weights)^T + cat(biases) with the compute-dtype operand cached on the layer while no parameter changed"""
     ws_ = [getattr(layer, n).weight for n in names]
     bs_ = [getattr(layer, n).bias for n in names]
-    key = (tuple(ops.param_key(p) for p in ws_), compute_dtype, x.device)
-    hit = layer.__dict__.get("_api_stage")
-    box = [hit[1] if (hit is not None and hit[0] == key) else None]
-    y = _HipLinear.apply(x, torch.cat(ws_, 0), torch.cat(bs_, 0), compute_dtype, box)
-    layer.__dict__["_api_stage"] = (key, box[0])
-    return y
+    w, b = torch.cat(ws_, 0), torch.cat(bs_, 0)
+    out_f, D = w.shape
+    cache = layer.__dict__.get("_api_cache")
+    if cache is None:
+        cache = layer.__dict__["_api_cache"] = staging.StageCache()
+    # out_f rounded up to 8 rows (16-byte K pieces for the data-gradient GEMM), the pad rows zero; a new tensor per rebuild: the
+    # autograd node of an earlier call may still hold the old one
+    slot, _ = cache.lookup("w", ws_, (((out_f + 7) // 8 * 8, D),), compute_dtype, x.device, alloc=torch.zeros, reuse=False,
+                           build=lambda bufs: ops.convert_2d(w.detach().float().contiguous(), bufs[0], out_f, D))
+    return _HipLinear.apply(x, w, b, compute_dtype, slot.bufs[0])
 
 
 class _WsddnScores(torch.autograd.Function):

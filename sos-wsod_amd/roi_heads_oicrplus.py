@@ -25,7 +25,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, staging
 from .box_head import DiscriminativeAdaptionNeck  # noqa: F401  (registers the box head the configs name)
 from .events import get_event_storage, has_event_storage
 from .fast_rcnn_oicr import OICROutputLayers
@@ -241,12 +241,12 @@ class OICRPlusHeads(nn.Module):
         self._drop_counter_host = 0       # stream position; lives in a device scalar once the first training forward ran, so that
         self._drop_ctr_dev = None         # a captured hipGraph of the step draws a fresh mask on every replay
         self._prestaged_labels = None     # graph capture / replay: (static device buffer, per-image class counts), see stage_labels
-        self._stage_cache = {}            # name -> (key list, persistent compute-dtype weight copy)
+        self._stage = staging.StageCache()        # "fc1", "fc2", "heads": the persistent compute-dtype operands the optimizer keeps current
+        self._derived = staging.StageCache()      # "heads_t" and the fp32x3 splits: derived from those, rebuilt after every update
         # fp32 mode only: the fc6 / fc7 GEMMs (forward, data and weight gradient: 97 % of the fp32 step's MFMA time) as six-product
         # bf16x3 GEMMs — about f32 accuracy at 16/6 of the exact-f32 MFMA rate (ops.gemm_f32x3).  Off by default: the parity mode
         # stays the exact-f32 MFMA; MODEL.AMD.FP32_GEMM "bf16x3" / SW_FP32X3=1 turn it on.
         self.fp32x3 = compute_dtype == torch.float32 and os.environ.get("SW_FP32X3", "0") == "1"
-        self._x3_cache = {}
         self.debug_drop_masks = None      # tests: [[m1, m2] per view] uint8 keep masks (A.2 #9)
         self.last_aux = None              # tests / metrics: device tensors of the last iteration
         K = num_classes
@@ -371,7 +371,7 @@ class OICRPlusHeads(nn.Module):
                 row += n
         assert row == self.n_head_cols
         self._head_flat = (flat_w, flat_b)
-        ops.invalidate_all_staged()
+        staging.invalidate_all()
 
     def _head_flat_ok(self, params, device):
         flat = getattr(self, "_head_flat", None)
@@ -388,26 +388,20 @@ class OICRPlusHeads(nn.Module):
 
     def _pack_head_weights(self, params, device):
         """10 (out, 4096) f32 masters -> one (ld_head, 4096) compute-dtype operand + f32 bias vector.  The operand is a
-        persistent buffer registered in ops.STAGING per predictor weight (row slice), so after an optimizer step it is
+        persistent buffer registered with the optimizer per predictor weight (row slice), so after an optimizer step it is
         already current."""
         if not self._head_flat_ok(params, device):
             self._flatten_head_params(device)
-            self._stage_cache.pop("heads", None)
         flat_w, flat_b = self._head_flat
         ws = [params[i] for i in range(4, len(params), 2)]
-        keys = [ops.param_key(w) for w in ws]
-        hit = self._stage_cache.get("heads")
-        if hit is not None and hit[0] == keys and hit[1].dtype == self.compute_dtype:
-            return hit[1], flat_b
-        Wh = torch.empty(self.ld_head, flat_w.shape[1], device=device, dtype=self.compute_dtype)
-        ops.convert_2d(flat_w, Wh, self.ld_head, flat_w.shape[1])
-        self._stage_cache["heads"] = (keys, Wh)
+        slot, built = self._stage.lookup("heads", ws, ((self.ld_head, flat_w.shape[1]),), self.compute_dtype, device,
+                                         lambda b: ops.convert_2d(flat_w, b[0], self.ld_head, flat_w.shape[1]))
+        Wh = slot.bufs[0]
         row = 0
-        for j, w in enumerate(ws):
+        for j, w in enumerate(ws if built else ()):
             n = w.shape[0]
             if w.requires_grad:
-                ops.register_staging(w, 1, self.compute_dtype, stage0=Wh[row:row + n], d0=Wh.shape[1], ld0=Wh.stride(0),
-                                     stamp=lambda pk, j=j, keys=keys: keys.__setitem__(j, pk))
+                staging.register(w, 1, self.compute_dtype, stage0=Wh[row:row + n], d0=Wh.shape[1], ld0=Wh.stride(0), slots=[(slot, j)])
             row += n
         return Wh, flat_b
 
@@ -418,49 +412,33 @@ class OICRPlusHeads(nn.Module):
         LD, D = Wh.shape
         if LD % 64 or D % 64 or not hasattr(self, "_head_flat"):
             return None
-        keys = list(self._stage_cache["heads"][0])
-        hit = self._stage_cache.get("heads_t")
-        if hit is not None and hit[0] == keys and hit[1].dtype == Wh.dtype and hit[1].device == device:
-            return hit[1]
-        buf = hit[1] if (hit is not None and hit[1].dtype == Wh.dtype and hit[1].device == device) else _padded(D, LD, device, Wh.dtype)
-        ops.convert_2d_t(self._head_flat[0], buf, LD, D)
-        self._stage_cache["heads_t"] = (keys, buf)
-        return buf
+        return self._derived.lookup("heads_t", self._flat_params()[4::2], ((D, LD),), Wh.dtype, device, alloc=_padded,
+                                    build=lambda b: ops.convert_2d_t(self._head_flat[0], b[0], LD, D))[0].bufs[0]
 
     def _staged_matrix(self, name, w, device, transposed=False):
         """persistent compute-dtype copy (padded row pitch) of an fc weight; see _pack_head_weights.  transposed=True
         also keeps the (cols, rows) transposed copy: the data-gradient GEMM then reads the weight K-contiguous like the
-        forward does (as a K-strided operand of 49 KiB row pitch it ran 25 % slower).  Returns copy or (copy, copy^T)."""
+        forward does (as a K-strided operand of 49 KiB row pitch it ran 25 % slower).  Returns (copy, copy^T or None)."""
         dt_ = self.compute_dtype
         rows, cols = w.shape
         transposed = transposed and rows % 64 == 0 and cols % 64 == 0
-        key = [ops.param_key(w)]
-        hit = self._stage_cache.get(name)
-        if hit is not None and hit[0] == key and hit[1].dtype == dt_ and hit[1].device == device and \
-                (hit[2] is not None or not transposed):
-            return (hit[1], hit[2]) if transposed else hit[1]
-        reuse = hit is not None and tuple(hit[1].shape) == (rows, cols) and hit[1].dtype == dt_ and hit[1].device == device
-        buf = hit[1] if reuse else _padded(rows, cols, device, dt_)
-        ops.convert_2d(w.detach(), buf, rows, cols)
-        buf_t = None
-        if transposed:
-            buf_t = hit[2] if (reuse and hit[2] is not None) else _padded(cols, rows, device, dt_)
-            ops.convert_2d_t(w.detach(), buf_t, rows, cols)
-        self._stage_cache[name] = (key, buf, buf_t)
-        if w.requires_grad:
-            ops.register_staging(w, 3 if transposed else 1, dt_, stage0=buf, stage1=buf_t, d0=cols, ld0=buf.stride(0),
-                                 ld1=0 if buf_t is None else buf_t.stride(0),
-                                 stamp=lambda pk, key=key: key.__setitem__(0, pk))
-        return (buf, buf_t) if transposed else buf
+
+        def build(bufs):
+            ops.convert_2d(w.detach(), bufs[0], rows, cols)
+            if transposed:
+                ops.convert_2d_t(w.detach(), bufs[1], rows, cols)
+        slot, built = self._stage.lookup(name, (w,), ((rows, cols), (cols, rows))[:1 + transposed], dt_, device, build, alloc=_padded)
+        buf, buf_t = slot.bufs[0], slot.bufs[1] if transposed else None
+        if built and w.requires_grad:
+            staging.register(w, 3 if transposed else 1, dt_, stage0=buf, stage1=buf_t, d0=cols, ld0=buf.stride(0),
+                             ld1=0 if buf_t is None else buf_t.stride(0), slots=[(slot, 0)])
+        return buf, buf_t
 
     def _x3_weight(self, name, w_master, staged_f32):
         """the three-piece bf16 operand (B side, K along the columns) of a staged f32 weight matrix, rebuilt when the master changed"""
-        key = ops.param_key(w_master)
-        hit = self._x3_cache.get(name)
-        if hit is None or hit[0] != key:
-            hit = (key, ops.split_bf16x3(staged_f32, 1, out=None if hit is None else hit[1]))
-            self._x3_cache[name] = hit
-        return hit[1]
+        rows, cols = staged_f32.shape
+        return self._derived.lookup(name, (w_master,), ((rows, 6 * cols),), torch.bfloat16, staged_f32.device, alloc=_padded,
+                                    build=lambda b: ops.split_bf16x3(staged_f32, 1, out=b[0]))[0].bufs[0]
 
     def _fc_gemm(self, A, B, C, M, N, K, ep=None, tag=None, a_kstrided=False, b_kstrided=False, wname=None, wmaster=None):
         """an fc-family GEMM: the compute dtype's own sw_gemm, or (fp32 mode with fp32x3) the six-product bf16x3 form; wname / wmaster:
@@ -508,12 +486,10 @@ class OICRPlusHeads(nn.Module):
                 seed = self._dropout_stream_seed()
                 ctr = self._drop_counter_device(dev)
                 hashes = [(seed, 0, 0.5, ctr), (seed, M * D1, 0.5, ctr)]       # position = device counter + offset inside the step
-        W1 = self._staged_matrix("fc1", fc1w, dev, transposed=inp["need_grad"])
-        W1, W1T = W1 if isinstance(W1, tuple) else (W1, None)
+        W1, W1T = self._staged_matrix("fc1", fc1w, dev, transposed=inp["need_grad"])
         # fc7's weight also keeps a transposed copy when a backward follows: its data gradient then reads the weight K-contiguous
         # (NT form, ping-pong loop) like fc6's — as a K-strided operand it ran 289 us against the forward's 261
-        W2 = self._staged_matrix("fc2", fc2w, dev, transposed=inp["need_grad"])
-        W2, W2T = W2 if isinstance(W2, tuple) else (W2, None)
+        W2, W2T = self._staged_matrix("fc2", fc2w, dev, transposed=inp["need_grad"])
         h1 = _padded(M, D1, dev, dt_)
         self._fc_gemm(pooled, W1, h1, M, D1, D0, ep=ops.make_epilogue(bias=fc1b, relu=True, drop_mask=masks[0], drop_hash=hashes[0], out_dtype=dt_),
                       tag="fc6_fwd", wname="fc1", wmaster=fc1w)

@@ -17,7 +17,7 @@ import weakref
 import copy
 import torch
 
-from . import ops
+from . import ops, staging
 from .structures import Boxes, Instances
 
 
@@ -75,12 +75,12 @@ def update_teacher_model(student: torch.nn.Module, teacher: torch.nn.Module, kee
         v.copy_(s * (1 - keep_rate) + v * keep_rate)
     hit[2].run(keep_rate)
     # the kernel wrote the TEACHER's state behind torch's version counters: its cached compute-dtype copies are stale — the teacher's
-    # only (a wholesale ops.invalidate_all_staged() here re-staged every frozen weight of every model alive in the process once per
+    # only (a wholesale staging.invalidate_all() here re-staged every frozen weight of every model alive in the process once per
     # iteration: the student's stem / res2, a VGG / OICR model next to it)
-    ops.PARAM_EPOCH += 1
+    staging.params_written()
     for p_ in hit[4]:
-        ops.mark_updated(p_)
-    ops.BUFFER_EPOCH += 1
+        staging.mark_updated(p_)
+    staging.buffers_written()
 
 
 def threshold_bbox(data_inst: Optional[dict], proposals: Instances, thres: float = 0.7, proposal_type: str = "roih",

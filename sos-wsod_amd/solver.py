@@ -7,7 +7,7 @@ from typing import List
 
 import torch
 
-from . import ops
+from . import ops, staging
 
 
 class HipSGD(torch.optim.Optimizer):
@@ -44,7 +44,7 @@ class HipSGD(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
         """One launch (sw_sgd_multi) per 24 parameter tensors.  Parameters whose module registered compute-dtype staging
-        copies (ops.STAGING) get those rewritten from the updated values in the same pass.  Parameters already updated in this
+        copies (staging.register) get those rewritten from the updated values in the same pass.  Parameters already updated in this
         iteration by step_params() (the data-parallel trainer's per-bucket update) are skipped."""
         done, self._done = self._done, set()
         self._update([(group, gi, p, p.grad) for gi, group in enumerate(self.param_groups) for p in group["params"]
@@ -77,9 +77,8 @@ class HipSGD(torch.optim.Optimizer):
         if self._group_of is None:
             self._group_of = {id(q): (group, gi) for gi, group in enumerate(self.param_groups) for q in group["params"]}
         ent = self._group_of.get(id(p))
-        staging = ops.STAGING.get(id(p))
-        if (ent is None or staging is None or staging["param"]() is not p or staging["kind"] != 3 or not self._staging_usable(staging, p)
-                or p.dtype != torch.float32 or not p.is_contiguous()):
+        staged = staging.entry_of(p)
+        if (ent is None or staged is None or staged["kind"] != 3 or p.dtype != torch.float32 or not p.is_contiguous()):
             return None
         group, gi = ent
         if self.device_hyper and (self._hyper_dev is None or not torch.cuda.is_current_stream_capturing()):
@@ -91,19 +90,12 @@ class HipSGD(torch.optim.Optimizer):
             # which is torch.optim.SGD's first step, instead of momentum taken from uninitialised memory
             st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
         entry = dict(param=p, buf=st["momentum_buffer"], lr=group["lr"], weight_decay=group["weight_decay"], first=first,
-                     staging=staging, hyper=self._hyper_dev[gi] if self.device_hyper else None)
-
-        def finish():
-            ops.PARAM_EPOCH += 1
-            ops.mark_updated(p)
-            if staging["stamp"] is not None:
-                staging["stamp"](ops.param_key(p))
-        return entry, float(group["momentum"]), finish
+                     staging=staged, hyper=self._hyper_dev[gi] if self.device_hyper else None)
+        return entry, float(group["momentum"]), lambda: staging.updated(p)
 
     def _update(self, items, grad_scale):
         if not items:
             return
-        ops.PARAM_EPOCH += 1
         by_mom = {}
         if self.device_hyper and (self._hyper_dev is None or not torch.cuda.is_current_stream_capturing()):
             self.sync_hyper()                  # (inside a capture the copy would freeze today's values into the graph)
@@ -115,26 +107,13 @@ class HipSGD(torch.optim.Optimizer):
             first = "momentum_buffer" not in st
             if first:
                 st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)
-            staging = ops.STAGING.get(id(p))
-            if staging is not None and (staging["param"]() is not p or not self._staging_usable(staging, p)):
-                staging = None
             by_mom.setdefault(float(group["momentum"]), []).append(
                 dict(param=p, grad=g, buf=st["momentum_buffer"], lr=group["lr"], weight_decay=group["weight_decay"],
-                     first=first, staging=staging, hyper=self._hyper_dev[gi] if self.device_hyper else None))
+                     first=first, staging=staging.entry_of(p), hyper=self._hyper_dev[gi] if self.device_hyper else None))
         for mom, entries in by_mom.items():
             ops.sgd_multi(entries, mom, grad_scale)
             for e in entries:
-                ops.mark_updated(e["param"])
-            for e in entries:
-                if e["staging"] is not None and e["staging"]["stamp"] is not None:
-                    e["staging"]["stamp"](ops.param_key(e["param"]))
-
-    @staticmethod
-    def _staging_usable(st, p):
-        for t in (st["stage0"], st["stage1"]):
-            if t is not None and t.device != p.device:
-                return False
-        return True
+                staging.updated(e["param"])
 
     def zero_grad(self, set_to_none=True):
         super().zero_grad(set_to_none=set_to_none)

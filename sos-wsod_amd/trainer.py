@@ -351,8 +351,8 @@ class _NativeDDP:
             with torch.no_grad():
                 for t in list(model.parameters()) + list(model.buffers()):
                     dist.broadcast(t.data, 0, group=self.group)
-            from . import ops
-            ops.invalidate_all_staged()
+            from . import staging
+            staging.invalidate_all()
         from . import ops as _ops
         self.upd = _ops.worker_stream("upd", self.dev)
         self.main = _ops.worker_stream("main", self.dev) if use_graph else None

@@ -77,19 +77,13 @@ def main():
     replays = tr_ddp._native.replays if (native and graph) else 0
     # the bucket-by-bucket update (several HipSGD calls per step) must leave EVERY staged compute-dtype weight copy current: a
     # forward after the steps re-stages nothing (a global update counter once invalidated all but the last bucket's stamps)
-    import sos_wsod_amd.ops as ops
     bb, hd = m_ddp.backbone, m_ddp.roi_heads
     stale = []
-    for (wid, mode), (key, buf) in bb._wk_cache.items():
+    for wid, mode in bb._stage:
         w = next(c.weight for blk in bb.blocks for c in blk.convs() if id(c.weight) == wid)
-        if w.requires_grad and key[0] != ops.param_key(w):
+        if w.requires_grad and not bb._stage.is_current((wid, mode)):
             stale.append(("conv", mode))
-    if hd._stage_cache["fc1"][0] != [ops.param_key(hd.box_head.fc1.weight)]:
-        stale.append("fc1")
-    if hd._stage_cache["fc2"][0] != [ops.param_key(hd.box_head.fc2.weight)]:
-        stale.append("fc2")
-    if hd._stage_cache["heads"][0] != [ops.param_key(p) for p in hd._flat_params()[4::2]]:
-        stale.append("heads")
+    stale += [name for name in ("fc1", "fc2", "heads") if not hd._stage.is_current(name)]
     m_ref, tr_ref, _ = run(False)
     same = all(torch.equal(a.detach(), b.detach()) for a, b in zip(m_ddp.parameters(), m_ref.parameters()))
     moved = float((m_ddp.roi_heads.box_head.fc1.weight.detach() - torch.from_numpy(P["roi_heads.box_head.fc1.weight"]).to(dev)).abs().max())

@@ -21,7 +21,7 @@ def _model():
 
 
 def test_pth_roundtrip_with_optimizer_scheduler_and_iteration(tmp_path):
-    import sos_wsod_amd.ops as ops
+    import sos_wsod_amd.staging as staging
     from sos_wsod_amd.checkpoint import DetectionCheckpointer
     from sos_wsod_amd.solver import WarmupMultiStepLR
     torch.manual_seed(0)
@@ -40,9 +40,9 @@ def test_pth_roundtrip_with_optimizer_scheduler_and_iteration(tmp_path):
     m2 = _model()
     opt2 = torch.optim.SGD(m2.parameters(), lr=0.5, momentum=0.9)
     sch2 = WarmupMultiStepLR(opt2, [5, 8], warmup_iters=3)
-    epoch = ops.PARAM_EPOCH
+    epoch = staging.epochs()[0]
     extra = DetectionCheckpointer(m2, str(tmp_path), optimizer=opt2, scheduler=sch2).resume_or_load("", resume=True)
-    assert extra == {"iteration": 3} and ops.PARAM_EPOCH > epoch          # cached weight copies are invalidated
+    assert extra == {"iteration": 3} and staging.epochs()[0] > epoch          # cached weight copies are invalidated
     for (k, a), (_, b) in zip(m1.state_dict().items(), m2.state_dict().items()):
         assert torch.equal(a, b), k
     assert sch2.last_epoch == sch1.last_epoch and opt2.param_groups[0]["lr"] == opt1.param_groups[0]["lr"]

@@ -219,15 +219,16 @@ def test_inference_matches_reference_golden(golden_dir):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_fused_staging_keeps_weight_copies_current(golden_dir, dtype):
-    """The optimizer rewrites the persistent compute-dtype weight copies (ops.STAGING) in its update pass.  After 3 steps
+    """The optimizer rewrites the persistent compute-dtype weight copies (staging.register) in its update pass.  After 3 steps
     every registered copy must equal, bit for bit, what the staging kernels make of the CURRENT f32 master, and the
     modules' caches must report those copies as current (so the next forward launches no staging kernel)."""
     import sos_wsod_amd.ops as ops
+    import sos_wsod_amd.staging as staging
     from sos_wsod_amd.solver import HipSGD
     from sos_wsod_amd.trainer import Trainer
     g, P, views, gt, masks, _ = _setup("s0", golden_dir, dtype)
     data = to_batched_inputs(views, gt)
-    ops.STAGING.clear()
+    staging.REGISTRY.clear()
     model = build_model(int(g["K"]), tuple(int(x) for x in g["dan"]), dtype)
     load_params(model, P)
     model.train()
@@ -236,12 +237,21 @@ def test_fused_staging_keeps_weight_copies_current(golden_dir, dtype):
     opt = HipSGD([{"params": [p], "lr": 1e-3, "weight_decay": 5e-4} for p in model.parameters() if p.requires_grad],
                  1e-3, momentum=0.9)
     tr = Trainer(model, opt)
-    for _ in range(3):
+    bb, hd = model.backbone, model.roi_heads
+
+    def staged_ptrs():                                             # every staged buffer, the ones rebuilt in every step included
+        caches = (bb._stage, bb._stage_x3, hd._stage, hd._derived)
+        return {(i, n): [b.data_ptr() for b in c.buffers(n)] for i, c in enumerate(caches) for n in c}
+    ptrs = None
+    for step in range(3):
         tr.run_step(data)
+        if step == 0:                                                  # captured step graphs hold these addresses
+            ptrs = staged_ptrs()
     torch.cuda.synchronize()
-    assert len(ops.STAGING) >= 9 + 2 + 10, len(ops.STAGING)        # conv3_1..conv5_3, fc6/fc7, 10 predictor matrices
+    assert ptrs == staged_ptrs() and "heads_t" in hd._derived
+    assert len(staging.REGISTRY) >= 9 + 2 + 10, len(staging.REGISTRY)        # conv3_1..conv5_3, fc6/fc7, 10 predictor matrices
     n_checked = 0
-    for st in ops.STAGING.values():
+    for st in staging.REGISTRY.values():
         p = st["param"]()
         if st["kind"] == 2:
             for mode, buf in ((0, st["stage0"]), (1, st["stage1"])):
@@ -259,13 +269,14 @@ def test_fused_staging_keeps_weight_copies_current(golden_dir, dtype):
         if v.requires_grad:
             assert not torch.equal(v.detach(), w0[k]), k               # the steps did move the weights
     # caches are current: a forward after the steps must not rebuild anything
-    bb, hd = model.backbone, model.roi_heads
-    for (wid, mode), (key, buf) in bb._wk_cache.items():
-        w = next(c.weight for blk in bb.blocks for c in blk.convs() if id(c.weight) == wid)
-        assert key[0] == ops.param_key(w)
-    assert hd._stage_cache["fc1"][0] == [ops.param_key(hd.box_head.fc1.weight)]
-    assert hd._stage_cache["fc2"][0] == [ops.param_key(hd.box_head.fc2.weight)]
-    assert hd._stage_cache["heads"][0] == [ops.param_key(p) for p in hd._flat_params()[4::2]]
+    assert len(list(bb._stage)) >= 13 + 8
+    for name in bb._stage:
+        assert bb._stage.is_current(name), name
+    assert hd._stage.is_current("fc1") and hd._stage.is_current("fc2") and hd._stage.is_current("heads")
+    # builds: of the caches whose slots the optimizer re-stamps (the derived copies are rebuilt after every update, by design)
+    builds = bb._stage.builds + hd._stage.builds
+    tr.run_step(data)
+    assert bb._stage.builds + hd._stage.builds == builds
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -440,11 +451,11 @@ def test_checkpoint_load_invalidates_the_compute_copies(golden_dir, tmp_path):
         losses = model(data)
     torch.cuda.synchronize()
     ref_sd = other.state_dict()
-    assert torch.equal(hd._stage_cache["fc1"][1], ref_sd["roi_heads.box_head.fc1.weight"].to(dtype))
+    assert torch.equal(hd._stage.buffers("fc1")[0], ref_sd["roi_heads.box_head.fc1.weight"].to(dtype))
     flat_w, _ = hd._head_flat
     assert hd.box_predictor.cls.weight.data_ptr() == flat_w.data_ptr()                 # still a view of the flat master
     assert torch.equal(flat_w[:int(g["K"])], ref_sd["roi_heads.box_predictor.cls.weight"])
-    wk = model.backbone._wk_cache[(id(model.backbone.blocks[4].convs()[2].weight), 0)][1]
+    wk = model.backbone._stage.buffers((id(model.backbone.blocks[4].convs()[2].weight), 0))[0]
     want = torch.zeros_like(wk)
     ops.conv_weight_prep(ref_sd["backbone.plain5.0.conv3.weight"], want, 0, 512)
     assert torch.equal(wk, want)

@@ -1048,6 +1048,7 @@ def test_fused_update_entry_without_its_gemm_leaves_a_first_step(ops):
     """HipSGD.fused_update_entry creates the momentum buffer before the fused GEMM runs.  When that GEMM is never launched (or fails), the
     next ordinary step() already counts as a later step (momentum * buffer + d_p): the buffer must hold zeros then, so that the step is
     torch.optim.SGD's first one — the same bits as a fresh HipSGD's first step, and torch's up to rounding."""
+    import sos_wsod_amd.staging as staging
     from sos_wsod_amd.solver import HipSGD
     M, N = 128, 256
     gen = torch.Generator(device="cuda"); gen.manual_seed(5)
@@ -1058,7 +1059,7 @@ def test_fused_update_entry_without_its_gemm_leaves_a_first_step(ops):
     def stepped(fused_entry_first):
         p = torch.nn.Parameter(w_init.clone())
         st0 = torch.zeros(M, N, device="cuda", dtype=torch.bfloat16); st1 = torch.zeros(N, M, device="cuda", dtype=torch.bfloat16)
-        ops.register_staging(p, 3, torch.bfloat16, stage0=st0, stage1=st1, d0=N, ld0=N, ld1=M)
+        staging.register(p, 3, torch.bfloat16, stage0=st0, stage1=st1, d0=N, ld0=N, ld1=M)
         opt = HipSGD([dict(params=[p], **hp)], hp["lr"], momentum=hp["momentum"])
         if fused_entry_first:
             junk = torch.full((M, N), 1e30, device="cuda"); del junk      # the block the buffer is carved from holds garbage

@@ -167,13 +167,13 @@ def test_predictions_survive_caller_side_tensor_ops():
     dets, _ = ol.inference((sc.detach(), dl.detach()), props)            # detached predictions: no AttributeError
     assert len(dets) == 2
     # the staged weight copy is cached until a parameter changes
-    st = ol.__dict__["_api_stage"][1]
+    st = ol._api_cache.buffers("w")[0]
     ol(x)
-    assert ol.__dict__["_api_stage"][1] is st
+    assert ol._api_cache.buffers("w")[0] is st
     with torch.no_grad():
         ol.cls_score.weight.add_(1.0)
     ol(x)
-    assert ol.__dict__["_api_stage"][1] is not st
+    assert ol._api_cache.buffers("w")[0] is not st
 
 
 def test_wsddn_scores_backward_kernel_against_float64():

@@ -1132,7 +1132,7 @@ def test_speculative_iteration_equals_the_reading_one(caps_reached):
 def test_detector_trains_the_same_under_hipsgd_and_torch_sgd(golden_dir):
     """Stage 3's solver is the same SGD (momentum 0.9, weight decay) as Stage 1's: the fused HipSGD and torch.optim.SGD drive the
     detector to the same parameters and losses over 3 supervised steps.  HipSGD writes the parameters behind torch's version
-    counters (ops.PARAM_EPOCH), torch's SGD bumps them: both must invalidate the detector's staged weight copies (a stale copy would
+    counters (staging.params_written), torch's SGD bumps them: both must invalidate the detector's staged weight copies (a stale copy would
     freeze the losses)."""
     from sos_wsod_amd.solver import HipSGD
     t = np.load(os.path.join(golden_dir, "stage3_a.npz"))
