@@ -6,6 +6,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, staging
+from .backbone_vgg import _dtype_from_cfg
 from .registry import ROI_BOX_HEAD_REGISTRY
 from .structures import ShapeSpec
 
@@ -40,7 +41,6 @@ class DiscriminativeAdaptionNeck(nn.Module):
 
     @classmethod
     def from_config(cls, cfg, input_shape):
-        from .backbone_vgg import _dtype_from_cfg
         return dict(input_shape=input_shape, conv_dims=[cfg.MODEL.ROI_BOX_HEAD.CONV_DIM] * cfg.MODEL.ROI_BOX_HEAD.NUM_CONV,
                     fc_dims=cfg.MODEL.ROI_BOX_HEAD.DAN_DIM, conv_norm=cfg.MODEL.ROI_BOX_HEAD.NORM,
                     compute_dtype=_dtype_from_cfg(cfg))

@@ -938,8 +938,11 @@ int launch_auto(GemmArgs& g, int splitk, hipStream_t s) {
     }
     return launch2<T, AMODE, BMODE, 256, 256, 2>(g, splitk, s);
   }
-  // 64-wide outputs (conv1_x): no half-empty N tile
-  if (g.N <= 64 && sk == 1) return launch2<T, AMODE, BMODE, 256, 64, 2, 32, 64>(g, splitk, s);
+  // 64-wide outputs (conv1_x): no half-empty N tile.  Not for a K-strided bf16 B: its LDS rows would hold 8 chunks and the
+  // transposed-read swizzle (Geom2::swz, 4 bits) needs 16 — a 1x1 weight gradient with <= 64 input channels came out wrong
+  if constexpr (!(sizeof(T) == 2 && Geom2<T, BMODE, 64>::KS)) {
+    if (g.N <= 64 && sk == 1) return launch2<T, AMODE, BMODE, 256, 64, 2, 32, 64>(g, splitk, s);
+  }
   // Few tiles and a long K (a ResNet's res4 / res5 1x1 convolutions at batch 1-2: 30-60 tiles x 16-32 K-tiles): one workgroup per
   // CU at most, and its K loop runs at one memory round trip per K-tile (~1 us against 0.15 us of MFMA work) on the 2-buffer ring.
   // A 4-buffer ring keeps three K-tiles in flight (128 KiB of LDS: fine when no second workgroup would share the CU anyway).

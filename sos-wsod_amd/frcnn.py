@@ -27,7 +27,7 @@ from typing import Dict, List
 import torch
 import torch.nn as nn
 
-from . import ops, staging
+from . import ops, staging, wgrad
 from .registry import META_ARCH_REGISTRY
 from .structures import Boxes, Instances
 
@@ -48,13 +48,8 @@ _RELU, _MASK_INPUT_GRAD, _GRAD_PREMASKED = 1, 2, 4
 FUSED_BLOCKS = True      # BottleneckBlock as one autograd node (_BottleneckFn); False: layer by layer (the form the fused one is tested against)
 
 
-def _epc(dtype):
-    return 8 if dtype == torch.bfloat16 else 4
-
-
 def _pad8(n):
     return (n + 7) // 8 * 8
-
 
 
 class _Staged:
@@ -111,7 +106,7 @@ def _pad_scale(scale, ld):
     return torch.cat([scale, torch.ones(ld - scale.shape[0], device=scale.device, dtype=scale.dtype)])
 
 
-class _LinearFn(ops.CountedFunction):
+class _LinearFn(wgrad.CountedFunction):
     """y (P, out) = x (P, in) @ W_eff^T (+ bias) (ReLU): sw_gemm with the epilogue fused; explicit backward (dgrad, wgrad GEMMs, column
     sums).  `staged` (ld, in) is the compute-dtype copy of the effective weight (rows beyond `out` zero), written by the model's
     stage plan; `bias` f32 or None; `scale` (out,) f32 or None = the FrozenBN fold (W_eff = W * scale: dW = scale * dW_eff).
@@ -149,7 +144,7 @@ class _LinearFn(ops.CountedFunction):
         ctx.shapes = [tuple(p.shape) for p in params]
         ctx.wkey = id(params[0]) if params else None
         if params and any(ctx.needs_input_grad[8:8 + len(splits)]):
-            ops.count_use(("lin", ctx.wkey))
+            wgrad.count_use(("lin", ctx.wkey))
         ctx.bkey = id(params[len(splits)]) if len(params) > len(splits) else None
         return y
 
@@ -185,35 +180,20 @@ class _LinearFn(ops.CountedFunction):
             # K = pixels (10^4 .. 10^5 for a 1x1 convolution), M x N = a handful of 128x128 tiles: K-split slabs + ordered fold inside
             # sw_gemm (deterministic; unsplit, 4 workgroups walked 60 000 pixels).  FrozenBN: dW = scale * dW_eff, applied to the rows
             # inside the fold; `scale` covers the out_f real rows, the pad rows of dwp are never handed out.  None: added to the
-            # buffer an earlier node of this backward pass returned (ops.grad_scope)
-            scope = ops.GRAD_SCOPE
-            lkey = ("lin", ctx.wkey)
-            if scope is not None and ctx.wkey is not None and scope.uses.get(lkey, 0) > 1:
-                # every use of this weight queues its (gs, x) pair; the last one runs them as one grouped launch + one fold
-                q = scope.queued.get(lkey)
-                first = q is None
-                if first:
-                    q = scope.queued[lkey] = dict(bufs=[torch.empty(ld, D, device=g.device, dtype=torch.float32)], probs=[],
-                                                  scales=[None if scale is None else _pad_scale(scale, ld)], left=scope.uses[lkey])
-                if P > 0:
-                    q["probs"].append([(gs, x)])
-                q["left"] -= 1
-                if q["left"] == 0:
-                    if q["probs"]:
-                        _flush_wgrad_1x1(q)
-                    else:
-                        q["bufs"][0].zero_()
-                dwp = q["bufs"][0] if first else None
-            else:
-                dwp = (_wgrad_1x1(gs, x, None if scale is None else _pad_scale(scale, ld), ctx.wkey) if P > 0
-                       else torch.zeros(ld, D, device=g.device, dtype=torch.float32))
+            # buffer an earlier node of this backward pass returned, or queued for the last use of this weight (wgrad.join)
+            rs = None if scale is None else _pad_scale(scale, ld)
+            dwp = wgrad.join(("lin", ctx.wkey), ((gs, x),) if P > 0 else None, ((ld, D),), (rs,), g.device, wgrad.flush_wgrad_1x1)
+            if dwp is wgrad.NOT_QUEUED:
+                dwp = wgrad.wgrad_1x1(gs, x, rs, ctx.wkey) if P > 0 else torch.zeros(ld, D, device=g.device, dtype=torch.float32)
+            elif dwp is not None:
+                dwp = dwp[0]
             r0 = 0
             for i, n in enumerate(ctx.splits):
                 if need[8 + i] and dwp is not None:
                     dws[i] = dwp[r0:r0 + n].view(ctx.shapes[i])
                 r0 += n
         if need_b:
-            dbp = _bias_grad(gs, ld, ctx.bkey)                          # (packed biases: one buffer, registered under the first one)
+            dbp = wgrad.bias_grad(gs, ld, ctx.bkey)                          # (packed biases: one buffer, registered under the first one)
             r0 = 0
             for i, n in enumerate(ctx.splits):
                 if i < len(dbs) and need[8 + nw + i] and dbp is not None:
@@ -223,7 +203,7 @@ class _LinearFn(ops.CountedFunction):
         return (dx, None, None, None, None, None, None, dres) + tuple(dws) + tuple(dbs)
 
 
-class _Conv3x3Fn(ops.CountedFunction):
+class _Conv3x3Fn(wgrad.CountedFunction):
     """3x3, stride 1, padding 1 on NHWC: sw_conv3x3_igemm (+ bias, ReLU fused) on the staged [co][tap][ci] copy of the effective
     weight; backward = weight gradient (split-K slabs, ordered fold; x FrozenBN scale), column sums, data gradient through the
     staged flipped-tap layout `staged_d` [ci][tap][co].  `w` / `b`: the parameters the gradients go to (b may be None)."""
@@ -241,7 +221,7 @@ class _Conv3x3Fn(ops.CountedFunction):
         ctx.save_for_backward(x, staged_d, out if relu else None, scale)
         ctx.relu, ctx.cout, ctx.wkey, ctx.bkey = relu, cout, id(w), (None if b is None else id(b))
         if ctx.needs_input_grad[6]:
-            ops.count_use(id(w))
+            wgrad.count_use(id(w))
         return out
 
     @staticmethod
@@ -254,9 +234,9 @@ class _Conv3x3Fn(ops.CountedFunction):
         dz = ops.relu_bwd(out, g, out=torch.empty_like(g)) if (ctx.relu and not ctx.premasked) else g
         dx = dw = db = None
         if ctx.needs_input_grad[6]:
-            dw = _wgrad_3x3(x, dz, scale, ctx.wkey)
+            dw = wgrad.wgrad_3x3(x, dz, scale, ctx.wkey)
         if ctx.needs_input_grad[7]:
-            db = _bias_grad(dz.view(n * H * W, cout), cout, ctx.bkey)
+            db = wgrad.bias_grad(dz.view(n * H * W, cout), cout, ctx.bkey)
         if ctx.needs_input_grad[0]:
             dx = torch.empty(n, H, W, cin, device=g.device, dtype=cd)
             ops.conv3x3(dz, wkd, dx, 1, ops.make_epilogue(out_dtype=cd))
@@ -277,158 +257,7 @@ def _view4(dw, cout, cin):
     return None if dw is None else dw.view(cout, cin, 1, 1)
 
 
-def _eff_splits(K, sk, bf16):
-    """the K-split count sw_gemm will really use (gemm.hip effective_splits)"""
-    bk = 64 if bf16 else 32
-    kps = -(-K // max(1, sk))
-    kps = -(-kps // bk) * bk
-    return -(-K // kps)
-
-
-def _wgrad_1x1(gs, x, scale, key=None):
-    """dW (out, in) f32 = scale[:, None] * gs^T x over the pixels: K-split slabs + ordered fold (deterministic).  Inside
-    ops.grad_scope a second use of the same weight (`key`) adds to the first use's buffer in the fold / epilogue and returns None
-    (ALWAYS, once a buffer is registered: autograd may already have replaced the registered tensor by a sum of its own if a later
-    use handed it a gradient too)."""
-    P, ld = gs.shape
-    D = x.shape[1]
-    tiles = ((ld + 127) // 128) * ((D + 127) // 128)
-    sk = max(1, min(64, 512 // tiles, P // 512))
-    prev = ops.pending_grad(key, (ld, D))
-    if prev is not None:
-        ws = None
-        if scale is not None and _eff_splits(P, sk, gs.dtype == torch.bfloat16) == 1:
-            ws = torch.empty(ld * D, device=gs.device, dtype=torch.float32)        # one slab: row scale + residual run in the fold
-        ops.gemm(gs, x, prev, ld, D, P, a_kstrided=True, b_kstrided=True, splitk=sk,
-                 ep=ops.make_epilogue(out_dtype=torch.float32, row_scale=scale, residual=prev, splitk_workspace=ws))
-        return None
-    dw = torch.empty(ld, D, device=gs.device, dtype=torch.float32)
-    ep = None if scale is None else ops.make_epilogue(out_dtype=torch.float32, row_scale=scale)
-    ops.gemm(gs, x, dw, ld, D, P, a_kstrided=True, b_kstrided=True, splitk=sk, ep=ep)
-    ops.note_grad(key, dw)
-    return dw
-
-
-def _bias_grad(gs2d, n, key=None):
-    """db (n,) f32 = column sums of the (masked) output gradient; ops.grad_scope as _wgrad_1x1 (key: the bias parameter)"""
-    P = gs2d.shape[0]
-    prev = ops.pending_grad(key, (n,))
-    if prev is not None:
-        if P > 0:
-            ops.colsum(gs2d, P, n, prev, accumulate=True)
-        return None
-    db = torch.empty(n, device=gs2d.device, dtype=torch.float32)
-    if P > 0:
-        ops.colsum(gs2d, P, n, db)
-    else:
-        db.zero_()
-    ops.note_grad(key, db)
-    return db.view(n)
-
-
-_GROUP_TARGETS_1X1 = (4, 6, 8, 12, 16, 24, 32, 40, 48, 56, 64, 72, 80, 96, 112, 128, 160)
-
-
-def _flush_wgrad_1x1(q):
-    """the queued 1x1 weight-gradient problems of one bottleneck block — per use (dh1, x), (gs, h2)[, (gs, x)] — as ONE
-    sw_gemm_kk_grouped launch and ONE sw_splitk_fold_multi (x FrozenBN scale) into the buffers autograd already holds"""
-    from .backbone_vgg import _wgrad_grouped_splits, _wgrad_grouped_target
-    uses, bufs, scales = q["probs"], q["bufs"], q["scales"]
-    dtype = uses[0][0][0].dtype
-    bk = 64 if dtype == torch.bfloat16 else 32
-    shapes = [(a.shape[0], a.shape[1], b.shape[1]) for use in uses for a, b in use]
-    target = _wgrad_grouped_target(shapes, bk, candidates=_GROUP_TARGETS_1X1)
-    probs, folds = [], []
-    for w, (buf, scale) in enumerate(zip(bufs, scales)):
-        ns = [_wgrad_grouped_splits(use[w][0].shape[0], bk, target) for use in uses]
-        nsl = [ops.gemm_kk_nslab(dtype, use[w][0].shape[0], s_) for use, s_ in zip(uses, ns)]
-        ws = torch.empty(sum(nsl), buf.numel(), device=buf.device, dtype=torch.float32)
-        off = 0
-        for use, s_, k in zip(uses, ns, nsl):
-            probs.append((use[w][0], use[w][1], ws[off:], s_))
-            off += k
-        folds.append((ws, sum(nsl), buf, scale, False))
-    ops.gemm_kk_grouped(probs)
-    ops.splitk_fold_multi(folds)
-    q["probs"] = []
-
-
-_GROUP_TARGETS = (8, 12, 16, 24, 32, 40, 48, 56, 64, 72, 80, 96, 112, 128, 160)      # K-tiles per work item tried for a grouped launch
-
-
-def _small_map(H, W):
-    """maps of a few pixels (p5 / p6 of small images: 4x4, 2x2) are below the gathering loader's tile geometry (sw_conv3x3_wgrad
-    returns -6): a direct kernel, one thread per (co, ci), takes them"""
-    return (64 // W) + 1 > 2 * H
-
-
-def _flush_wgrad_3x3(q):
-    """all queued (x, dy) pairs of one 3x3 weight: ONE grouped 256x256-tile launch (sw_conv3x3_wgrad_grouped: every pair's K-splits
-    as work items of one resident grid) + ONE fold over all slabs (x FrozenBN scale) into the buffer autograd already holds.
-    Measured (tools/probes/stage3_grouped_wgrad_probe.py): the RPN head's 10 uses 641 -> 383 us, an FPN output convolution's two 330 -> 256
-    (p2) / 71 -> 46 (p4), res5 conv2 83 -> 48, res3 conv2 74 -> 52."""
-    from .backbone_vgg import _wgrad_grouped_splits, _wgrad_grouped_target
-    dw, scale, probs = q["buf"], q["scale"], q["probs"]
-    cout, cin = dw.shape[:2]
-    big = [(x, dz) for x, dz in probs if not _small_map(x.shape[1], x.shape[2])]
-    small = [(x, dz) for x, dz in probs if _small_map(x.shape[1], x.shape[2])]
-    wrote = False
-    if big:
-        bk = 64 if big[0][0].dtype == torch.bfloat16 else 32
-        shapes = [(x.shape[0] * x.shape[1] * x.shape[2], cout, 9 * cin) for x, _ in big]
-        target = _wgrad_grouped_target(shapes, bk, candidates=_GROUP_TARGETS)
-        splits = [_wgrad_grouped_splits(sh[0], bk, target) for sh in shapes]
-        nsl = [ops.conv3x3_wgrad_nslab(x, cout, sp) for (x, _), sp in zip(big, splits)]
-        ws = torch.empty(sum(nsl), cout * 9 * cin, device=dw.device, dtype=torch.float32)
-        off, items = 0, []
-        for (x, dz), sp, n in zip(big, splits, nsl):
-            items.append((x, dz, ws[off:], 1, sp))
-            off += n
-        ops.conv3x3_wgrad_grouped(items)
-        ops.conv3x3_wgrad_fold(ws, sum(nsl), dw, cout_scale=scale)
-        wrote = True
-    for x, dz in small:
-        ops.conv3x3_wgrad_small(x, dz, dw, cout_scale=scale, accumulate=wrote)
-        wrote = True
-    q["probs"] = []
-
-
-def _wgrad_3x3(x4, dz4, scale, key=None):
-    """dW (cout, cin, 3, 3) f32 of a 3x3 convolution (sw_conv3x3_wgrad: slabs + fold, x FrozenBN scale).  Inside ops.grad_scope: a
-    weight whose uses were counted in the forward passes (ops.count_use) queues its (x, dy) pairs and the LAST use computes all of
-    them at once (_flush_wgrad_3x3) into the buffer the first use handed to autograd; an uncounted weight adds to the first use's
-    buffer in the fold, as _wgrad_1x1 does."""
-    n, H, W, cin = x4.shape
-    cout = dz4.shape[3]
-    sc = ops.GRAD_SCOPE
-    if sc is not None and key is not None and sc.uses.get(key, 0) > 1:
-        q = sc.queued.get(key)
-        first = q is None
-        if first:
-            q = sc.queued[key] = dict(buf=torch.empty(cout, cin, 3, 3, device=x4.device, dtype=torch.float32), scale=scale, probs=[],
-                                      left=sc.uses[key])
-        q["probs"].append((x4, dz4))
-        q["left"] -= 1
-        if q["left"] == 0:
-            _flush_wgrad_3x3(q)
-        return q["buf"].view(cout, cin, 3, 3) if first else None
-    prev = ops.pending_grad(key, (cout, cin, 3, 3))
-    dw = prev if prev is not None else torch.empty(cout, cin, 3, 3, device=x4.device, dtype=torch.float32)
-    if _small_map(H, W):
-        ops.conv3x3_wgrad_small(x4, dz4, dw, cout_scale=scale, accumulate=prev is not None)
-    else:
-        tiles = ((cout + 127) // 128) * ((9 * cin + 127) // 128)
-        sk = max(1, min(32, 512 // tiles, max(1, n * H * W // 1024)))
-        ops.conv3x3_wgrad(x4, dz4, dw, 1, splitk=sk, cout_scale=scale, accumulate=prev is not None)
-    if prev is not None:
-        return None
-    ops.note_grad(key, dw)
-    # (a view: the registered alias keeps `dw` itself referenced as its base, and autograd's accumulator copies a gradient whose
-    # tensor object somebody else holds instead of adopting it — 18 device-to-device copies per iteration)
-    return dw.view(cout, cin, 3, 3)
-
-
-class _BottleneckFn(ops.CountedFunction):
+class _BottleneckFn(wgrad.CountedFunction):
     """One bottleneck block (conv1 1x1 [stride s] -> ReLU -> conv2 3x3 -> ReLU -> conv3 1x1, + shortcut, ReLU) as ONE autograd node
     with an explicit backward.  Layer by layer (`_LinearFn` / `_Conv3x3Fn` nodes) every ReLU mask was a kernel of its own in front of
     the layer's gradients and autograd added the two gradients of the block input with a torch kernel; here the masks of conv1's and
@@ -496,9 +325,9 @@ class _BottleneckFn(ops.CountedFunction):
         ctx.keys = tuple(id(w) for w in weights) + (None,) * (4 - len(weights))
         if ctx.needs_input_grad[3]:
             for _ in maps:
-                ops.count_use(id(weights[1]))                            # conv2: every map's weight gradient joins one grouped launch
+                wgrad.count_use(id(weights[1]))                            # conv2: every map's weight gradient joins one grouped launch
         if all(ctx.needs_input_grad[2:]):
-            ops.count_use(("1x1", id(weights[0])))                      # the block's 1x1 weights: one grouped launch for all passes
+            wgrad.count_use(("1x1", id(weights[0])))                      # the block's 1x1 weights: one grouped launch for all passes
         n, H, W = maps[0]
         return out.view(n, H, W, cout) if single else out
 
@@ -528,8 +357,8 @@ class _BottleneckFn(ops.CountedFunction):
         dw2 = None
         if need[3]:
             for i in range(len(maps)):
-                r = _wgrad_3x3(m4(h1, i, mid), m4(dh2, i, mid), sc2, keys[1])
-                dw2 = r if dw2 is None else dw2                       # (inside ops.grad_scope only the first use hands out a buffer)
+                r = wgrad.wgrad_3x3(m4(h1, i, mid), m4(dh2, i, mid), sc2, keys[1])
+                dw2 = r if dw2 is None else dw2                       # (inside wgrad.grad_scope only the first use hands out a buffer)
                 if r is not None and r is not dw2:
                     dw2 = dw2 + r                                     # outside a scope: plain sums
         dh1 = torch.empty(P, mid, device=g.device, dtype=cd)
@@ -550,34 +379,23 @@ class _BottleneckFn(ops.CountedFunction):
                 n, H, W = in_maps[0]
                 dx = dx.view(n, H, W, cin)
         # ---- the 1x1 weight gradients: conv1 (dh1^T x), conv3 (gs^T h2), shortcut (gs^T x)
-        scope = ops.GRAD_SCOPE
-        bkey = ("1x1", keys[0])
-        dw1 = dw3 = dwsc = None
-        if scope is not None and all(need[2:]) and (scope.uses.get(bkey, 0) > 1 or (len(maps) > 1 and scope.uses.get(bkey, 0) == 1)):
-            # every pass's three problems are queued; the last use runs all of them as ONE grouped launch + ONE multi-fold
-            # (several maps in one call: the rows of all of them are one problem per weight — still one grouped launch)
-            q = scope.queued.get(bkey)
-            first = q is None
-            if first:
-                shp = [(mid, cin), (cout, mid)] + ([(cout, cin)] if wsc is not None else [])
-                q = scope.queued[bkey] = dict(bufs=[torch.empty(a, b, device=g.device, dtype=torch.float32) for a, b in shp],
-                                              scales=[sc1, sc3] + ([scs] if wsc is not None else []), probs=[], left=scope.uses[bkey])
-            q["probs"].append([(dh1, x2), (gs, h2)] + ([(gs, x2)] if wsc is not None else []))
-            q["left"] -= 1
-            if q["left"] == 0:
-                _flush_wgrad_1x1(q)
-            if first:
-                dw1, dw3 = q["bufs"][0].view(mid, cin, 1, 1), q["bufs"][1].view(cout, mid, 1, 1)
-                dwsc = q["bufs"][2].view(cout, cin, 1, 1) if wsc is not None else None
-        else:
-            dw3 = _view4(_wgrad_1x1(gs, h2, sc3, keys[2]), cout, mid) if need[4] else None
-            dw1 = _view4(_wgrad_1x1(dh1, x2, sc1, keys[0]), mid, cin) if need[2] else None
-            if wsc is not None and len(need) > 5 and need[5]:
-                dwsc = _view4(_wgrad_1x1(gs, x2, scs, keys[3]), cout, cin)
-        return (dx, None, dw1, dw2, dw3) + ((dwsc,) if wsc is not None else ())
+        # every pass's three problems are queued; the last use runs all of them as ONE grouped launch + ONE multi-fold (several maps
+        # in one call: the rows of all of them are one problem per weight — still one grouped launch, so one counted use is enough)
+        nw = 2 if wsc is None else 3
+        dws = wgrad.NOT_QUEUED
+        if all(need[2:]):
+            dws = wgrad.join(("1x1", keys[0]), ((dh1, x2), (gs, h2), (gs, x2))[:nw], ((mid, cin, 1, 1), (cout, mid, 1, 1), (cout, cin, 1, 1))[:nw],
+                             (sc1, sc3, scs)[:nw], g.device, wgrad.flush_wgrad_1x1, force=len(maps) > 1)
+        if dws is wgrad.NOT_QUEUED:
+            dw3 = _view4(wgrad.wgrad_1x1(gs, h2, sc3, keys[2]), cout, mid) if need[4] else None
+            dw1 = _view4(wgrad.wgrad_1x1(dh1, x2, sc1, keys[0]), mid, cin) if need[2] else None
+            dws = (dw1, dw3, _view4(wgrad.wgrad_1x1(gs, x2, scs, keys[3]), cout, cin) if nw == 3 and need[5] else None)
+        elif dws is None:
+            dws = (None,) * nw
+        return (dx, None, dws[0], dw2, dws[1], *dws[2:nw])
 
 
-class _Conv3x3LevelsFn(ops.CountedFunction):
+class _Conv3x3LevelsFn(wgrad.CountedFunction):
     """L independent 3x3 convolutions (stride 1, padding 1, + bias, optional ReLU) of L maps as ONE launch each way (ops.conv3x3_multi:
     the FPN levels — the RPN head's shared convolution on p2..p6, the four FPN output convolutions).  args: L, flags (the `relu`
     argument of _Conv3x3Fn), then L inputs, L staged forward weights, L staged data-gradient weights, L bias values, L weight parameters,
@@ -608,7 +426,7 @@ class _Conv3x3LevelsFn(ops.CountedFunction):
         need = ctx.needs_input_grad
         for i, w in enumerate(ws):
             if need[2 + 4 * L + i]:
-                ops.count_use(id(w))
+                wgrad.count_use(id(w))
         return tuple(outs)
 
     @staticmethod
@@ -630,9 +448,9 @@ class _Conv3x3LevelsFn(ops.CountedFunction):
             n, H, W, _ = xs[i].shape
             cout = dzs[i].shape[3]
             if need[2 + 4 * L + i]:
-                dws[i] = _wgrad_3x3(xs[i], dzs[i], None, ctx.wkeys[i])
+                dws[i] = wgrad.wgrad_3x3(xs[i], dzs[i], None, ctx.wkeys[i])
             if need[2 + 5 * L + i]:
-                dbs[i] = _bias_grad(dzs[i].view(n * H * W, cout), cout, ctx.bkeys[i])
+                dbs[i] = wgrad.bias_grad(dzs[i].view(n * H * W, cout), cout, ctx.bkeys[i])
         probs = []
         for i in range(L):
             if need[2 + i]:

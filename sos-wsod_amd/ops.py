@@ -84,7 +84,6 @@ class KernelTimer:
 
 
 TIMER = None
-GRAD_SCOPE = None      # the active grad_scope (or None)
 
 
 _WORKER_STREAMS = {}
@@ -126,91 +125,6 @@ class capture_guard:
         if self._was:
             gc.enable()
         return False
-
-
-class grad_scope:
-    """Wrap the forward passes AND the one `backward()` call of an iteration whose graph uses parameters more than once (the Stage-3
-    student: two forward passes per iteration, unbias/ubteacher/engine/trainer.py:527-538; the RPN head's convolution on five FPN
-    levels in each).  Autograd would hand every use's weight gradient to the parameter's accumulator and add them with a torch
-    kernel.  Inside the scope
-      * the first weight-gradient node of a parameter registers the buffer it returns (`note_grad`) and every later node of the same
-        parameter ADDS to that buffer inside its own fold / GEMM epilogue (`pending_grad`) and returns no gradient;
-      * a forward pass counts the uses of a 3x3 weight (`count_use`); its weight-gradient nodes then only QUEUE their (x, dy)
-        pair and the last of them runs all pairs as one grouped launch + one fold (frcnn._wgrad_3x3).
-    The accumulator node of a parameter runs after all of its incoming edges (every use), on the same stream, so it sees the
-    finished sum; the data-parallel reducer's hooks hang on that node and are therefore not affected.  A counted use whose
-    backward node never runs would leave a queued gradient unfinished: __exit__ raises in that case (opt out: do not open a
-    scope).  Outside a scope every helper is inert: plain autograd behaviour."""
-
-    def __enter__(self):
-        global GRAD_SCOPE
-        self._prev, GRAD_SCOPE = GRAD_SCOPE, self
-        self.bufs, self.uses, self.queued = {}, {}, {}
-        return self
-
-    def finish(self):
-        """Call between `backward()` and `optimizer.step()`: every queued weight gradient must have been run by its last use.  A
-        counted use whose backward node never ran leaves the buffer autograd was handed unfinished (uninitialised memory): raise
-        BEFORE the optimizer applies it."""
-        left = [k for k, q in self.queued.items() if q["probs"]]
-        if left:
-            self.bufs, self.uses, self.queued = {}, {}, {}
-            raise RuntimeError(f"grad_scope: {len(left)} queued weight gradient(s) were never finished — a use counted in the forward pass "
-                               "did not take part in backward(); run this graph without ops.grad_scope")
-
-    def __exit__(self, exc_type, *exc):
-        global GRAD_SCOPE
-        GRAD_SCOPE = self._prev
-        left = [k for k, q in self.queued.items() if q["probs"]]
-        self.bufs, self.uses, self.queued = {}, {}, {}
-        if left and exc_type is None:
-            raise RuntimeError(f"grad_scope: {len(left)} queued weight gradient(s) were never finished — a use counted in the forward pass "
-                               "did not take part in backward(); run this graph without ops.grad_scope")
-        return False
-
-
-CALLER_GRAD_ENABLED = True      # grad mode of the code that called the running CountedFunction.apply (see there)
-
-
-class CountedFunction(torch.autograd.Function):
-    """torch.autograd.Function whose forward may call `count_use`.  Inside `forward` autograd has ALREADY switched grad mode off —
-    whether the caller ran under torch.no_grad() or not — and ctx.needs_input_grad stays True for a parameter that requires grad:
-    the only place that still sees the caller's mode is `apply` itself, so it is recorded there.  (Round 5 first tested
-    torch.is_grad_enabled() inside count_use: always False in a forward, so nothing was counted and every Stage-3 weight gradient
-    silently took the one-by-one path — 16.2 -> 17.3 ms; found in the kernel statistics, where the grouped launches had disappeared.)"""
-
-    @classmethod
-    def apply(cls, *args, **kwargs):
-        global CALLER_GRAD_ENABLED
-        prev, CALLER_GRAD_ENABLED = CALLER_GRAD_ENABLED, torch.is_grad_enabled()
-        try:
-            return super().apply(*args, **kwargs)
-        finally:
-            CALLER_GRAD_ENABLED = prev
-
-
-def count_use(key):
-    """forward side (inside a CountedFunction.forward): this pass will contribute one weight-gradient node for `key`.  A pass under
-    torch.no_grad() builds no node: not counted (a counted use that never reaches backward would leave a queued gradient unfinished)."""
-    if GRAD_SCOPE is not None and key is not None and CALLER_GRAD_ENABLED:
-        GRAD_SCOPE.uses[key] = GRAD_SCOPE.uses.get(key, 0) + 1
-
-
-def pending_grad(key, shape):
-    """the f32 buffer an earlier node of this backward pass registered for `key` (viewed as `shape`), or None"""
-    if GRAD_SCOPE is None or key is None:
-        return None
-    buf = GRAD_SCOPE.bufs.get(key)
-    if buf is None or buf.numel() != int(torch.Size(shape).numel()) or not buf.is_contiguous():
-        return None
-    return buf.view(shape)
-
-
-def note_grad(key, buf):
-    if GRAD_SCOPE is not None and key is not None:
-        # an ALIAS (its own tensor object on the same storage): autograd's accumulator adopts a gradient without copying it only
-        # when nobody else holds the tensor object it was handed (18 device-to-device copies per Stage-3 iteration otherwise)
-        GRAD_SCOPE.bufs[key] = buf.view(buf.shape)
 
 
 def grad_target(param, shape, dev):

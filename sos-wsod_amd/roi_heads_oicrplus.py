@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, staging
+from .backbone_vgg import _dtype_from_cfg
 from .box_head import DiscriminativeAdaptionNeck  # noqa: F401  (registers the box head the configs name)
 from .events import get_event_storage, has_event_storage
 from .fast_rcnn_oicr import OICROutputLayers
@@ -303,7 +304,6 @@ class OICRPlusHeads(nn.Module):
     # ------------------------------------------------------------------ construction from cfg
     @classmethod
     def from_config(cls, cfg, input_shape: Dict[str, ShapeSpec]):
-        from .backbone_vgg import _dtype_from_cfg
         dtype = _dtype_from_cfg(cfg)
         # keys the reference acts on that this path does not implement: refuse instead of training with other numerics
         assert not cfg.get("OICRPLUS", {}).get("BBOX_UPDATE", False), "OICRPLUS.BBOX_UPDATE True is not implemented"

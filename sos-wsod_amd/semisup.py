@@ -17,7 +17,7 @@ import weakref
 import copy
 import torch
 
-from . import ops, staging
+from . import ops, staging, wgrad
 from .structures import Boxes, Instances
 
 
@@ -267,7 +267,7 @@ class SemiSupStep:
                  bbox_threshold=0.7, unsup_loss_weight=4.0, burn_up_with_strong_aug=True, has_multi_label=False, fuse_grad_sums=True,
                  lockstep=True, overlap_teacher=None, speculate=True):
         self.model, self.model_teacher, self.optimizer = model, model_teacher, optimizer
-        self.fuse_grad_sums = fuse_grad_sums          # ops.grad_scope around backward (False: autograd sums the two passes' weight gradients)
+        self.fuse_grad_sums = fuse_grad_sums          # wgrad.grad_scope around backward (False: autograd sums the two passes' weight gradients)
         core = getattr(model, "module", model)                                 # (DistributedDataParallel wraps the student)
         self.lockstep = bool(lockstep) and hasattr(getattr(getattr(core, "backbone", None), "bottom_up", None), "forward_lockstep")
         self.burn_up_step, self.teacher_update_iter, self.ema_keep_rate = burn_up_step, teacher_update_iter, ema_keep_rate
@@ -329,8 +329,8 @@ class SemiSupStep:
     def _attempt(self, data):
         if self.fuse_grad_sums:
             # the student's two passes share every weight: inside the scope their gradients are summed in the kernels, and the uses of
-            # a 3x3 weight counted during the forward passes run as one grouped launch (ops.grad_scope)
-            with ops.grad_scope():
+            # a 3x3 weight counted during the forward passes run as one grouped launch (wgrad.grad_scope)
+            with wgrad.grad_scope():
                 return self._forward_backward(data)
         return self._forward_backward(data)
 
@@ -411,6 +411,5 @@ class SemiSupStep:
         if _fr.SPECULATE is not None:
             _fr.SPECULATE.seal()                      # the forward is queued: compare its counts beside the backward (frcnn.Speculation.seal)
         losses.backward()
-        if ops.GRAD_SCOPE is not None:
-            ops.GRAD_SCOPE.finish()                   # a queued weight gradient that never ran must not reach the optimizer
+        wgrad.finish()                                # a queued weight gradient that never ran must not reach the optimizer
         return record, loss_dict

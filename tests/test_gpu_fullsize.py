@@ -531,7 +531,7 @@ def test_config4_bf16_conv5_forward_dgrad_wgrad_at_99x165_against_float64():
     (32 670 pixels for the weights) and one bf16 rounding of a bf16 output."""
     import torch.nn.functional as F
     import sos_wsod_amd.ops as ops
-    from sos_wsod_amd.backbone_vgg import _wgrad_direct_splits
+    from sos_wsod_amd.wgrad import wgrad_direct_splits
     dev = torch.device("cuda", 0)
     bf = torch.bfloat16
     n, H, W, C, dil = 2, 99, 165, 512, 2
@@ -566,7 +566,7 @@ def test_config4_bf16_conv5_forward_dgrad_wgrad_at_99x165_against_float64():
     rel_d = float((gotd - refd).norm() / refd.norm())
     assert rel_d <= 3e-3, rel_d
     # ---- weight gradient: the grouped entry (direct kernel) with the backbone's split plan + the ordered fold, f32 out
-    ns = _wgrad_direct_splits([(n, H, W, C, C, dil)])[0]
+    ns = wgrad_direct_splits([(n, H, W, C, C, dil)])[0]
     nslab = ops.conv3x3_wgrad_nslab(xg, C, ns)
     slabs = torch.empty(nslab, C * 9 * C, device=dev)
     ops.conv3x3_wgrad_grouped([(xg, dyg, slabs, dil, ns)])

@@ -860,7 +860,7 @@ def test_semisup_step_against_the_reference_run_of_its_own_trainer_methods(golde
 
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
 def test_weight_gradients_summed_in_the_kernels_equal_autograd_sums(mode):
-    """ops.grad_scope: in a semi-supervised iteration every student weight is used by two forward passes (and the RPN head's 3x3
+    """wgrad.grad_scope: in a semi-supervised iteration every student weight is used by two forward passes (and the RPN head's 3x3
     convolution by five levels in each); inside the scope the second and later weight-gradient kernels of a parameter add to the
     first one's buffer (split-K fold / GEMM epilogue with the buffer as its own residual) and autograd's accumulator receives ONE
     gradient.  Same f32 additions as autograd's own sums: every gradient within 1e-5 (fp32; see the note at the comparison)."""
@@ -904,7 +904,7 @@ def test_weight_gradients_summed_in_the_kernels_equal_autograd_sums(mode):
         assert "loss_cls_pseudo" in record
         grads[fuse] = {n: p.grad.detach().clone() for n, p in student.named_parameters() if p.grad is not None}
     ops.conv3x3_wgrad_grouped, ops.gemm_kk_grouped = real3, real1
-    # the uses were counted (ops.CountedFunction) and the last use of a weight ran all pairs as ONE grouped launch: >= one launch per
+    # the uses were counted (wgrad.CountedFunction) and the last use of a weight ran all pairs as ONE grouped launch: >= one launch per
     # 3x3 weight with several uses (13 bottleneck conv2 + the RPN head + 4 FPN outputs) and per bottleneck block's 1x1 weights
     assert calls[True][0] >= 10 and calls[True][1] >= 10, calls
     assert set(grads[True]) == set(grads[False]) and len(grads[True]) > 60

@@ -19,11 +19,11 @@ elif which.startswith("wgrad") and which != "wgrad_grouped":
     x = rnd(n_, H_, W_, cin); dy = rnd(n_, H_, W_, cout); dw = torch.empty(cout, cin, 3, 3, device=dev); ws = torch.empty(cout * 9 * cin, device=dev)
     f = lambda: ops.conv3x3_wgrad(x, dy, dw, dil, splitk=sk, workspace=ws)
 elif which == "wgrad_grouped":          # every conv weight gradient of one backward pass (9 layers x 2 view batches), one launch
-    from sos_wsod_amd.backbone_vgg import _wgrad_direct_splits
+    from sos_wsod_amd.wgrad import wgrad_direct_splits
     L = [(128, 128, 128, 256, 1), (128, 128, 256, 256, 1), (128, 128, 256, 256, 1), (64, 64, 256, 512, 1), (64, 64, 512, 512, 1),
          (64, 64, 512, 512, 1), (63, 63, 512, 512, 2), (63, 63, 512, 512, 2), (63, 63, 512, 512, 2)]
     # the direct kernel's own split plan (what the backbone passes)
-    plan = iter(_wgrad_direct_splits([(2, H, W, ci, co, dil) for H, W, ci, co, dil in L for _v in range(2)]))
+    plan = iter(wgrad_direct_splits([(2, H, W, ci, co, dil) for H, W, ci, co, dil in L for _v in range(2)]))
     probs = []
     for H, W, ci, co, dil in L:
         for _v in range(2):

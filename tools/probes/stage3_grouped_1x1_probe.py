@@ -3,7 +3,7 @@ pass (K-split + fold each) against ONE sw_gemm_kk_grouped launch over all of the
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import sos_wsod_amd.ops as ops
-from sos_wsod_amd.backbone_vgg import _wgrad_grouped_target, _wgrad_grouped_splits
+from sos_wsod_amd.wgrad import wgrad_grouped_target, wgrad_grouped_splits
 dt, dev = torch.bfloat16, "cuda"
 def t(fn, n=20):
     for _ in range(3): fn()
@@ -32,10 +32,10 @@ for name, P1, cin, mid, cout, sc in [("res3.0", 15200, 256, 128, 512, True), ("r
     res = []
     for T in (0, 4, 8, 16, 32):
         shapes = [(a.shape[0], a.shape[1], b.shape[1]) for use in uses for a, b in use]
-        target = _wgrad_grouped_target(shapes, 64, candidates=CAND) if T == 0 else T
+        target = wgrad_grouped_target(shapes, 64, candidates=CAND) if T == 0 else T
         probs, folds = [], []
         for w in range(nw):
-            ns = [_wgrad_grouped_splits(use[w][0].shape[0], 64, target) for use in uses]
+            ns = [wgrad_grouped_splits(use[w][0].shape[0], 64, target) for use in uses]
             nsl = [ops.gemm_kk_nslab(dt, use[w][0].shape[0], s) for use, s in zip(uses, ns)]
             M, N = uses[0][w][0].shape[1], uses[0][w][1].shape[1]
             ws = torch.empty(sum(nsl), M * N, device=dev)

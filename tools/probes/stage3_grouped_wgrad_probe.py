@@ -4,7 +4,7 @@ batch 2 and batch 1), an FPN output convolution (2 uses), res4 / res5 conv2 (2 u
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import sos_wsod_amd.ops as ops
-from sos_wsod_amd.backbone_vgg import _wgrad_grouped_target, _wgrad_grouped_splits
+from sos_wsod_amd.wgrad import wgrad_grouped_target, wgrad_grouped_splits
 dt, dev = torch.bfloat16, "cuda"
 def t(fn, n=20):
     for _ in range(3): fn()
@@ -28,8 +28,8 @@ for name, probs in sets.items():
     res = []
     for T in (0, 16, 24, 32, 48, 64, 96):
         shapes = [(x.shape[0] * x.shape[1] * x.shape[2], C, 9 * C) for x, _ in xs]
-        target = _wgrad_grouped_target(shapes, 64) if T == 0 else T
-        splits = [_wgrad_grouped_splits(s[0], 64, target) for s in shapes]
+        target = wgrad_grouped_target(shapes, 64) if T == 0 else T
+        splits = [wgrad_grouped_splits(s[0], 64, target) for s in shapes]
         nsl = [ops.conv3x3_wgrad_nslab(x, C, sp) for (x, _), sp in zip(xs, splits)]
         ws = torch.empty(sum(nsl), C * 9 * C, device=dev)
         offs = [sum(nsl[:i]) for i in range(len(nsl))]

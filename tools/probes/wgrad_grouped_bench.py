@@ -3,7 +3,7 @@
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import sos_wsod_amd.ops as ops
-from sos_wsod_amd.backbone_vgg import _wgrad_grouped_splits
+from sos_wsod_amd.wgrad import wgrad_grouped_splits
 dt, dev = torch.bfloat16, "cuda"
 LAYERS = [("conv3_1", 128, 128, 128, 256, 1), ("conv3_2", 128, 128, 256, 256, 1), ("conv3_3", 128, 128, 256, 256, 1),
           ("conv4_1", 64, 64, 256, 512, 1), ("conv4_2", 64, 64, 512, 512, 1), ("conv4_3", 64, 64, 512, 512, 1),
@@ -36,7 +36,7 @@ for T in [int(v) for v in os.environ.get("TS", "32,48,64,96,128").split(",")]:
         probs, folds = [], []
         for i in range(0, len(data), 2):
             cout, cin = data[i][2].shape[3], data[i][1].shape[3]
-            ns = [_wgrad_grouped_splits(d[1].shape[0] * d[1].shape[1] * d[1].shape[2], 64, T) for d in data[i:i + 2]]
+            ns = [wgrad_grouped_splits(d[1].shape[0] * d[1].shape[1] * d[1].shape[2], 64, T) for d in data[i:i + 2]]
             nsl = [ops.conv3x3_wgrad_nslab(d[1], cout, s) for d, s in zip(data[i:i + 2], ns)]
             ws = torch.empty(sum(nsl), cout * 9 * cin, device=dev)
             off = 0

@@ -4,7 +4,7 @@ TS=... lists K-tile targets per item (default: the backbone's own split plan).""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import sos_wsod_amd.ops as ops
-from sos_wsod_amd.backbone_vgg import _wgrad_grouped_splits, _wgrad_direct_splits
+from sos_wsod_amd.wgrad import wgrad_grouped_splits, wgrad_direct_splits
 dt, dev = torch.bfloat16, "cuda"
 
 
@@ -30,14 +30,14 @@ for name, views in [("headline", [(512, 512), (512, 512)]), ("recipe", [(832, 11
             h, w, cin, cout, dil = layers[v][li]
             data.append(((torch.randn(2, h, w, cin, device=dev) * .5).to(dt), (torch.randn(2, h, w, cout, device=dev) * .5).to(dt), dil))
     flops = sum(2.0 * x.numel() * 9 * dy.shape[3] for x, dy, _ in data)
-    # 0: the direct kernel's own split plan (backbone_vgg._wgrad_direct_splits)
+    # 0: the direct kernel's own split plan (wgrad.wgrad_direct_splits)
     targets = [int(v) for v in os.environ["TS"].split(",")] if "TS" in os.environ else [0]
-    plan = _wgrad_direct_splits([(x.shape[0], x.shape[1], x.shape[2], x.shape[3], dy.shape[3], dil) for x, dy, dil in data])
+    plan = wgrad_direct_splits([(x.shape[0], x.shape[1], x.shape[2], x.shape[3], dy.shape[3], dil) for x, dy, dil in data])
     for T in targets:
         probs, folds, nslabs = [], [], 0
         for i in range(0, len(data), 2):
             cout, cin = data[i][1].shape[3], data[i][0].shape[3]
-            ns = [_wgrad_grouped_splits(d[0].shape[0] * d[0].shape[1] * d[0].shape[2], 64, T) for d in data[i:i + 2]] if T else plan[i:i + 2]
+            ns = [wgrad_grouped_splits(d[0].shape[0] * d[0].shape[1] * d[0].shape[2], 64, T) for d in data[i:i + 2]] if T else plan[i:i + 2]
             nsl = [ops.conv3x3_wgrad_nslab(d[0], cout, s) for d, s in zip(data[i:i + 2], ns)]
             ws = torch.empty(sum(nsl), cout * 9 * cin, device=dev); off = 0
             for d, s, k in zip(data[i:i + 2], ns, nsl):
