@@ -508,6 +508,21 @@ int sw_maxpool3x3s2(int dtype, int N, int H, int W, int C, const void* in, void*
  * sw_scatter2x is its backward: out [N][H][W][C] = g at the even pixels, 0 elsewhere (fully written). */
 int sw_subsample2x(int dtype, int N, int H, int W, int C, const void* in, void* out, sw_stream_t stream);
 int sw_scatter2x(int dtype, int N, int H, int W, int C, const void* g, void* out, sw_stream_t stream);
+/* A 3x3 convolution (padding 1, stride 1 or 2) as sw_gemm over an explicit column matrix (csrc/conv_col.hip): the stride-2 conv2 of a
+ * torchvision-style bottleneck (detectron2/modeling/backbone/resnet.py:146-166, the `stride_in_1x1 = False` branch: conv1 keeps the
+ * resolution, the 3x3 conv2 carries the stride) and the 3x3 convolutions of FastRCNNConvFCHead on the (R, 7, 7, C) ROI maps
+ * (detectron2/modeling/roi_heads/box_head.py:25-92, the conv part).  in [nimg][H][W][C]; Ho = (H - 1) / stride + 1, Wo likewise;
+ *   col[(n * Ho + oy) * Wo + ox][(3 * ky + kx) * C + c] = in[n][stride * oy + ky - 1][stride * ox + kx - 1][c], 0 outside the map
+ * with row pitch ldcol: the [tap][ci] order of the staged [co][tap][ci] weight (sw_stage_weights_multi kind 1), which is therefore
+ * the (Cout, 9 C) B operand of sw_gemm as it stands.  All 9 C columns of every row are written, columns beyond are not touched;
+ * values are copied as bits.  sw_col2im3x3 is the adjoint in gather form: dx[n][iy][ix][c] = the sum, in ascending tap order in f32,
+ * of the cells of dcol that sw_im2col3x3 fills from that element (at most 9, stride 2: at most 4), set to 0 where relu_ref
+ * [nimg][H][W][C] (same dtype; may be NULL) is not > 0 (sw_relu_bwd's rule), rounded once; every element of dx is written, no
+ * atomics (two runs are bit-identical).  Contract: C % 8 == 0, ldcol >= 9 C, ldcol % 8 == 0 (else -5), stride 1 or 2 (else -3),
+ * 16-byte aligned pointers (else -4), fewer than 2^31 elements in col (else -6). */
+int sw_im2col3x3(int dtype, int nimg, int H, int W, int C, int stride, const void* in, void* col, long ldcol, sw_stream_t stream);
+int sw_col2im3x3(int dtype, int nimg, int H, int W, int C, int stride, const void* dcol, long ldcol, const void* relu_ref, void* dx,
+                 sw_stream_t stream);
 /* out = a + b, with ReLU when relu != 0 (the residual join of a bottleneck block, resnet.py:209-211) */
 int sw_add_relu(int dtype, long n, const void* a, const void* b, void* out, int relu, sw_stream_t stream);
 /* FPN top-down pathway (fpn.py:142-144): out [N][2h][2w][C] = lateral + nearest-neighbour 2x upsampling of top [N][h][w][C];

@@ -98,6 +98,10 @@ def get_cfg() -> CfgNode:
         DEVICE="cuda", META_ARCHITECTURE="GeneralizedRCNN", WEIGHTS="", LOAD_PROPOSALS=False, MASK_ON=False, KEYPOINT_ON=False,
         PIXEL_MEAN=[103.530, 116.280, 123.675], PIXEL_STD=[1.0, 1.0, 1.0],
         BACKBONE=dict(NAME="build_resnet_backbone", FREEZE_AT=2),
+        RESNETS=dict(DEPTH=50, OUT_FEATURES=["res4"], NUM_GROUPS=1, NORM="FrozenBN", WIDTH_PER_GROUP=64, STRIDE_IN_1X1=True,
+                     RES5_DILATION=1, RES2_OUT_CHANNELS=256, STEM_OUT_CHANNELS=64, DEFORM_ON_PER_STAGE=[False, False, False, False],
+                     DEFORM_MODULATED=False, DEFORM_NUM_GROUPS=1),
+        FPN=dict(IN_FEATURES=[], OUT_CHANNELS=256, NORM="", FUSE_TYPE="sum"),
         PROPOSAL_GENERATOR=dict(NAME="RPN", MIN_SIZE=0),
         ROI_HEADS=dict(NAME="Res5ROIHeads", NUM_CLASSES=80, IN_FEATURES=["res4"], IOU_THRESHOLDS=[0.5], IOU_LABELS=[0, 1],
                        BATCH_SIZE_PER_IMAGE=512, POSITIVE_FRACTION=0.25, SCORE_THRESH_TEST=0.05, NMS_THRESH_TEST=0.5,

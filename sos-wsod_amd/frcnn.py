@@ -9,7 +9,8 @@ roi_heads.box_head.fc1, roi_heads.box_predictor.{cls_score,bbox_pred}), same bra
 (`forward(batched_inputs, branch=...)`), so semisup.SemiSupStep drives it like the reference's trainer drives its model.
 
 Execution plan (MI355X-first): NHWC activations end to end; a 1x1 convolution is sw_gemm over the pixels (stride 2 = a pixel
-subsample in front, STRIDE_IN_1X1), a 3x3 convolution the implicit-GEMM / direct MFMA kernel with bias + ReLU fused, FrozenBN is
+subsample in front, STRIDE_IN_1X1), a 3x3 convolution the implicit-GEMM / direct MFMA kernel with bias + ReLU fused (stride 2 and
+the box head's convolutions on ROI maps, the SoS-WSOD+ forms: sw_im2col3x3 + sw_gemm, _Conv3x3ColFn), FrozenBN is
 folded into the weight and bias; the frozen stem + res2 run without autograd; ROIAlign, the FPN joins, the RPN losses, the focal
 / L1 losses, box decoding and NMS are kernels of csrc/detector.hip / heads.hip.  Every dense layer is a torch.autograd.Function
 around those kernels with an explicit backward; autograd only links the nodes.  The index side — per-level top-k of the RPN,
@@ -240,6 +241,96 @@ class _Conv3x3Fn(wgrad.CountedFunction):
         if ctx.needs_input_grad[0]:
             dx = torch.empty(n, H, W, cin, device=g.device, dtype=cd)
             ops.conv3x3(dz, wkd, dx, 1, ops.make_epilogue(out_dtype=cd))
+        return dx, None, None, None, None, None, dw, db
+
+
+COL_CHUNK_BYTES = 256 << 20     # _Conv3x3ColFn: images (ROIs) per pass so that one column matrix stays at or below this
+
+
+class _Conv3x3ColFn(wgrad.CountedFunction):
+    """3x3, padding 1, stride 1 or 2 on NHWC through an explicit column matrix: sw_im2col3x3, then sw_gemm on the staged
+    [co][tap][ci] weight viewed as (cout, 9 cin) with bias (FrozenBN shift) + ReLU in its epilogue.  For the layers the direct /
+    implicit-GEMM kernels do not take: the stride-2 conv2 of a torchvision-style bottleneck (a quarter of the stride-1 FLOP, no
+    subsample) and the box head's convolutions on (R, 7, 7, C) ROI maps.  Backward: data gradient = GEMM gs W into dcol, then
+    sw_col2im3x3 (gather, no atomics; masks by the input when `_MASK_INPUT_GRAD`); weight gradient = the (1,1)-form GEMM gs^T col into
+    one f32 [co][tap][ci] slab per pass, folded to OIHW x FrozenBN scale by sw_conv3x3_wgrad_fold (deterministic); the column matrix
+    is rebuilt in the backward (a data-movement pass) instead of kept.  The images are walked in passes of COL_CHUNK_BYTES of columns.
+    Inside wgrad.grad_scope a second use of the weight adds to the first use's buffer in the fold (pending_grad), like wgrad_3x3."""
+
+    @staticmethod
+    def _chunks(n, rows_per_img, cin, es):
+        per = max(1, COL_CHUNK_BYTES // max(1, rows_per_img * 9 * cin * es))
+        return [(i, min(n, i + per)) for i in range(0, n, per)]
+
+    @staticmethod
+    def forward(ctx, x, staged, bias, scale, relu, stride, w, b):
+        n, H, W, cin = x.shape
+        cout = w.shape[0]
+        cd = x.dtype
+        flags = int(relu)
+        relu = bool(flags & _RELU)
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        x = x.contiguous()
+        out = torch.empty(n, Ho, Wo, cout, device=x.device, dtype=cd)
+        w2 = staged.view(cout, 9 * cin)
+        ep = ops.make_epilogue(bias=bias, relu=relu, out_dtype=cd)
+        col = None
+        for i0, i1 in _Conv3x3ColFn._chunks(n, Ho * Wo, cin, x.element_size()):
+            rows = (i1 - i0) * Ho * Wo
+            if col is None or col.shape[0] != rows:
+                col = torch.empty(rows, 9 * cin, device=x.device, dtype=cd)
+            ops.im2col3x3(x[i0:i1], col, stride)
+            ops.gemm(col, w2, out[i0:i1].view(rows, cout), rows, cout, 9 * cin, ep=ep)
+        ctx.save_for_backward(x, staged, out if relu else None, scale)
+        ctx.relu, ctx.stride, ctx.cout = relu, stride, cout
+        ctx.mask_in, ctx.premasked = bool(flags & _MASK_INPUT_GRAD), bool(flags & _GRAD_PREMASKED)
+        ctx.wkey, ctx.bkey = id(w), (None if b is None else id(b))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, staged, out, scale = ctx.saved_tensors
+        n, H, W, cin = x.shape
+        cout, stride, cd = ctx.cout, ctx.stride, x.dtype
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        g = g.contiguous()
+        if g.dtype != cd:
+            g = g.to(cd)
+        gs = ops.relu_bwd(out, g, out=torch.empty_like(g)) if (ctx.relu and not ctx.premasked and n > 0) else g
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[6], ctx.needs_input_grad[7]
+        w2 = staged.view(cout, 9 * cin)
+        dx = torch.empty_like(x) if need_x else None
+        chunks = _Conv3x3ColFn._chunks(n, Ho * Wo, cin, x.element_size())
+        slabs = torch.empty(max(1, len(chunks)), cout * 9 * cin, device=x.device, dtype=torch.float32) if need_w else None
+        col = None
+        for c, (i0, i1) in enumerate(chunks):
+            rows = (i1 - i0) * Ho * Wo
+            g2 = gs[i0:i1].view(rows, cout)
+            if col is None or col.shape[0] != rows:
+                col = torch.empty(rows, 9 * cin, device=x.device, dtype=cd)
+            if need_w:
+                ops.im2col3x3(x[i0:i1], col, stride)
+                tiles = ((cout + 127) // 128) * ((9 * cin + 127) // 128)
+                ops.gemm(g2, col, slabs[c].view(cout, 9 * cin), cout, 9 * cin, rows, a_kstrided=True, b_kstrided=True,
+                         splitk=max(1, min(32, 512 // tiles, rows // 1024)))
+            if need_x:
+                ops.gemm(g2, w2, col, rows, 9 * cin, cout, b_kstrided=True, ep=ops.make_epilogue(out_dtype=cd))
+                ops.col2im3x3(col, dx[i0:i1], stride, relu_ref=x[i0:i1] if ctx.mask_in else None)
+        dw = db = None
+        if need_w:
+            prev = wgrad.pending_grad(ctx.wkey, (cout, cin, 3, 3))
+            dw = prev if prev is not None else torch.empty(cout, cin, 3, 3, device=x.device, dtype=torch.float32)
+            if chunks:
+                ops.conv3x3_wgrad_fold(slabs, len(chunks), dw, cout_scale=scale, accumulate=prev is not None)
+            elif prev is None:
+                dw.zero_()
+            if prev is not None:
+                dw = None
+            else:
+                wgrad.note_grad(ctx.wkey, dw)
+                dw = dw.view(cout, cin, 3, 3)
+        if need_b:
+            db = wgrad.bias_grad(gs.view(n * Ho * Wo, cout), cout, ctx.bkey)
         return dx, None, None, None, None, None, dw, db
 
 
@@ -641,12 +732,15 @@ class ConvBN(nn.Module):
     """Conv2d(bias=False, norm=FrozenBN) of the reference: parameter `weight` (OIHW) + submodule `norm`.  The FrozenBN fold lives in
     the staged weight (W * scale) and the epilogue bias (shift); d/dweight = scale * d/dW_eff in the layer's backward."""
 
-    def __init__(self, cin, cout, k, stride=1):
+    def __init__(self, cin, cout, k, stride=1, col=False):
         super().__init__()
         self.weight = nn.Parameter(torch.empty(cout, cin, k, k))
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
         self.norm = FrozenBatchNorm2d(cout)
         self.k, self.stride = k, stride
+        # a 3x3 convolution through the column matrix (_Conv3x3ColFn): every stride-2 one, and stride-1 ones on request (ROI maps)
+        self.col = k == 3 and (col or stride == 2)
+        assert k == 3 or not col
 
     def _stage_entries(self, cd):
         if self.k == 7:
@@ -659,7 +753,7 @@ class ConvBN(nn.Module):
         if self.k == 3:
             st.w = torch.empty(cout, 9, cin, device=dev, dtype=cd)
             ent = [dict(kind=1, w=self.weight, dst=st.w, bn=bn, scale=st.scale, shift=st.shift)]
-            if self.weight.requires_grad:
+            if self.weight.requires_grad and not self.col:           # (the column form's data gradient reads st.w itself)
                 st.wd = torch.empty(cin, 9, cout, device=dev, dtype=cd)
                 ent.append(dict(kind=2, w=self.weight, dst=st.wd, bn=bn))
         else:
@@ -672,6 +766,8 @@ class ConvBN(nn.Module):
         st = _staged_of(self)
         if self.k == 3:
             assert residual is None
+            if self.col:
+                return _Conv3x3ColFn.apply(x, st.w, st.shift, st.scale, relu, self.stride, self.weight, None)
             return _Conv3x3Fn.apply(x, st.w, st.wd, st.shift, st.scale, relu, self.weight, None)
         if self.stride == 2:
             x = _Subsample2Fn.apply(x)
@@ -685,11 +781,11 @@ class ConvBN(nn.Module):
 class Conv(nn.Module):
     """plain Conv2d with bias (FPN laterals / outputs, RPN head).  packed=True: staged by the owner as part of a packed GEMM."""
 
-    def __init__(self, cin, cout, k, packed=False):
+    def __init__(self, cin, cout, k, packed=False, col=False):
         super().__init__()
         self.weight = nn.Parameter(torch.empty(cout, cin, k, k)); self.bias = nn.Parameter(torch.zeros(cout))
         nn.init.kaiming_uniform_(self.weight, a=1)
-        self.k, self.packed = k, packed
+        self.k, self.packed, self.col = k, packed, bool(col) and k == 3          # col: through _Conv3x3ColFn (ROI maps)
 
     def _stage_entries(self, cd):
         if self.packed:
@@ -697,7 +793,10 @@ class Conv(nn.Module):
         cout, cin = self.weight.shape[:2]
         dev = self.weight.device
         st = _Staged()
-        if self.k == 3:
+        if self.k == 3 and self.col:
+            st.w = torch.empty(cout, 9, cin, device=dev, dtype=cd)
+            ent = [dict(kind=1, w=self.weight, dst=st.w)]
+        elif self.k == 3:
             st.w = torch.empty(cout, 9, cin, device=dev, dtype=cd); st.wd = torch.empty(cin, 9, cout, device=dev, dtype=cd)
             ent = [dict(kind=1, w=self.weight, dst=st.w), dict(kind=2, w=self.weight, dst=st.wd)]
         else:
@@ -709,6 +808,8 @@ class Conv(nn.Module):
     def forward(self, x, relu=False):
         """relu: False / True or layer flags (_RELU | _GRAD_PREMASKED ...)"""
         st = _staged_of(self)
+        if self.k == 3 and self.col:
+            return _Conv3x3ColFn.apply(x, st.w, self.bias.detach(), None, relu, 1, self.weight, self.bias)
         if self.k == 3:
             return _Conv3x3Fn.apply(x, st.w, st.wd, self.bias.detach(), None, relu, self.weight, self.bias)
         n, H, W, C = x.shape
@@ -732,17 +833,28 @@ def _packed_linear_entries(weights, biases, cd):
 
 
 class BottleneckBlock(nn.Module):
-    """backbone/resnet.py:100-213 with STRIDE_IN_1X1 (the stride sits in conv1 and in the shortcut)"""
+    """backbone/resnet.py:100-213.  stride_in_1x1 (RESNETS.STRIDE_IN_1X1, the MSRA form): the stride sits in conv1 and in the shortcut;
+    False (the torchvision form): conv1 runs at full resolution and the 3x3 conv2 carries the stride (resnet.py:146-166) — a
+    stride-2 block of that form runs layer by layer, its conv2 through _Conv3x3ColFn; with stride 1 the two forms are one."""
 
-    def __init__(self, cin, cout, mid, stride):
+    def __init__(self, cin, cout, mid, stride, stride_in_1x1=True):
         super().__init__()
+        self.stride_in_3x3 = stride == 2 and not stride_in_1x1
+        s1, s3 = (1, stride) if self.stride_in_3x3 else (stride, 1)
         self.shortcut = ConvBN(cin, cout, 1, stride) if cin != cout else None
-        self.conv1 = ConvBN(cin, mid, 1, stride); self.conv2 = ConvBN(mid, mid, 3); self.conv3 = ConvBN(mid, cout, 1)
+        self.conv1 = ConvBN(cin, mid, 1, s1); self.conv2 = ConvBN(mid, mid, 3, s3); self.conv3 = ConvBN(mid, cout, 1)
         # set by the owner of a chain of blocks (ResNet): this block's input is the previous block's output and nobody else reads it /
         # this block's output is read by the next block only (see _MASK_INPUT_GRAD / _GRAD_PREMASKED; fused form only)
         self.mask_input_grad = self.grad_premasked = False
 
     def forward(self, x):
+        if self.stride_in_3x3:
+            # conv1's and conv2's ReLU outputs have one reader each (conv2 / conv3): that reader's data gradient leaves masked
+            # (col2im / the GEMM epilogue), the producer skips its relu_bwd; the block output's mask follows the chain's flag
+            sc = self.shortcut(x, False)
+            h = self.conv1(x.contiguous(), _RELU | _GRAD_PREMASKED)
+            h = self.conv2(h, _RELU | _MASK_INPUT_GRAD | _GRAD_PREMASKED)
+            return self.conv3(h, _RELU | _MASK_INPUT_GRAD | (_GRAD_PREMASKED if self.grad_premasked else 0), residual=sc.contiguous())
         if FUSED_BLOCKS:
             ws = (self.conv1.weight, self.conv2.weight, self.conv3.weight) + (() if self.shortcut is None else (self.shortcut.weight,))
             return _BottleneckFn.apply(x.contiguous(), self, *ws)
@@ -773,13 +885,14 @@ class BasicStem(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, freeze_at=2):
+    def __init__(self, freeze_at=2, stride_in_1x1=True):
         super().__init__()
+        self.stride_in_1x1 = bool(stride_in_1x1)
         self.stem = BasicStem()
         cin = 64
         self.stage_names = []
         for name, nblk, mid, cout, stride in R50_STAGES:
-            blocks = [BottleneckBlock(cin if b == 0 else cout, cout, mid, stride if b == 0 else 1) for b in range(nblk)]
+            blocks = [BottleneckBlock(cin if b == 0 else cout, cout, mid, stride if b == 0 else 1, stride_in_1x1) for b in range(nblk)]
             for b, blk in enumerate(blocks):         # inside a stage block b's output feeds block b + 1 and nothing else (the LAST
                 blk.mask_input_grad = b > 0          # block's is the stage output: the next stage and an FPN lateral read it)
                 blk.grad_premasked = b < nblk - 1
@@ -813,8 +926,9 @@ class ResNet(nn.Module):
         every batch, the batches' rows sit back to back in one matrix, every 1x1 convolution of res2..res5 is ONE GEMM over all rows
         and every 3x3 convolution one multi-problem launch over the batches' maps (_BottleneckFn with several maps).
         Rows are independent in every layer, so each image's features are what forward() gives for its own batch.
-        -> one feature dict per batch.  Needs the fused block form and freeze_at == 2; anything else runs the batches one by one."""
-        if not (FUSED_BLOCKS and self.freeze_at == 2 and len(x4s) > 1):
+        -> one feature dict per batch.  Needs the fused block form (so STRIDE_IN_1X1) and freeze_at == 2; anything else runs the
+        batches one by one."""
+        if not (FUSED_BLOCKS and self.stride_in_1x1 and self.freeze_at == 2 and len(x4s) > 1):
             return [self.forward(x) for x in x4s]
         feats = [{} for _ in x4s]
         # the stems' max-pools write their outputs back to back into ONE matrix: from there on — res2 included (round 5; it ran per batch
@@ -840,11 +954,16 @@ class FPN(nn.Module):
     """backbone/fpn.py:18-188: laterals 1x1, top-down nearest upsampling + add, outputs 3x3, p6 = p5 subsampled (LastLevelMaxPool)"""
     size_divisibility = 32
 
-    def __init__(self, bottom_up):
+    def __init__(self, bottom_up, norm=""):
+        """norm (FPN.NORM): "" = convolutions with bias; "FrozenBN" = bias-free convolutions followed by a FrozenBN (fpn.py:69-91)"""
         super().__init__()
-        self.bottom_up = bottom_up
+        assert norm in ("", "FrozenBN"), f"MODEL.FPN.NORM = {norm!r} is not implemented by this detector (implemented: '', 'FrozenBN')"
+        self.bottom_up, self.norm = bottom_up, norm
         for s, c in zip(FPN_STAGES, (256, 512, 1024, 2048)):
-            self.add_module(f"fpn_lateral{s}", Conv(c, 256, 1)); self.add_module(f"fpn_output{s}", Conv(256, 256, 3))
+            if norm:
+                self.add_module(f"fpn_lateral{s}", ConvBN(c, 256, 1)); self.add_module(f"fpn_output{s}", ConvBN(256, 256, 3))
+            else:
+                self.add_module(f"fpn_lateral{s}", Conv(c, 256, 1)); self.add_module(f"fpn_output{s}", Conv(256, 256, 3))
 
     def forward(self, x4):
         return self.forward_top(self.bottom_up(x4))
@@ -853,11 +972,14 @@ class FPN(nn.Module):
         """the pyramid from the bottom-up features {res2..res5}"""
         prevs, prev = [], None
         for s in reversed(FPN_STAGES):
-            lat = getattr(self, f"fpn_lateral{s}")(c[f"res{s}"])
+            lat = getattr(self, f"fpn_lateral{s}")(c[f"res{s}"], False)
             prev = lat if prev is None else _UpsampleAddFn.apply(lat, prev)
             prevs.insert(0, prev)
         # the four output convolutions are independent once the top-down sums exist: one launch (each way)
-        outs = list(_conv3x3_levels([getattr(self, f"fpn_output{s}") for s in FPN_STAGES], [p.contiguous() for p in prevs]))
+        if self.norm:                   # (FrozenBN: the weight gradients carry the fold's scale — level by level through _Conv3x3Fn)
+            outs = [getattr(self, f"fpn_output{s}")(p.contiguous(), False) for s, p in zip(FPN_STAGES, prevs)]
+        else:
+            outs = list(_conv3x3_levels([getattr(self, f"fpn_output{s}") for s in FPN_STAGES], [p.contiguous() for p in prevs]))
         outs.append(_Subsample2Fn.apply(outs[-1]))
         return outs                                                  # [p2, p3, p4, p5, p6] NHWC
 
@@ -1181,16 +1303,37 @@ class PseudoLabRPN(nn.Module):
 
 
 class FastRCNNConvFCHead(nn.Module):
-    def __init__(self, d_in=256 * 7 * 7, fc_dim=1024):
+    """detectron2/modeling/roi_heads/box_head.py:25-117: `conv_dims` 3x3 convolutions (+ conv_norm "" / "FrozenBN", ReLU) on the
+    (R, C, 7, 7) ROI maps, flatten, then `fc_dims` linear layers + ReLU (ROI_BOX_HEAD.NUM_CONV / CONV_DIM / NUM_FC / FC_DIM / NORM).
+    The defaults are the 2-fc head of Base-RCNN-FPN.yaml; SoS-WSOD+ (sos_plus_test.yaml) runs 4 conv + 1 fc with FrozenBN.  The
+    convolutions run on NHWC (R, 7, 7, C) maps through _Conv3x3ColFn (which walks the ROIs in passes of COL_CHUNK_BYTES of columns);
+    the pooler's rows and fc1's weight stay in the reference's (C, 7, 7) order, so the rows are re-laid on the way in and out."""
+
+    def __init__(self, conv_dims=(), fc_dims=(1024, 1024), conv_norm="", in_channels=256, resolution=7):
         super().__init__()
-        self.fc1 = nn.Linear(d_in, fc_dim); self.fc2 = nn.Linear(fc_dim, fc_dim)
-        for m in (self.fc1, self.fc2):
+        assert conv_norm in ("", "FrozenBN"), \
+            f"MODEL.ROI_BOX_HEAD.NORM = {conv_norm!r} is not implemented by this detector (implemented: '', 'FrozenBN')"
+        assert len(conv_dims) + len(fc_dims) > 0 and all(c % 8 == 0 for c in tuple(conv_dims) + (in_channels,))
+        self.resolution, self.in_channels = resolution, in_channels
+        self.convs, self.fcs = [], []
+        c = in_channels
+        for k, d in enumerate(conv_dims, start=1):
+            m = ConvBN(c, d, 3, col=True) if conv_norm else Conv(c, d, 3, col=True)
+            nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")          # c2_msra_fill
+            self.add_module(f"conv{k}", m); self.convs.append(m)
+            c = d
+        d_in = c * resolution * resolution
+        for k, d in enumerate(fc_dims, start=1):
+            m = nn.Linear(d_in, d)
             nn.init.kaiming_uniform_(m.weight, a=1); nn.init.constant_(m.bias, 0)
+            self.add_module(f"fc{k}", m); self.fcs.append(m)
+            d_in = d
+        self.out_features = d_in
 
     def _stage_entries(self, cd):
         st = []
         ent = []
-        for m in (self.fc1, self.fc2):
+        for m in self.fcs:
             o, i = m.weight.shape
             st.append(_Staged(w=torch.zeros(_pad8(o), i, device=m.weight.device, dtype=cd)))
             ent.append(dict(kind=0, w=m.weight, dst=st[-1].w))
@@ -1198,12 +1341,28 @@ class FastRCNNConvFCHead(nn.Module):
         return ent
 
     def forward(self, x, out_grad_premasked=False):
-        """out_grad_premasked: the caller's only consumer of the result masks its data gradient by result > 0 (_MASK_INPUT_GRAD)"""
-        s1, s2 = _staged_of(self)
-        x = _LinearFn.apply(x, s1.w, self.fc1.bias.detach(), None, _RELU | _GRAD_PREMASKED, False, (self.fc1.out_features,), None,
-                            self.fc1.weight, self.fc1.bias)
-        f2 = _RELU | _MASK_INPUT_GRAD | (_GRAD_PREMASKED if out_grad_premasked else 0)
-        return _LinearFn.apply(x, s2.w, self.fc2.bias.detach(), None, f2, False, (self.fc2.out_features,), None, self.fc2.weight, self.fc2.bias)
+        """x (R, C * 7 * 7) in (C, 7, 7) order.  out_grad_premasked: the caller's only consumer of the result masks its data
+        gradient by result > 0 (_MASK_INPUT_GRAD)"""
+        sts = _staged_of(self)
+        R = x.shape[0]
+        last = len(self.convs) + len(self.fcs) - 1
+        if self.convs:
+            P = self.resolution
+            x = x.view(R, self.in_channels, P * P).permute(0, 2, 1).contiguous().view(R, P, P, self.in_channels)
+            for k, m in enumerate(self.convs):
+                # conv k > 0 reads a ReLU output nobody else reads: its col2im masks, its producer skips relu_bwd
+                f = _RELU | (_MASK_INPUT_GRAD if k > 0 else 0) | (_GRAD_PREMASKED if (k < len(self.convs) - 1 or (k == last and out_grad_premasked)) else 0)
+                x = m(x, f)
+            x = x.view(R, P * P, x.shape[3]).permute(0, 2, 1).reshape(R, P * P * x.shape[3])
+            if not self.fcs:
+                return x
+        for k, (m, st) in enumerate(zip(self.fcs, sts)):
+            i = len(self.convs) + k
+            # (the 2-fc head: fc1 _RELU | _GRAD_PREMASKED, fc2 _RELU | _MASK_INPUT_GRAD [| _GRAD_PREMASKED]; behind convolutions the
+            # rows were re-laid by a copy, so fc1 does not mask its input gradient and the last convolution masks its own output's)
+            f = _RELU | (_MASK_INPUT_GRAD if k > 0 else 0) | (_GRAD_PREMASKED if (k < len(self.fcs) - 1 or (i == last and out_grad_premasked)) else 0)
+            x = _LinearFn.apply(x, st.w, m.bias.detach(), None, f, False, (m.out_features,), None, m.weight, m.bias)
+        return x
 
 
 class FastRCNNFocaltLossOutputLayers(nn.Module):
@@ -1256,7 +1415,7 @@ class StandardROIHeadsPseudoLab(nn.Module):
     """unbias/ubteacher/modeling/roi_heads/roi_heads.py:377-546"""
 
     def __init__(self, num_classes, sampler, batch_size_per_image=512, positive_fraction=0.25, proposal_append_gt=True, loss="FocalLoss",
-                 box_loss_type="smooth_l1"):
+                 box_loss_type="smooth_l1", box_head=None):
         super().__init__()
         # ROI_HEADS.LOSS (roi_heads.py:106-113, 405-406): "FocalLoss" (gamma 1.5) or detectron2's "CrossEntropy" (mean softmax CE
         # over the sampled rows) — the focal kernel with gamma 0 is that CE: (1 - p)^0 = 1, and its gradient term in gamma vanishes
@@ -1266,8 +1425,8 @@ class StandardROIHeadsPseudoLab(nn.Module):
         self.box_loss_type = box_loss_type
         self.keep_loss_inputs = False                 # set by TwoStagePseudoLabGeneralizedRCNN.image_losses for its one forward
         self.padded_detections = False                # True / a PaddedDetections block: set and restored by tta.GeneralizedRCNNWithTTA
-        self.box_head = FastRCNNConvFCHead()
-        self.box_predictor = FastRCNNFocaltLossOutputLayers(1024, num_classes)
+        self.box_head = FastRCNNConvFCHead(**(box_head or {}))
+        self.box_predictor = FastRCNNFocaltLossOutputLayers(self.box_head.out_features, num_classes)
         self.num_classes, self.sampler = num_classes, sampler
         self.batch_size_per_image, self.positive_fraction, self.proposal_append_gt = batch_size_per_image, positive_fraction, proposal_append_gt
 
@@ -1416,7 +1575,7 @@ class StandardROIHeadsPseudoLab(nn.Module):
         return pred, logits
 
 
-def _loss_kwargs(M):
+def _loss_kwargs(M, default_loss="FocalLoss"):
     """The loss-selection keys of a detector config -> (RPN kwargs, ROI-head kwargs): ROI_HEADS.LOSS "FocalLoss" / "CrossEntropy"
     (code_release/voc_baseline.yaml, voc_split.yaml); RPN. and ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE "smooth_l1" / "smooth_l1_mean" (the
     split configs; without gradient only: the heads raise NotImplementedError on a forward that would need its gradient).  Anything
@@ -1424,7 +1583,7 @@ def _loss_kwargs(M):
     def get(node, key, default):
         return node.get(key, default) if hasattr(node, "get") else default
     R, H, B = get(M, "RPN", {}), get(M, "ROI_HEADS", {}), get(M, "ROI_BOX_HEAD", {})
-    loss = get(H, "LOSS", "FocalLoss")
+    loss = get(H, "LOSS", default_loss)
     assert loss in ("FocalLoss", "CrossEntropy"), \
         f"MODEL.ROI_HEADS.LOSS = {loss!r} is not implemented by this detector (implemented: 'FocalLoss', 'CrossEntropy')"
     types = {}
@@ -1440,16 +1599,22 @@ class TwoStagePseudoLabGeneralizedRCNN(nn.Module):
     """unbias/ubteacher/modeling/meta_arch/rcnn.py:8-107.  `TwoStagePseudoLabGeneralizedRCNN(cfg)` (the registry call of
     rcnn_multi.build_model, selected by MODEL.META_ARCHITECTURE of unbias/configs/code_release/voc_ssod.yaml) or explicit arguments."""
 
+    # the module names of a config this class answers to, and the ROI_HEADS.LOSS of a config that does not name one
+    PROPOSAL_GENERATOR_NAMES, ROI_HEADS_NAMES, DEFAULT_ROI_LOSS = ("PseudoLabRPN",), ("StandardROIHeadsPseudoLab",), "FocalLoss"
+
     def __init__(self, cfg=None, *, num_classes=20, compute_dtype=torch.float32, freeze_at=2, sampler=None,
-                 pixel_mean=(103.530, 116.280, 123.675), pixel_std=(1.0, 1.0, 1.0)):
+                 pixel_mean=(103.530, 116.280, 123.675), pixel_std=(1.0, 1.0, 1.0), stride_in_1x1=True, fpn_norm="", box_head=None):
+        """stride_in_1x1 / fpn_norm / box_head (keyword arguments of FastRCNNConvFCHead): RESNETS.STRIDE_IN_1X1, FPN.NORM and the
+        ROI_BOX_HEAD.NUM_CONV / CONV_DIM / NUM_FC / NORM keys of a config (_arch_kwargs); the defaults are Base-RCNN-FPN.yaml's model,
+        False / "FrozenBN" / 4 conv + 1 fc with FrozenBN the SoS-WSOD+ detectors (code_release/sos_plus*_test.yaml)"""
         super().__init__()
         if cfg is not None:
             M = cfg.MODEL
             # the configuration this class implements (Base-RCNN-FPN.yaml + voc_ssod.yaml); anything else is refused, not ignored
-            # (the RPN / ROI-head / test keys: _cfg_kwargs)
+            # (the RPN / ROI-head / test keys: _cfg_kwargs; the architecture keys: _arch_kwargs)
             assert M.BACKBONE.get("NAME", "build_resnet_fpn_backbone") == "build_resnet_fpn_backbone"
-            assert M.get("PROPOSAL_GENERATOR", {}).get("NAME", "PseudoLabRPN") == "PseudoLabRPN"
-            assert M.ROI_HEADS.get("NAME", "StandardROIHeadsPseudoLab") == "StandardROIHeadsPseudoLab"
+            assert M.get("PROPOSAL_GENERATOR", {}).get("NAME", self.PROPOSAL_GENERATOR_NAMES[0]) in self.PROPOSAL_GENERATOR_NAMES
+            assert M.ROI_HEADS.get("NAME", self.ROI_HEADS_NAMES[0]) in self.ROI_HEADS_NAMES
             assert M.get("RPN", {}).get("LOSS", "CrossEntropy") == "CrossEntropy"          # (ROI_HEADS.LOSS: _loss_kwargs)
             num_classes, freeze_at = M.ROI_HEADS.NUM_CLASSES, M.BACKBONE.get("FREEZE_AT", 2)
             pixel_mean, pixel_std = M.PIXEL_MEAN, M.PIXEL_STD
@@ -1457,14 +1622,15 @@ class TwoStagePseudoLabGeneralizedRCNN(nn.Module):
             compute_dtype = torch.bfloat16 if dt_name == "bf16" else torch.float32
             sampler = Sampler(int(cfg.get("SEED", 0)) if int(cfg.get("SEED", 0)) >= 0 else 0)
             rpn_kw, roi_kw, pred_kw = self._cfg_kwargs(M, cfg.get("TEST", {}))
-            rpn_loss_kw, roi_loss_kw = _loss_kwargs(M)
+            rpn_loss_kw, roi_loss_kw = _loss_kwargs(M, self.DEFAULT_ROI_LOSS)
             rpn_kw = dict(rpn_kw, **rpn_loss_kw); roi_kw = dict(roi_kw, **roi_loss_kw)
+            stride_in_1x1, fpn_norm, box_head = self._arch_kwargs(M)
         else:
-            rpn_kw, roi_kw, pred_kw = {}, {}, {}
+            rpn_kw, roi_kw, pred_kw = {}, dict(loss=self.DEFAULT_ROI_LOSS), {}
         sampler = sampler if sampler is not None else Sampler()
-        self.backbone = FPN(ResNet(freeze_at))
+        self.backbone = FPN(ResNet(freeze_at, stride_in_1x1), fpn_norm)
         self.proposal_generator = PseudoLabRPN(sampler, **rpn_kw)
-        self.roi_heads = StandardROIHeadsPseudoLab(num_classes, sampler, **roi_kw)
+        self.roi_heads = StandardROIHeadsPseudoLab(num_classes, sampler, box_head=box_head, **roi_kw)
         bp = self.roi_heads.box_predictor
         for k, v in pred_kw.items():
             setattr(bp, k, v)
@@ -1498,7 +1664,7 @@ class TwoStagePseudoLabGeneralizedRCNN(nn.Module):
                  (get(R, "LOSS_WEIGHT", 1.0), 1.0, "RPN.LOSS_WEIGHT"), (get(R, "BBOX_REG_LOSS_WEIGHT", 1.0), 1.0, "RPN.BBOX_REG_LOSS_WEIGHT"),
                  (get(R, "BOUNDARY_THRESH", -1), -1, "RPN.BOUNDARY_THRESH"),
                  (list(get(H, "IOU_THRESHOLDS", [0.5])), [0.5], "ROI_HEADS.IOU_THRESHOLDS"), (list(get(H, "IOU_LABELS", [0, 1])), [0, 1], "ROI_HEADS.IOU_LABELS"),
-                 (get(B, "FC_DIM", 1024), 1024, "ROI_BOX_HEAD.FC_DIM"), (get(B, "NUM_FC", 2), 2, "ROI_BOX_HEAD.NUM_FC"), (get(B, "NUM_CONV", 0), 0, "ROI_BOX_HEAD.NUM_CONV"),
+                 (get(B, "FC_DIM", 1024), 1024, "ROI_BOX_HEAD.FC_DIM"),                # (NUM_FC, NUM_CONV, CONV_DIM, NORM: _arch_kwargs)
                  (get(B, "POOLER_RESOLUTION", 7), 7, "ROI_BOX_HEAD.POOLER_RESOLUTION"), (get(B, "POOLER_SAMPLING_RATIO", 0), 0, "ROI_BOX_HEAD.POOLER_SAMPLING_RATIO"),
                  (get(B, "POOLER_TYPE", "ROIAlignV2"), "ROIAlignV2", "ROI_BOX_HEAD.POOLER_TYPE"), (get(B, "SMOOTH_L1_BETA", 0.0), 0.0, "ROI_BOX_HEAD.SMOOTH_L1_BETA"),
                  (tuple(get(B, "BBOX_REG_WEIGHTS", (10.0, 10.0, 5.0, 5.0))), (10.0, 10.0, 5.0, 5.0), "ROI_BOX_HEAD.BBOX_REG_WEIGHTS"),
@@ -1510,6 +1676,32 @@ class TwoStagePseudoLabGeneralizedRCNN(nn.Module):
                 ok = (list(got) == list(want)) if isinstance(want, (list, tuple)) else got == want
             assert ok, f"MODEL.{name} = {got!r} is not implemented by this detector (implemented: {want!r})"
         return rpn_kw, roi_kw, pred_kw
+
+    @staticmethod
+    def _arch_kwargs(M):
+        """The architecture keys of a config -> (stride_in_1x1, fpn_norm, box_head kwargs): RESNETS.STRIDE_IN_1X1, FPN.NORM ("" /
+        "FrozenBN"), ROI_BOX_HEAD.NUM_CONV, CONV_DIM, NUM_FC and NORM ("" / "FrozenBN") are passed on (defaults: Base-RCNN-FPN.yaml's);
+        the other RESNETS / FPN keys of detectron2/config/defaults.py are refused unless they name what is built (ResNet-50, FrozenBN,
+        one group, no dilation / deformable convolution, 256 FPN channels fused by sum)."""
+        def get(node, key, default):
+            return node.get(key, default) if hasattr(node, "get") else default
+        Rn, F, B = get(M, "RESNETS", {}), get(M, "FPN", {}), get(M, "ROI_BOX_HEAD", {})
+        fixed = [(get(Rn, "DEPTH", 50), 50, "RESNETS.DEPTH"), (get(Rn, "NORM", "FrozenBN"), "FrozenBN", "RESNETS.NORM"),
+                 (get(Rn, "NUM_GROUPS", 1), 1, "RESNETS.NUM_GROUPS"), (get(Rn, "WIDTH_PER_GROUP", 64), 64, "RESNETS.WIDTH_PER_GROUP"),
+                 (get(Rn, "RES5_DILATION", 1), 1, "RESNETS.RES5_DILATION"), (get(Rn, "RES2_OUT_CHANNELS", 256), 256, "RESNETS.RES2_OUT_CHANNELS"),
+                 (get(Rn, "STEM_OUT_CHANNELS", 64), 64, "RESNETS.STEM_OUT_CHANNELS"),
+                 (any(get(Rn, "DEFORM_ON_PER_STAGE", [False])), False, "RESNETS.DEFORM_ON_PER_STAGE"),
+                 (get(F, "OUT_CHANNELS", 256), 256, "FPN.OUT_CHANNELS"), (get(F, "FUSE_TYPE", "sum"), "sum", "FPN.FUSE_TYPE")]
+        fpn_norm, head_norm = get(F, "NORM", ""), get(B, "NORM", "")
+        fixed += [(fpn_norm in ("", "FrozenBN"), True, f"FPN.NORM {fpn_norm!r}"), (head_norm in ("", "FrozenBN"), True, f"ROI_BOX_HEAD.NORM {head_norm!r}")]
+        n_conv, n_fc = int(get(B, "NUM_CONV", 0)), int(get(B, "NUM_FC", 2))
+        conv_dim = int(get(B, "CONV_DIM", 256))
+        fixed += [(n_conv >= 0 and n_fc >= 0 and n_conv + n_fc > 0, True, f"ROI_BOX_HEAD.NUM_CONV {n_conv} / NUM_FC {n_fc}"),
+                  (n_conv == 0 or conv_dim % 8 == 0, True, f"ROI_BOX_HEAD.CONV_DIM {conv_dim}")]
+        for got, want, name in fixed:
+            assert got == want, f"MODEL.{name} = {got!r} is not implemented by this detector (implemented: {want!r})"
+        return (bool(get(Rn, "STRIDE_IN_1X1", True)), fpn_norm,
+                dict(conv_dims=(conv_dim,) * n_conv, fc_dims=(get(B, "FC_DIM", 1024),) * n_fc, conv_norm=head_norm))
 
     def refresh_staged_weights(self):
         """the layers' compute-dtype weight copies follow the parameters: one launch when anything changed since the last call"""
@@ -1679,3 +1871,19 @@ class TwoStagePseudoLabGeneralizedRCNN(nn.Module):
             return dets
         return [{"instances": detector_postprocess(d, inp.get("height", s[0]), inp.get("width", s[1]))}
                 for d, inp, s in zip(dets, batched_inputs, sizes)]
+
+
+@META_ARCH_REGISTRY.register()
+class GeneralizedRCNN(TwoStagePseudoLabGeneralizedRCNN):
+    """detectron2/detectron2/modeling/meta_arch/rcnn.py:24-259 — the meta-architecture config.get_cfg() names by default and the
+    SoS-WSOD+ test configs select (unbias/configs/code_release/sos_plus_test.yaml, sos_plus_wo_imagenet_test.yaml): the same detector
+    with the reference's plain interface.  In training `forward(batched_inputs)` returns the four losses (rcnn.py:125-175), in
+    eval mode `inference`.  PROPOSAL_GENERATOR.NAME "RPN" and ROI_HEADS.NAME "StandardROIHeads" build the modules of the base
+    class — their pseudo-label branches are not reached through this interface — and a config without ROI_HEADS.LOSS trains with
+    detectron2's cross entropy."""
+    PROPOSAL_GENERATOR_NAMES, ROI_HEADS_NAMES, DEFAULT_ROI_LOSS = ("RPN", "PseudoLabRPN"), ("StandardROIHeads", "StandardROIHeadsPseudoLab"), "CrossEntropy"
+
+    def forward(self, batched_inputs):
+        if not self.training:
+            return self.inference(batched_inputs)
+        return super().forward(batched_inputs, branch="supervised")[0]

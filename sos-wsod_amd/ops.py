@@ -1095,6 +1095,29 @@ def scatter2x(g, out):
     return out
 
 
+def im2col3x3(x, col, stride):
+    """x (n, H, W, C) -> col (n * Ho * Wo, >= 9 C) in [tap][c] column order, Ho = (H - 1) // stride + 1 (sw_im2col3x3): with the
+    staged [co][tap][ci] weight as B, a 3x3 convolution of stride 1 or 2 is gemm(col, staged.view(cout, 9 C))"""
+    _need_gpu(x, col)
+    n, H, W, C = x.shape
+    assert x.is_contiguous() and col.dim() == 2 and col.stride(1) == 1 and col.dtype == x.dtype
+    assert col.shape[0] == n * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) and col.shape[1] >= 9 * C
+    check(lib.sw_im2col3x3(dt(x), n, H, W, C, stride, _p(x), _p(col), col.stride(0), _stream()), "sw_im2col3x3")
+    return col
+
+
+def col2im3x3(dcol, dx, stride, relu_ref=None):
+    """the adjoint of im2col3x3: dx (n, H, W, C) = the gathered sums of dcol's cells (f32, ascending tap order, rounded once), 0 where
+    relu_ref (same shape and dtype as dx) <= 0 (sw_col2im3x3); every element of dx is written"""
+    _need_gpu(dcol, dx, relu_ref)
+    n, H, W, C = dx.shape
+    assert dx.is_contiguous() and dcol.dim() == 2 and dcol.stride(1) == 1 and dcol.dtype == dx.dtype
+    assert dcol.shape[0] == n * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) and dcol.shape[1] >= 9 * C
+    assert relu_ref is None or (relu_ref.shape == dx.shape and relu_ref.dtype == dx.dtype and relu_ref.is_contiguous())
+    check(lib.sw_col2im3x3(dt(dx), n, H, W, C, stride, _p(dcol), dcol.stride(0), _p(relu_ref), _p(dx), _stream()), "sw_col2im3x3")
+    return dx
+
+
 def add_relu(a, b, out, relu=True):
     check(lib.sw_add_relu(dt(a), a.numel(), _p(a), _p(b), _p(out), int(relu), _stream()), "sw_add_relu")
     return out
