@@ -357,8 +357,10 @@ int sw_scale_scalars(int n, const float* g, const float* weights, float* out, sw
 
 /* sw_threshold_select: pseudo-label thresholding (threshold_bbox :361-400): keeps detection i iff scores[i] > thres (and, when
  * allowed_classes != NULL, classes[i] is one of the n_allowed image-level labels: the "multi_label" filter), compacted in input
- * order.  out_count[1]; out_boxes [n][4], out_classes [n] (optional: the "rpn" branch has none), out_scores [n], out_index [n]
- * (optional: source positions).  One workgroup; n is a few hundred teacher detections per image. */
+ * order.  allowed_classes == NULL: no class filter; allowed_classes != NULL with n_allowed == 0: an empty label set, nothing is kept
+ * (no class is in it, trainer.py:381-386); with a filter `classes` must be given.  out_count[1]; out_boxes [n][4], out_classes [n]
+ * (optional: the "rpn" branch has none), out_scores [n], out_index [n] (optional: source positions); rows from out_count[0] on are
+ * not written.  One workgroup; n is a few hundred teacher detections per image. */
 int sw_threshold_select(int n, const float* scores, const int32_t* classes, const float* boxes, float thres,
                         const int32_t* allowed_classes, int n_allowed, int32_t* out_count, float* out_boxes,
                         int32_t* out_classes, float* out_scores, int32_t* out_index, sw_stream_t stream);

@@ -707,7 +707,8 @@ __global__ __launch_bounds__(256) void det_loss_partial_kernel(
     float se = 0.f;
     for (int j = lane; j < C; j += 64) se += expf(x[j] - m);
     se = wave_reduce_sum(se);
-    const float ce = m + logf(se) - x[t];
+    const float c = 64.f * rintf(m * 0.015625f);                          // as focal_loss_kernel (heads.hip): exact offset, 0 for |m| < 32
+    const float ce = (m - c) + logf(se) - (x[t] - c);
     s_ce += powf(fmaxf(1.f - expf(-ce), 0.f), gamma) * ce;              // gamma 0: the plain cross-entropy term
     if (t < K) {
       const float* s = roi_boxes + r * 4;

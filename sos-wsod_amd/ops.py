@@ -917,7 +917,8 @@ def scale_scalars(g, weights, out):
 
 def threshold_select(scores, classes, boxes, thres, allowed=None):
     """-> (count[1] i32, boxes [n,4], classes [n] i32 or None, scores [n], index [n] i32): entries with score > thres (and class in
-    `allowed`, an int32 device tensor, when given), compacted in input order; the first count rows are valid"""
+    `allowed`, an int32 device tensor, when given: an empty one is an empty label set and keeps nothing), compacted in input order;
+    the first count rows are valid"""
     _need_gpu(scores, boxes)
     n = scores.shape[0]
     dev = scores.device
@@ -925,9 +926,13 @@ def threshold_select(scores, classes, boxes, thres, allowed=None):
     ob = torch.empty(max(n, 1), 4, device=dev); osc = torch.empty(max(n, 1), device=dev)
     oc = torch.empty(max(n, 1), device=dev, dtype=torch.int32) if classes is not None else None
     oi = torch.empty(max(n, 1), device=dev, dtype=torch.int32)
-    check(lib.sw_threshold_select(n, _p(scores), _p(classes), _p(boxes), float(thres), _p(allowed),
-                                  0 if allowed is None else allowed.numel(), _p(cnt), _p(ob), _p(oc), _p(osc), _p(oi), _stream()),
-          "sw_threshold_select")
+    n_allowed = 0 if allowed is None else allowed.numel()
+    if allowed is not None and classes is None:
+        raise ValueError("threshold_select: a class filter needs the classes")
+    # the entry reads NULL as "no filter", and an empty tensor has no address: hand it one it never reads, with n_allowed = 0
+    allowed_p = _p(allowed) if n_allowed or allowed is None else _p(cnt)
+    check(lib.sw_threshold_select(n, _p(scores), _p(classes), _p(boxes), float(thres), allowed_p, n_allowed, _p(cnt), _p(ob), _p(oc),
+                                  _p(osc), _p(oi), _stream()), "sw_threshold_select")
     return cnt, ob, oc, osc, oi
 
 

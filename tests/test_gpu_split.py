@@ -26,46 +26,7 @@ def ops():
 
 
 # ------------------------------------------------------------------------------------------ the kernel
-def _deltas64(src, tgt, w):
-    sw, sh = src[:, 2] - src[:, 0], src[:, 3] - src[:, 1]
-    sx, sy = src[:, 0] + 0.5 * sw, src[:, 1] + 0.5 * sh
-    tw, th = tgt[:, 2] - tgt[:, 0], tgt[:, 3] - tgt[:, 1]
-    tx, ty = tgt[:, 0] + 0.5 * tw, tgt[:, 1] + 0.5 * th
-    return np.stack([w[0] * (tx - sx) / sw, w[1] * (ty - sy) / sh, w[2] * np.log(tw / sw), w[3] * np.log(th / sh)], 1)
-
-
-def _restated(inp, rpn_bs, rpn_type, K, gamma, roi_type):
-    """float64 restatement of sw_det_loss_per_image (rpn.py:395-425, box_regression.py:229-268, fast_rcnn.py:73-105,497-564)"""
-    lo, de, lab, an, ma, lg, cls, bx, gt, cnt = [t.double().cpu().numpy() if t.is_floating_point() else t.cpu().numpy() for t in inp]
-    N = lo.shape[0]
-    res = np.zeros((N, 5))
-    off = 0
-    with np.errstate(invalid="ignore", divide="ignore"):
-        for n in range(N):
-            x, lb = lo[n], lab[n]
-            v = lb >= 0
-            bce = (np.maximum(x, 0) - x * (lb == 1) + np.log1p(np.exp(-np.abs(x))))[v].sum()
-            fg = lb == 1
-            l1 = np.abs(de[n][fg] - _deltas64(an[fg], ma[n][fg], (1.0, 1.0, 1.0, 1.0))).sum()
-            rc = bce / rpn_bs
-            rl = (l1 / (4 * fg.sum())) / rpn_bs if rpn_type == "smooth_l1_mean" else l1 / rpn_bs
-            c = int(cnt[n])
-            rows = slice(off, off + c)
-            off += c
-            z = lg[rows, :K + 1]
-            m = z.max(1, keepdims=True) if c else np.zeros((0, 1))
-            lse = (m[:, 0] + np.log(np.exp(z - m).sum(1))) if c else np.zeros(0)
-            t = cls[rows]
-            ce = lse - z[np.arange(c), t]
-            p = np.exp(-ce)
-            lcls = ((1 - p) ** gamma * ce).sum() / c if c else 0.0
-            f = t < K
-            pred = np.stack([lg[rows][f][i, K + 1 + 4 * t[f][i]: K + 5 + 4 * t[f][i]] for i in range(int(f.sum()))]) if f.any() else np.zeros((0, 4))
-            bl = np.abs(pred - _deltas64(bx[rows][f], gt[rows][f], (10.0, 10.0, 5.0, 5.0))).sum()
-            lbox = bl / (4 * f.sum()) if roi_type == "smooth_l1_mean" else bl / max(c, 1)
-            res[n, :4] = lcls, lbox, rc, rl
-            res[n, 4] = lcls + lbox + rc + rl
-    return res
+from losses_ref import det_loss_ref as _restated  # noqa: E402  (the one float64 restatement of sw_det_loss_per_image)
 
 
 def _random_inputs(N, A, K, counts, zero_rpn_fg, zero_roi_fg, seed=0):
