@@ -781,6 +781,63 @@ int sw_strong_aug_u8(int H, int W, const uint8_t* in, const sw_aug_recipe* recip
  * largest H and W among them; stages: SW_AUG_STAGE_* bits, which launches the batch needs.  Same bytes as n single calls. */
 int sw_strong_aug_multi_u8(int n, const sw_aug_item* items_dev, int max_h, int max_w, int stages, sw_stream_t stream);
 
+/* Baseline JPEG reader, every pixel equal to Pillow's (libjpeg's defaults: the "islow" integer IDCT, "fancy" chroma upsampling,
+ * the 16-bit fixed-point YCbCr -> RGB rule).  Replaces the pixel side of detection_utils.read_image
+ * (detectron2/data/detection_utils.py:162-185: Image.open, convert("RGB"), the plane reversal for BGR); the EXIF orientation it
+ * reports is applied by the caller.  The HOST parses the markers and undoes the Huffman coding (two plain C functions, no GPU
+ * call, no globals: callable from any number of threads); dequantisation, IDCT, upsampling, colour and plane order are two
+ * kernels over a whole batch of images of mixed sizes and samplings.
+ *
+ * Covered (sw_jpeg_probe returns 1): 8-bit SOF0 / SOF1, Huffman coding, one interleaved scan, 1 component (sampling 1x1) or 3
+ * YCbCr components with luma 1x1, 2x1 or 2x2 and chroma 1x1.  Not covered (returns 0, `info` undefined): every other SOF,
+ * 12-bit samples, a scan without all components, 2 or 4 components, any other sampling, height 0 (DNL), an Adobe APP14 marker whose
+ * transform is not 1, component ids 'R' 'G' 'B' without JFIF.  Negative: -1 argument, -2 no SOI (not a JPEG), -3 the marker
+ * segments end early, -4 malformed segment, -5 a table or the frame is missing, -6 the entropy-coded data ends early, -7 invalid
+ * Huffman code or coefficient index, -8 restart marker missing or wrong, -9 `info` does not describe this stream;
+ * sw_jpeg_strerror names them.
+ * Stricter than libjpeg, which warns and decodes on: entropy data that ends early, or bytes between the last MCU of a restart
+ * interval and its RSTn, are errors here. */
+typedef struct sw_jpeg_info {
+  int32_t width, height;
+  int32_t ncomp;                      /* 1 or 3 */
+  int32_t restart_interval;           /* in MCUs; 0: none */
+  int32_t orientation;                /* EXIF tag 274 of the first APP1 "Exif" segment's IFD0 if in 1..8, else 1 */
+  int32_t mcus_x, mcus_y;
+  int32_t hsamp[3], vsamp[3], qtable[3];
+  int32_t blocks_w[3], blocks_h[3];   /* the component's padded grid in 8 x 8 blocks: mcus_x * hsamp, mcus_y * vsamp */
+  int64_t coef_bytes;                 /* 128 * sum(blocks_w * blocks_h) */
+} sw_jpeg_info;
+int sw_jpeg_probe(const uint8_t* bytes, long n, sw_jpeg_info* info);
+/* coef: info->coef_bytes bytes; quantised coefficients, 64 per block in natural (de-zigzagged) order, blocks in raster order over
+ * component 0's padded grid, then component 1's, then 2's.  qtables: uint16[4][64] by table index, natural order, an undefined
+ * table all 0.  Reads bytes[0 .. n) only.  coef is zeroed first, so on a negative return every block is defined: the blocks decoded
+ * before the error hold their coefficients (the block the error fell in holds those decoded so far), all later ones are 0. */
+int sw_jpeg_entropy_decode(const uint8_t* bytes, long n, const sw_jpeg_info* info, int16_t* coef, uint16_t* qtables);
+const char* sw_jpeg_strerror(int code);
+/* one image of a batch, as the kernels read it */
+typedef struct sw_jpeg_desc {
+  uint8_t* out;                       /* (3, height, width) u8; exactly these 3 * height * width bytes are written */
+  int64_t coef_off;                   /* int16 elements from `coef` to this image's first block */
+  int64_t qtab_off;                   /* uint16 elements from `qtables` to this image's four tables */
+  int64_t plane_off;                  /* bytes from `workspace` to component 0's padded plane; the others follow */
+  int32_t block_start, quad_start;    /* blocks / 4-pixel row pieces of the images before this one */
+  int32_t width, height, ncomp, hsamp, vsamp, bgr;
+  int32_t blocks_w[3], blocks_h[3], qtable[3];
+  int32_t pad_;
+} sw_jpeg_desc;
+/* HOST arithmetic: the batch layout.  Image i's coefficients start where image i-1's end (the first at 0), its tables at
+ * uint16 256 * i, its planes at 64 bytes per block in the same order: sw_jpeg_workspace_bytes = 64 * all blocks.  bgr: plane order of
+ * every output (0: R, G, B).  -6: 2^31 blocks or 4-pixel pieces or more. */
+long sw_jpeg_workspace_bytes(int n_images, const sw_jpeg_info* infos);
+int sw_jpeg_describe_batch(int n_images, const sw_jpeg_info* infos, void* const* outs, int bgr, sw_jpeg_desc* descs,
+                           long* total_blocks, long* total_quads);
+/* Two launches whatever n_images is: blocks -> padded component planes in `workspace` (dequantise, IDCT, +128, limit), then planes ->
+ * pixels (upsample, convert, plane order).  descs: DEVICE array of n_images entries as sw_jpeg_describe_batch fills them, with the
+ * totals it returned; coef, qtables: DEVICE copies of what sw_jpeg_entropy_decode wrote, 16-byte aligned; workspace: 256-byte
+ * aligned.  Integer arithmetic only: the same bytes on every run. */
+int sw_jpeg_decode_batch(int n_images, const sw_jpeg_desc* descs, long total_blocks, long total_quads, const int16_t* coef,
+                         const uint16_t* qtables, uint8_t* workspace, sw_stream_t stream);
+
 const char* sw_version(void);
 
 #ifdef __cplusplus

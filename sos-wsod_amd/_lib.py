@@ -111,6 +111,23 @@ class SgdTensor(ctypes.Structure):
     ]
 
 
+class JpegInfo(ctypes.Structure):
+    """sw_jpeg_info"""
+    _fields_ = [("width", c_int32), ("height", c_int32), ("ncomp", c_int32), ("restart_interval", c_int32),
+                ("orientation", c_int32), ("mcus_x", c_int32), ("mcus_y", c_int32),
+                ("hsamp", c_int32 * 3), ("vsamp", c_int32 * 3), ("qtable", c_int32 * 3),
+                ("blocks_w", c_int32 * 3), ("blocks_h", c_int32 * 3), ("coef_bytes", ctypes.c_int64)]
+
+
+class JpegDesc(ctypes.Structure):
+    """sw_jpeg_desc"""
+    _fields_ = [("out", c_void_p), ("coef_off", ctypes.c_int64), ("qtab_off", ctypes.c_int64), ("plane_off", ctypes.c_int64),
+                ("block_start", c_int32), ("quad_start", c_int32),
+                ("width", c_int32), ("height", c_int32), ("ncomp", c_int32), ("hsamp", c_int32), ("vsamp", c_int32),
+                ("bgr", c_int32), ("blocks_w", c_int32 * 3), ("blocks_h", c_int32 * 3), ("qtable", c_int32 * 3),
+                ("pad_", c_int32)]
+
+
 SGD_MAX_TENSORS = 24          # SW_SGD_MAX_TENSORS
 _EP = ctypes.POINTER(Epilogue)
 _F4 = ctypes.POINTER(c_float)
@@ -262,6 +279,14 @@ SIGNATURES = {
     # ---- proposal recall (csrc/proposal_recall.hip)
     "sw_proposal_recall": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
+    # ---- JPEG reader (csrc/jpeg.hip); the first five are host code
+    "sw_jpeg_probe": (c_int, [c_void_p, c_long, ctypes.POINTER(JpegInfo)]),
+    "sw_jpeg_entropy_decode": (c_int, [c_void_p, c_long, ctypes.POINTER(JpegInfo), c_void_p, c_void_p]),
+    "sw_jpeg_strerror": (ctypes.c_char_p, [c_int]),
+    "sw_jpeg_workspace_bytes": (c_long, [c_int, ctypes.POINTER(JpegInfo)]),
+    "sw_jpeg_describe_batch": (c_int, [c_int, ctypes.POINTER(JpegInfo), ctypes.POINTER(c_void_p), c_int, ctypes.POINTER(JpegDesc),
+                                       ctypes.POINTER(c_long), ctypes.POINTER(c_long)]),
+    "sw_jpeg_decode_batch": (c_int, [c_int, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sw_version": (ctypes.c_char_p, []),
 }
 

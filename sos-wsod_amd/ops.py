@@ -1506,3 +1506,53 @@ def proposal_recall(prop_off, prop_box, gt_off, gt_box, cuts, thr, ovmax=None, j
     check(lib.sw_proposal_recall(n_img, _p(prop_off), _p(prop_box), _p(gt_off), _p(gt_box), n_cut, _p(cuts), n_thr, _p(thr),
                                  _p(ovmax), _p(jmax), _p(cnt_yes), _stream()), "sw_proposal_recall")
     return ovmax, jmax, cnt_yes
+
+
+# ================================================================================================ JPEG reader (csrc/jpeg.hip)
+def jpeg_error(code):
+    """the host code's reason for a probe / entropy-decode return code"""
+    return lib.sw_jpeg_strerror(int(code)).decode()
+
+
+def jpeg_probe(data):
+    """sw_jpeg_probe over a contiguous uint8 numpy array (HOST code, no GPU).  -> (code, JpegInfo): 1 covered, 0 left to Pillow,
+    negative malformed (-2: not a JPEG at all)"""
+    from ._lib import JpegInfo
+    info = JpegInfo()
+    return lib.sw_jpeg_probe(ctypes.c_void_p(data.ctypes.data), data.size, ctypes.byref(info)), info
+
+
+def jpeg_entropy_decode(data, info, coef_addr, qtab_addr):
+    """sw_jpeg_entropy_decode (HOST code; ctypes drops the GIL for its duration): info.coef_bytes bytes of int16 coefficients to
+    coef_addr, 512 bytes of tables to qtab_addr, both host addresses.  -> the return code"""
+    return lib.sw_jpeg_entropy_decode(ctypes.c_void_p(data.ctypes.data), data.size, ctypes.byref(info), ctypes.c_void_p(coef_addr),
+                                      ctypes.c_void_p(qtab_addr))
+
+
+def jpeg_workspace_bytes(infos):
+    """bytes of planes sw_jpeg_decode_batch writes for these images; infos: a ctypes array of JpegInfo"""
+    n = lib.sw_jpeg_workspace_bytes(len(infos), infos)
+    if n < 0:
+        raise ValueError("sw_jpeg_workspace_bytes: an info does not describe a covered image")
+    return n
+
+
+def jpeg_describe_batch(infos, outs, bgr, descs_addr):
+    """fill len(infos) sw_jpeg_desc records at the host address descs_addr (sw_jpeg_describe_batch).  outs: (3, H, W) uint8 device
+    tensors.  -> (total_blocks, total_quads)"""
+    from ._lib import JpegDesc
+    n = len(infos)
+    for o, f in zip(outs, infos):
+        _need_gpu(o)
+        assert o.dtype == torch.uint8 and tuple(o.shape) == (3, f.height, f.width) and o.is_contiguous(), "out: contiguous (3, H, W) uint8"
+    ptrs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+    tb, tq = ctypes.c_long(), ctypes.c_long()
+    check(lib.sw_jpeg_describe_batch(n, infos, ptrs, int(bool(bgr)), ctypes.cast(descs_addr, ctypes.POINTER(JpegDesc)),
+                                     ctypes.byref(tb), ctypes.byref(tq)), "sw_jpeg_describe_batch")
+    return tb.value, tq.value
+
+
+def jpeg_decode_batch(n, descs_addr, total_blocks, total_quads, coef_addr, qtab_addr, workspace_addr):
+    """the two launches of sw_jpeg_decode_batch on the current stream; every address is a device address"""
+    check(lib.sw_jpeg_decode_batch(n, ctypes.c_void_p(descs_addr), total_blocks, total_quads, ctypes.c_void_p(coef_addr),
+                                   ctypes.c_void_p(qtab_addr), ctypes.c_void_p(workspace_addr), _stream()), "sw_jpeg_decode_batch")

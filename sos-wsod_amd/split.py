@@ -307,6 +307,10 @@ def parse_args(argv=None):
     s.add_argument("--voc-root", default="datasets/VOC2007")
     s.add_argument("--images-per-batch", type=int, default=8)
     s.add_argument("--seed", type=int, default=0)
+    s.add_argument("--decode", choices=("pillow", "device"), default="pillow",
+                   help="pillow: decode on the host, one thread; device: image_io.JpegLoader (Huffman decoding on the host, the "
+                        "pixels on the GPU, equal to Pillow's; unlike pillow it also applies the EXIF orientation, as the "
+                        "reference's read_image does)")
     return p.parse_args(argv)
 
 
@@ -352,7 +356,12 @@ def main(argv=None, *, scorer=None, dataset_dicts=None):
     else:
         target = None
     print("loss calculating")
-    losses = scorer(target, dicts, _pillow_bgr, images_per_batch=args.images_per_batch, seed=args.seed, min_sizes=min_sizes,
+    if args.decode == "device":
+        from .image_io import JpegLoader
+        loader = JpegLoader("BGR")
+    else:
+        loader = _pillow_bgr
+    losses = scorer(target, dicts, loader, images_per_batch=args.images_per_batch, seed=args.seed, min_sizes=min_sizes,
                     max_size=max_size)
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
