@@ -306,7 +306,17 @@ int sw_oicr_predict(int R, int K, int refine_k, const float* logits, long ld, in
 /* sw_detect_postprocess: clip boxes to the image, keep score > score_thresh (background column excluded), per-class
  * greedy NMS (IoU > nms_thresh on boxes offset by class*(max_coord+1), as batched_nms forms them), first topk by
  * score.  Outputs det_count[1], det_boxes [topk][4], det_scores, det_classes, det_rows (proposal index).
- * Limits: R <= 16384, K*topk <= 16384.
+ * Limits: R <= 16384, K*topk <= 16384, topk >= 1 (else -6, nothing written); R <= 0: det_count = 0.
+ * Order: inside a class by score descending, then proposal index ascending; the final list by score descending, then r*K + c
+ * ascending (the position in the reference's nonzero() list).  Scores rank by VALUE: -0.0 and +0.0 are one score, the position
+ * decides between them, and a zero score is returned as +0.0; every other score is returned bit for bit.
+ * Where this entry differs from the reference on purpose:
+ *  - rows with a non-finite box or score are NOT dropped (fast_rcnn_oicr.py:110-114 drops them): the callers pass finite rows;
+ *  - NMS runs per class.  batched_nms makes ONE greedy pass over all classes; after the class offset boxes of different classes
+ *    have IoU 0 (or NaN), which never exceeds nms_thresh >= 0, so the keep set is the same.  With nms_thresh < 0 it is not: here
+ *    every class keeps its best box (plus the boxes whose IoU with every kept one is NaN: two empty boxes), the one-pass form
+ *    would let the best box of the image suppress every other class.
+ * Only the first det_count rows of the four output arrays are written.
  * workspace_bytes says how large the workspace is.  With >= sw_detect_workspace_bytes(R, K, topk) bytes the per-class NMS of every
  * class that holds >= 256 candidates runs in its mask form — candidates sorted per class, the 64 x 64 IoU tiles of every class
  * computed over all CUs, one wave per class resolving the chunks in order (the RPN's per-level lists of detectron2's

@@ -683,6 +683,11 @@ __global__ __launch_bounds__(256) void predict_kernel(int R, int K, int RK, cons
 
 __device__ __forceinline__ float clipf(float v, float hi) { return fminf(fmaxf(v, 0.f), hi); }
 
+// The detection keys rank by score VALUE as the reference's sort does: -0.0 and +0.0 are one score (an RPN logit can be either) and the
+// position decides between them.  make_key ranks by bits (+0.0 above -0.0), so a zero goes into a detection key as +0.0 — and comes out of
+// sw_detect_postprocess as +0.0.
+__device__ __forceinline__ float det_score(float s) { return s == 0.f ? 0.f : s; }
+
 // max coordinate over the clipped boxes that pass the score filter (boxes.max() inside batched_nms)
 __global__ void det_maxcoord_kernel(int R, int K, float thresh, float imw, float imh, const float* __restrict__ scores,
                                     const float* __restrict__ boxes, float* __restrict__ out) {
@@ -733,7 +738,7 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
     int base = 0;
     if (lane == 0 && m) base = atomicAdd(&s_valid, __popcll(m));
     base = __shfl(base, 0);
-    if (ok) keys[base + __popcll(m & ((1ull << lane) - 1))] = make_key(scores[(long)i * (K + 1) + c], (unsigned)i);
+    if (ok) keys[base + __popcll(m & ((1ull << lane) - 1))] = make_key(det_score(scores[(long)i * (K + 1) + c]), (unsigned)i);
     if (i < R) sup[i] = 0;
   }
   __syncthreads();
@@ -850,7 +855,7 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
   for (int t = 0; t < nv && nk < topk; ++t) {
     const int p = (int)(keys[t] & 0xFFFFFFFFu);
     if (sup[p]) continue;
-    if (tid == 0) { cls_rows[c * topk + nk] = p; cls_scores[c * topk + nk] = scores[(long)p * (K + 1) + c]; }
+    if (tid == 0) { cls_rows[c * topk + nk] = p; cls_scores[c * topk + nk] = det_score(scores[(long)p * (K + 1) + c]); }
     ++nk;
     const float* bp = boxes + (long)p * 4 * K + 4 * c;
     float a[4] = {__fadd_rn(clipf(bp[0], imw), off), __fadd_rn(clipf(bp[1], imh), off), __fadd_rn(clipf(bp[2], imw), off),

@@ -1186,7 +1186,7 @@ def test_detect_postprocess_vs_oracle(ops, R, K):
 @pytest.mark.parametrize("case", ["rpn", "classes", "one_class_beyond_lds", "ragged"])
 def test_detect_postprocess_mask_form_equals_single_workgroup_form(ops, case):
     """sw_detect_postprocess with the full workspace (mask form: prep / 64x64 IoU tiles over the chip / one resolving wave per class) against
-    the same entry with sw_detect_workspace_bytes(0, K, topk) bytes (one workgroup per class, itself pinned by the oracle above and by tools/fuzz_parity.py): every output bit
+    the same entry with sw_detect_workspace_bytes(0, K, topk) bytes (one workgroup per class, itself pinned against an independent reference by test_gpu_detect_postprocess.py, as the mask form is): every output bit
     for bit — the RPN's use (5 levels as classes, 8741 candidates, best 1000 at IoU 0.7), 20 classes x 2000 proposals at the
     detector's thresholds, ONE class of 5000 candidates (rows beyond the resolver's 4096-row LDS window), classes of 0 / 1 / 65
     candidates."""
