@@ -3,12 +3,21 @@
 //   uwsod/projects/WSL/wsl/layers/csrc/ROILoopPool/ROILoopPool_cpu.cpp:26-79 (fwd), :98-123 (bwd)
 // (= torchvision 0.7 RoIPool): round(x*scale), +1 extent, float bin = extent/P, floor/ceil bin edges,
 // clip to the map, strict '>' from -FLT_MAX (first max in row-major order), empty bin -> 0 / -1.
+// Every forward form below computes exactly that, bit for bit; they differ in where the map is held and how a bin window is walked.
 //
-// Forward: one workgroup per (roi, 64-channel slab).  Lanes run over channels so that every pixel read
-// is one coalesced 128/256-byte row segment of the NHWC map (the whole map is L2 / Infinity-Cache
-// resident); the 4 waves split the PHxPW bins; results are transposed through LDS so that the
-// (R, C, PH, PW) output — the layout the reference's fc6 weight expects — is written as one contiguous
-// run of 64*PH*PW elements per workgroup.  HBM-bound on the output + argmax stream.
+// Forward forms, in the order sw_roi_pool_fwd / roi_fwd_dispatch try them:
+//   1. prepared tasks   roi_pool_geo_kernel + roi_pool_tasks_kernel + roi_pool_fwd_tasks_kernel: with a workspace; bf16, C % 8 == 0,
+//                       pooled size <= 8 x 8, maps that do NOT fit LDS whole at 8 channels per lane.  Row sparse table over row bands,
+//                       the (ROI, bin row) tasks sorted once per call instead of once per channel slab.
+//   2. sparse table     roi_pool_fwd_sparse_kernel: bf16, C % 8 == 0, pooled size <= 8 x 8, R <= 16384.  Whole map at 8 channels per
+//                       lane, else row bands at 4.  Two LDS reads per window ROW.
+//   3. plane, row bands roi_pool_fwd_plane_kernel<KEY, BAND>: bf16, C % 8 == 0, maps whose plane does not fit at 16 bytes per pixel.
+//   4. plane            roi_pool_fwd_plane_kernel: the widest channel slab (16 / 8 / 4 bytes per pixel) whose plane fits LDS; bf16 maps
+//                       of < 65535 pixels scan packed keys (KEY), f32 compares values.  One LDS read per window PIXEL.
+//   5. gather           roi_pool_fwd_kernel: everything else (H or W > 255, planes too large, unaligned maps): a workgroup per ROI
+//                       reads its windows from L2.
+// Forms 1-4 need H, W <= 255 (8-bit bin tables) and a 16-byte aligned map.  What the forms share — the reference's bin edges, the
+// class rules, the packed candidates and their decode, the sparse table's build / advance / scan — is defined once, ahead of them.
 //
 // Backward: one workgroup per (image, CB-channel slab) owns dfeat[:, :, slab] in LDS (H*W*CB f32),
 // sweeps every ROI of that image once, accumulates with LDS atomics and writes its slab exactly once:
@@ -62,6 +71,148 @@ template <> struct ArgIdx<unsigned short> {
   __device__ static __forceinline__ int dec(unsigned short v) { return v == 0xFFFF ? -1 : (int)v; }
 };
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// What the forward forms share.
+//
+// Bin p of a ROI axis (ROILoopPool_cpu.cpp:36-52): [floor(p * bin), ceil((p + 1) * bin)) plus the ROI's start, clipped to the map.
+// THE bit-exact contract with the reference: the one place that spells it.
+struct BinRange {
+  int s, e;                                                          // [s, e)
+  __device__ __forceinline__ unsigned int packed() const { return (unsigned)(s | (e << 8)); }      // start | end << 8  (H, W <= 255)
+};
+__device__ __forceinline__ BinRange bin_unclipped(float bin, int p) {
+  return BinRange{(int)floorf(__fmul_rn((float)p, bin)), (int)ceilf(__fmul_rn((float)(p + 1), bin))};
+}
+__device__ __forceinline__ BinRange bin_clipped(float bin, int start, int p, int extent) {
+  const BinRange u = bin_unclipped(bin, p);
+  return BinRange{min(max(u.s + start, 0), extent), min(max(u.e + start, 0), extent)};
+}
+__device__ __forceinline__ BinRange bin_rows(const RoiGeom& g, int ph, int H) { return bin_clipped(g.bin_h, g.start_h, ph, H); }
+__device__ __forceinline__ BinRange bin_cols(const RoiGeom& g, int pw, int W) { return bin_clipped(g.bin_w, g.start_w, pw, W); }
+// width of bin column pw's window before clipping (the level rule below is about the ROI, not about where the map cuts it)
+__device__ __forceinline__ int bin_cols_unclipped_width(const RoiGeom& g, int pw) {
+  const BinRange u = bin_unclipped(g.bin_w, pw);
+  return u.e - u.s;
+}
+
+// Size class of a bin extent: a window is ~ ceil(bin) + 1 pixels high (wide).  Lanes of a wave walk their windows to the longest one,
+// so tasks are grouped by class: neighbours of similar size waste less.
+constexpr int SP_NT = 1024, SP_CH = 128, SP_NLEV = 6, SP_NHC = 7, SP_NCLS = SP_NLEV * SP_NHC;
+__device__ __forceinline__ int bin_size_class(float b) {
+  return b < 1.f ? 0 : b < 2.f ? 1 : b < 3.f ? 2 : b < 4.f ? 3 : b < 6.f ? 4 : b < 8.f ? 5 : 6;      // SP_NHC classes
+}
+// Class of a ROI in the sparse-table forms: level x window-height class.  Level L = floor(log2(narrowest UNCLIPPED bin window)),
+// capped at SP_NLEV - 1: the unclipped widths of one ROI differ by at most one pixel, so 2^L <= width <= 2^(L+1) for all of them.
+__device__ __forceinline__ int roi_level_class(const RoiGeom& g, int PW) {
+  int m = 1 << 30;
+  for (int pw = 0; pw < PW; ++pw) m = min(m, bin_cols_unclipped_width(g, pw));
+  m = max(m, 1);
+  const int L = min(31 - __clz(m), SP_NLEV - 1);
+  return L * SP_NHC + bin_size_class(g.bin_h);
+}
+
+// Packed candidates (bf16 maps of < 65535 pixels).  A bf16 value becomes an order-preserving 16-bit key (positive: b ^ 0x8000,
+// negative: ~b) and the running maximum of a (bin, channel) is ONE u32  key << 16 | (0xFFFE - pixel): v_max_u32 then implements
+// "larger value, else earlier pixel" — exactly the winner of the reference's strict '>' scan in row-major order.  The start value
+// KEY_INIT can only be beaten by values > -inf, i.e. exactly those that beat -FLT_MAX.
+__device__ __forceinline__ unsigned int key16_of(unsigned int bts) {
+  unsigned int key = (bts & 0x8000u) ? (bts ^ 0xFFFFu) : (bts | 0x8000u);
+  if (bts > 0x7F80u && bts < 0x8000u) key = 0;                                // +NaN never wins, as with the reference's '>'
+  if (bts == 0x8000u) key = 0x8000u;                                          // -0.0 == +0.0 under '>': the earlier pixel wins
+  return key;                                                                 // (a bin won by a -0.0 pixel then outputs +0.0)
+}
+constexpr unsigned int KEY_INIT = 0x007FFFFFu;                                // key(-inf) << 16 | 0xFFFF
+
+// candidate -> (value, pixel).  key -> bf16 bits: positive values (key bit 15 set) flip that bit back, negative ones were stored
+// complemented; the pixel index 0xFFFE - low half is -1 by itself when nothing won (low half still 0xFFFF).  best never drops below
+// KEY_INIT, and a channel still AT it (empty bin, or a window of -inf / NaN only) is the one case the reference answers differently
+// (0 resp. -FLT_MAX): one min over the channels finds it, so the common path pays no per-channel selects
+template <int CB>
+__device__ __forceinline__ void decode_candidates(const unsigned int (&best)[CB], bool empty, float (&mv)[CB], int (&mi)[CB]) {
+  unsigned int lowest = best[0];
+#pragma unroll
+  for (int q = 0; q < CB; ++q) {
+    const unsigned int m = (unsigned int)((int)best[q] >> 31);
+    mv[q] = __uint_as_float((best[q] & 0xFFFF0000u) ^ (0x80000000u | (~m & 0x7FFF0000u)));
+    mi[q] = (int)(0xFFFEu - (best[q] & 0xFFFFu));
+    lowest = min(lowest, best[q]);
+  }
+  if (lowest == KEY_INIT) {
+#pragma unroll
+    for (int q = 0; q < CB; ++q)
+      if (best[q] == KEY_INIT) mv[q] = empty ? 0.f : -FLT_MAX;
+  }
+}
+
+// A finished task (ROI, bin, CB channels) goes straight to the (R, C, PH, PW) output at o = its first channel's element.
+// 2 x CB two-byte stores per task (a 64-lane wave writes one contiguous 98-byte run per channel and ROI): measured 45 us of the
+// 260 us a 4000-ROI call takes (stores compiled out: 215 us), the rest is the scan's VALU issue — staging the rows through LDS
+// for 16-byte stores would need 31 KiB more LDS and drop 63x63 maps to one workgroup per CU (measured with padded LDS: +10 %),
+// so the stores stay direct
+template <typename T, typename IT, int CB>
+__device__ __forceinline__ void store_task(T* __restrict__ out, IT* __restrict__ argmax, long o, int nb, const float (&mv)[CB],
+                                           const int (&mi)[CB], float mul) {
+#pragma unroll
+  for (int q = 0; q < CB; ++q) {
+    Elem<T>::store(out + o + (long)q * nb, __fmul_rn(mv[q], mul));        // (nontemporal 2-byte stores: 250 -> 415 us, they are
+    argmax[o + (long)q * nb] = ArgIdx<IT>::enc(mi[q]);                    //  not merged into full lines on the way out)
+  }
+}
+
+// One chunk's bin tables in LDS, for the ROIs roi_of(0 .. cnt-1): bin ranges once per (ROI, bin row / column) instead of once per
+// (ROI, bin, channel slab lane) — the plane scan is VALU-issue bound (rocprof: 31 VALU instructions per window pixel, a third of them
+// this per-task geometry).  STORE_R: s_r[cnt] receives the ROI row of the entries.
+template <int NT, bool STORE_R, typename RoiOf>
+__device__ __forceinline__ void fill_bin_tables(int cnt, int PH, int PW, int H, int W, float scale, const float* __restrict__ rois,
+                                                const float* __restrict__ row_scale, float row_scale_add, RoiOf roi_of,
+                                                unsigned short* s_hb, unsigned short* s_wb, float* s_mul, int* s_r) {
+  for (int i = threadIdx.x; i < cnt * (PH + PW); i += NT) {
+    const int li = i / (PH + PW), k = i - li * (PH + PW);
+    const int r = roi_of(li);
+    const RoiGeom g = roi_geom(rois + (long)r * 5, scale, PH, PW);
+    if (k == 0) {
+      if (STORE_R) s_r[li] = r;
+      s_mul[li] = row_scale ? (row_scale[r] + row_scale_add) : 1.0f;
+    }
+    if (k < PH) s_hb[li * PH + k] = (unsigned short)bin_rows(g, k, H).packed();
+    else s_wb[li * PW + (k - PH)] = (unsigned short)bin_cols(g, k - PH, W).packed();
+  }
+}
+
+// Row bands (maps that do not fit LDS whole): band b OWNS map rows [b * S, (b + 1) * S) — a (ROI, bin row) pair belongs to the band
+// that owns its first window row — and HOLDS `rows` rows from y0(b) on in LDS; the rows - S >= ceil(H / PH) + 1 rows of overlap hold
+// the rest of any window of a ROI that lies inside the image.  clamp_last: the last band starts early enough to hold `rows` rows too
+// (more ROIs then lie inside one band).
+struct BandGeom {
+  int S, rows, n_bands;
+  bool clamp_last;
+  __host__ __device__ int owner(int first_row) const { const int b = first_row / S; return b < n_bands - 1 ? b : n_bands - 1; }
+  __host__ __device__ int y0(int band, int H) const {
+    const int y = band * S, top = H - rows > 0 ? H - rows : 0;
+    return clamp_last && y > top ? top : y;
+  }
+  __host__ __device__ int y1(int band, int H) const { const int y = y0(band, H) + rows; return y < H ? y : H; }
+};
+
+// The (ROI entry, bin row) pairs of a chunk that `band` owns, compacted into s_task as entry << 8 | bin row; *s_ntask (zeroed by the
+// caller) counts them.  Order inside a wave is kept: the size classes stay together; across waves it is whatever order the counter was
+// reached in — the results do not depend on it.
+template <int NT>
+__device__ __forceinline__ void compact_owned_pairs(int n_pairs, int PH, const unsigned short* s_hb, const BandGeom& bg, int band,
+                                                    unsigned int* s_task, int* s_ntask) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int e0 = 0; e0 < n_pairs; e0 += NT) {
+    const int e = e0 + tid;
+    bool mine = false;
+    if (e < n_pairs) mine = bg.owner((int)(s_hb[e] & 0xFF)) == band;
+    const unsigned long long m = __ballot(mine);
+    int base = 0;
+    if (lane == 0 && m) base = atomicAdd(s_ntask, __popcll(m));
+    base = __shfl(base, 0);
+    if (mine) { const int li = e / PH; s_task[base + __popcll(m & ((1ull << lane) - 1))] = (unsigned)(li << 8) | (unsigned)(e - li * PH); }
+  }
+}
+
 // Forward.  Workgroup = (roi, slab of 64*VEC channels), 4 waves split the PHxPW bins, lane = VEC adjacent channels
 // (bf16: one 4-byte load carries 2 channels => 256-byte wave loads).  The scan of a bin is latency bound (every NHWC
 // row segment is an L2 / Infinity-Cache hit), so a wave keeps 8 pixel loads in flight: the bin window is walked as a
@@ -98,12 +249,8 @@ __global__ __launch_bounds__(256) void roi_pool_fwd_kernel(int H, int W, int C, 
   const T* fimg = feat + (long)g.batch * H * W * C + (cok ? c : 0);
   for (int b = wave; b < nb; b += 4) {
     const int ph = b / PW, pw = b - ph * PW;
-    int hs = (int)floorf(__fmul_rn((float)ph, g.bin_h));
-    int ws = (int)floorf(__fmul_rn((float)pw, g.bin_w));
-    int he = (int)ceilf(__fmul_rn((float)(ph + 1), g.bin_h));
-    int we = (int)ceilf(__fmul_rn((float)(pw + 1), g.bin_w));
-    hs = min(max(hs + g.start_h, 0), H); he = min(max(he + g.start_h, 0), H);
-    ws = min(max(ws + g.start_w, 0), W); we = min(max(we + g.start_w, 0), W);
+    const BinRange rh = bin_rows(g, ph, H), rw = bin_cols(g, pw, W);
+    const int hs = rh.s, he = rh.e, ws = rw.s, we = rw.e;
     const bool empty = (he <= hs) || (we <= ws);
     float mv[VEC]; int mi[VEC];
 #pragma unroll
@@ -391,17 +538,12 @@ __device__ __forceinline__ void pix_decode(const typename PixWord<CB * (int)size
   }
 }
 
-// KEY = true (bf16 maps of < 65535 pixels): the LDS copy holds order-preserving 16-bit keys instead of bf16 bits
-// (positive: b ^ 0x8000, negative: ~b, +NaN -> 0 so that it never wins, as with the reference's '>'), and the running
-// maximum of a (bin, channel) is ONE u32  key << 16 | (0xFFFE - pixel): v_max_u32 then implements "larger value, else
-// earlier pixel" — 2 VALU instructions per channel and pixel instead of convert + compare + two selects.  The start
-// value key(-inf) << 16 | 0xFFFF can only be beaten by values > -inf, i.e. exactly those that beat -FLT_MAX.
-// (-0.0 shares +0.0's key, as they compare equal; a bin won by a -0.0 pixel then outputs +0.0.)
+// KEY = true (bf16 maps of < 65535 pixels): the LDS copy holds the 16-bit keys of the packed candidates (key16_of) instead of bf16
+// bits, and a window pixel costs 2 VALU instructions per channel instead of convert + compare + two selects.
 //
 // BAND = true (maps whose whole plane does not fit LDS with 16-byte pixels; KEY form only): a workgroup holds `band_rows`
-// consecutive map ROWS of all W columns instead of the whole plane, and the (ROI, bin row) pairs of its ROI chunk are dealt to the
-// band whose first `band_S` rows hold the bin's first window row; band_rows - band_S >= ceil(H / PH) + 1 rows of overlap hold the
-// rest of any window of a ROI that lies inside the image.  So large maps keep 8 channels per lane (the per-task cost outside the
+// consecutive map ROWS of all W columns instead of the whole plane (BandGeom), and works on the (ROI, bin row) pairs of its ROI chunk
+// that its band owns.  So large maps keep 8 channels per lane (the per-task cost outside the
 // scan and the scan's loop overhead are paid per slab: 150x200 map, 4000 ROIs: 4-byte slabs 1.76 ms) at the price of loading
 // each map row ~2x.  Window rows past the band (ROIs reaching far outside the image: their clipped bins can be as tall as the
 // map) are read from global memory by a cold loop.  The pairs owned by a band are compacted into an LDS list first.
@@ -409,20 +551,25 @@ template <typename T, int CB>
 __device__ __forceinline__ typename PixWord<CB * (int)sizeof(T)>::type pix_to_keys(typename PixWord<CB * (int)sizeof(T)>::type w) {
   unsigned int* u = (unsigned int*)&w;
 #pragma unroll
-  for (int i = 0; i < CB * (int)sizeof(T) / 4; ++i) {
-    unsigned int k = 0;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const unsigned int bts = (u[i] >> (16 * h)) & 0xFFFFu;
-      unsigned int key = (bts & 0x8000u) ? (bts ^ 0xFFFFu) : (bts | 0x8000u);
-      if (bts > 0x7F80u && bts < 0x8000u) key = 0;              // +NaN never wins
-      if (bts == 0x8000u) key = 0x8000u;                        // -0.0 == +0.0 under '>': the earlier pixel wins
-      k |= key << (16 * h);
-    }
-    u[i] = k;
-  }
+  for (int i = 0; i < CB * (int)sizeof(T) / 4; ++i) u[i] = key16_of(u[i] & 0xFFFFu) | (key16_of(u[i] >> 16) << 16);
   return w;
 }
+
+// Dynamic LDS of the plane kernel: built from the same arguments by the kernel (which takes its pointers from it) and by the
+// launchers (which take the byte count).  rows = 0 gives the bytes beside the pixels.
+struct PlaneLds {
+  size_t list, hb, wb, mul, task, bytes;
+  __host__ __device__ PlaneLds(int rows, int W, int pxb, int chunk, int PH, int PW, bool band) {
+    size_t o = ((size_t)rows * W * pxb + 15) & ~(size_t)15;          // [rows * W] pixels of pxb bytes (CB channels)
+    list = o; o += (size_t)chunk * 4;                                // [chunk] ROIs of this image
+    hb = o; o += (size_t)chunk * PH * 2;                             // [chunk][PH] bin row range  start | end << 8  (H, W <= 255)
+    wb = o; o += (size_t)chunk * PW * 2;                             // [chunk][PW] bin column range
+    mul = (o + 3) & ~(size_t)3; o += 4 + (size_t)chunk * 4;          // [chunk] output scale of the ROI (f32: 4 bytes to align it)
+    task = mul + (size_t)chunk * 4;                                  // BAND: [chunk * PH] owned (ROI << 8 | bin row)
+    if (band) o += (size_t)chunk * PH * 4;
+    bytes = o;
+  }
+};
 
 template <typename T, int CB, int NT, typename IT, bool KEY, bool BAND = false>
 __global__ __launch_bounds__(NT) void roi_pool_fwd_plane_kernel(int H, int W, int C, long ld, int PH, int PW, float scale,
@@ -436,20 +583,21 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_plane_kernel(int H, int W, in
   typedef typename PixWord<PXB>::type word_t;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int s_cnt, s_ntask;
+  const BandGeom bg{band_S, band_rows, n_bands, false};
   const int band = BAND ? (int)(blockIdx.z % n_bands) : 0, zfirst = BAND ? (int)(blockIdx.z / n_bands) : (int)blockIdx.z;
-  const int y0 = BAND ? band * band_S : 0, y1 = BAND ? min(H, y0 + band_rows) : H;      // map rows [y0, y1) live in LDS
-  const int lds_rows = BAND ? band_rows : H;
-  word_t* plane = (word_t*)smem;                                   // [rows*W] pixels x CB channels
-  int* s_list = (int*)(smem + (((size_t)lds_rows * W * PXB + 15) & ~(size_t)15));   // [chunk] ROIs of this image
-  unsigned short* s_hb = (unsigned short*)(s_list + chunk);        // [chunk][PH] bin row range  start | end << 8  (H, W <= 255)
-  unsigned short* s_wb = s_hb + chunk * PH;                        // [chunk][PW] bin column range
-  float* s_mul = (float*)(s_wb + chunk * PW + ((chunk * (PH + PW)) & 1));   // [chunk] output scale of the ROI (4-byte aligned)
-  unsigned int* s_task = (unsigned int*)(s_mul + chunk);           // BAND: [chunk * PH] owned (ROI << 8 | bin row)
+  const int y0 = BAND ? bg.y0(band, H) : 0, y1 = BAND ? bg.y1(band, H) : H;             // map rows [y0, y1) live in LDS
+  const PlaneLds lds(BAND ? band_rows : H, W, PXB, chunk, PH, PW, BAND);
+  word_t* plane = (word_t*)smem;
+  int* s_list = (int*)(smem + lds.list);
+  unsigned short* s_hb = (unsigned short*)(smem + lds.hb);
+  unsigned short* s_wb = (unsigned short*)(smem + lds.wb);
+  float* s_mul = (float*)(smem + lds.mul);
+  unsigned int* s_task = (unsigned int*)(smem + lds.task);
   const int c0 = xcd_grouped_slab() * CB, img = blockIdx.y;
   const int tid = threadIdx.x;
   const int npx = H * W;
   const T* fimg = feat + (long)img * npx * C + c0;
-  constexpr int NC1 = 7, NCLS = NC1 * NC1;
+  constexpr int NC1 = SP_NHC, NCLS = NC1 * NC1;
   __shared__ int s_hist[NCLS + 1];
   bool plane_loaded = false;
   // The workgroup keeps its slab (band) of the map and walks ROI chunks zfirst, zfirst + n_zsplit, ...: the slab is fetched once
@@ -469,8 +617,7 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_plane_kernel(int H, int W, in
   for (int r = r0 + tid; r < r1; r += NT)
     if ((int)rois[(long)r * 5] == img) {
       const RoiGeom g0 = roi_geom(rois + (long)r * 5, scale, PH, PW);
-      auto cls1 = [](float b) { return b < 1.f ? 0 : b < 2.f ? 1 : b < 3.f ? 2 : b < 4.f ? 3 : b < 6.f ? 4 : b < 8.f ? 5 : 6; };
-      my_cls = cls1(g0.bin_h) * NC1 + cls1(g0.bin_w);          // window ~ (ceil(bin_h) + 1) x (ceil(bin_w) + 1) pixels
+      my_cls = bin_size_class(g0.bin_h) * NC1 + bin_size_class(g0.bin_w);
       atomicAdd(&s_hist[my_cls + 1], 1);
       atomicAdd(&s_cnt, 1);
     }
@@ -490,41 +637,13 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_plane_kernel(int H, int W, in
     }
     __syncthreads();
   }
-  // bin ranges once per (ROI, bin row / column) instead of once per (ROI, bin, channel slab lane): the scan below is
-  // VALU-issue bound (rocprof: 31 VALU instructions per window pixel, a third of them this per-task geometry)
-  for (int i = tid; i < cnt * (PH + PW); i += NT) {
-    const int li = i / (PH + PW), k = i - li * (PH + PW);
-    const RoiGeom g = roi_geom(rois + (long)s_list[li] * 5, scale, PH, PW);
-    if (k == 0) s_mul[li] = row_scale ? (row_scale[s_list[li]] + row_scale_add) : 1.0f;
-    if (k < PH) {
-      int hs = (int)floorf(__fmul_rn((float)k, g.bin_h)), he = (int)ceilf(__fmul_rn((float)(k + 1), g.bin_h));
-      hs = min(max(hs + g.start_h, 0), H); he = min(max(he + g.start_h, 0), H);
-      s_hb[li * PH + k] = (unsigned short)(hs | (he << 8));
-    } else {
-      const int pw = k - PH;
-      int ws = (int)floorf(__fmul_rn((float)pw, g.bin_w)), we = (int)ceilf(__fmul_rn((float)(pw + 1), g.bin_w));
-      ws = min(max(ws + g.start_w, 0), W); we = min(max(we + g.start_w, 0), W);
-      s_wb[li * PW + pw] = (unsigned short)(ws | (we << 8));
-    }
-  }
+  fill_bin_tables<NT, false>(cnt, PH, PW, H, W, scale, rois, row_scale, row_scale_add, [&](int li) { return s_list[li]; }, s_hb, s_wb,
+                             s_mul, (int*)nullptr);
   __syncthreads();
   const int nb = PH * PW;
-  constexpr unsigned KEY_INIT = 0x007FFFFFu;                       // key(-inf) << 16 | 0xFFFF
   int ntask = cnt * PH;                                            // (ROI, bin row) pairs this workgroup works on
   if (BAND) {
-    // the pairs whose first window row falls into this band's first band_S rows, compacted (order inside a wave kept: the size
-    // classes stay together; across waves it is whatever order the counter was reached in — the results do not depend on it)
-    const int lane = tid & 63;
-    for (int e0 = 0; e0 < cnt * PH; e0 += NT) {
-      const int e = e0 + tid;
-      bool mine = false;
-      if (e < cnt * PH) mine = min((int)(s_hb[e] & 0xFF) / band_S, n_bands - 1) == band;
-      const unsigned long long m = __ballot(mine);
-      int base = 0;
-      if (lane == 0 && m) base = atomicAdd(&s_ntask, __popcll(m));
-      base = __shfl(base, 0);
-      if (mine) { const int li_ = e / PH; s_task[base + __popcll(m & ((1ull << lane) - 1))] = (unsigned)(li_ << 8) | (unsigned)(e - li_ * PH); }
-    }
+    compact_owned_pairs<NT>(cnt * PH, PH, s_hb, bg, band, s_task, &s_ntask);
     __syncthreads();
     ntask = s_ntask;
   }
@@ -586,23 +705,7 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_plane_kernel(int H, int W, in
             }
         }
       }
-      // key -> bf16 bits: positive values (key bit 15 set) flip that bit back, negative ones were stored complemented; the pixel
-      // index 0xFFFE - low half is -1 by itself when nothing won (low half still 0xFFFF).  best never drops below KEY_INIT, and a
-      // channel still AT it (empty bin, or a window of -inf / NaN only) is the one case the reference answers differently
-      // (0 resp. -FLT_MAX): one min over the channels finds it, so the common path pays no per-channel selects
-      unsigned int lowest = best[0];
-#pragma unroll
-      for (int q = 0; q < CB; ++q) {
-        const unsigned int m = (unsigned int)((int)best[q] >> 31);
-        mv[q] = __uint_as_float((best[q] & 0xFFFF0000u) ^ (0x80000000u | (~m & 0x7FFF0000u)));
-        mi[q] = (int)(0xFFFEu - (best[q] & 0xFFFFu));
-        lowest = min(lowest, best[q]);
-      }
-      if (lowest == KEY_INIT) {
-#pragma unroll
-        for (int q = 0; q < CB; ++q)
-          if (best[q] == KEY_INIT) mv[q] = empty ? 0.f : -FLT_MAX;
-      }
+      decode_candidates<CB>(best, empty, mv, mi);
     } else {
 #pragma unroll
       for (int q = 0; q < CB; ++q) { mv[q] = empty ? 0.f : -FLT_MAX; mi[q] = -1; }
@@ -621,17 +724,7 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_plane_kernel(int H, int W, in
         }
       }
     }
-    // 2 x CB two-byte stores per task (a 64-lane wave writes one contiguous 98-byte run per channel and ROI): measured 45 us of the
-    // 260 us a 4000-ROI call takes (stores compiled out: 215 us), the rest is the scan's VALU issue — staging the rows through LDS
-    // for 16-byte stores would need 31 KiB more LDS and drop 63x63 maps to one workgroup per CU (measured with padded LDS: +10 %),
-    // so the stores stay direct
-    const float mul = s_mul[li];
-    const long o = (long)r * ld + (long)c0 * nb + b;
-#pragma unroll
-    for (int q = 0; q < CB; ++q) {
-      Elem<T>::store(out + o + (long)q * nb, __fmul_rn(mv[q], mul));        // (nontemporal 2-byte stores: 250 -> 415 us, they are
-      argmax[o + (long)q * nb] = ArgIdx<IT>::enc(mi[q]);                    //  not merged into full lines on the way out)
-    }
+    store_task<T, IT, CB>(out, argmax, (long)r * ld + (long)c0 * nb + b, nb, mv, mi, s_mul[li]);
     if (BAND) {
       pw += dtw; te += dte;
       if (pw >= PW) { pw -= PW; ++te; }
@@ -665,16 +758,160 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_plane_kernel(int H, int W, in
 // window ROW instead of ~31 per pixel PAIR; what remains is the per-task work outside the scan (16 two-byte stores, key -> value ->
 // x prior -> bf16).
 // CB = 8: two 16-byte planes (channels 0-3 | 4-7) = 32 B per pixel, the whole map in LDS (<= ~4600 pixels: 63x63);
-// CB = 4 + BAND: one plane, row bands with a halo as in the scan form above (large maps: 99x165 -> 3 bands), rows below a band from
-// global memory.
-constexpr int SP_NT = 1024, SP_CH = 128, SP_NLEV = 6, SP_NHC = 7, SP_NCLS = SP_NLEV * SP_NHC;
+// CB = 4 + BAND: one plane, row bands with a halo (BandGeom; large maps: 99x165 -> 3 bands), rows below a band from global memory.
 
-__device__ __forceinline__ unsigned int key16_of(unsigned int bts) {          // pix_to_keys for one bf16 value
-  unsigned int key = (bts & 0x8000u) ? (bts ^ 0xFFFFu) : (bts | 0x8000u);
-  if (bts > 0x7F80u && bts < 0x8000u) key = 0;                                // +NaN never wins
-  if (bts == 0x8000u) key = 0x8000u;                                          // -0.0 == +0.0 under '>'
-  return key;
+// ---- the pieces the sparse-table kernel and the prepared-task kernel share: ONE definition of the table's arithmetic, so the two
+// forms' results are identical bit for bit by construction.  tab: [CB / 4][npl_px] entries of 4 channels' candidates.
+
+// the raw words of one pixel's CB bf16 channels
+template <int CB>
+__device__ __forceinline__ void load_pixel_words(const unsigned short* __restrict__ p, unsigned int (&u)[CB / 2]) {
+  if constexpr (CB == 8) { const u32x4 w = *(const u32x4*)p; u[0] = w[0]; u[1] = w[1]; u[2] = w[2]; u[3] = w[3]; }
+  else { const u32x2 w = *(const u32x2*)p; u[0] = w[0]; u[1] = w[1]; }
 }
+
+// level 0: the candidates of table pixel px (inv = 0xFFFE - its map pixel) from its raw words
+template <int CB>
+__device__ __forceinline__ void store_level0(u32x4* tab, int npl_px, int px, unsigned int inv, const unsigned int (&u)[CB / 2]) {
+#pragma unroll
+  for (int pl = 0; pl < CB / 4; ++pl) {
+    u32x4 t;
+    t[0] = (key16_of(u[2 * pl] & 0xFFFFu) << 16) | inv;     t[1] = (key16_of(u[2 * pl] >> 16) << 16) | inv;
+    t[2] = (key16_of(u[2 * pl + 1] & 0xFFFFu) << 16) | inv; t[3] = (key16_of(u[2 * pl + 1] >> 16) << 16) | inv;
+    tab[pl * npl_px + px] = t;
+  }
+}
+
+struct BlockBarrier { __device__ __forceinline__ void operator()() const { __syncthreads(); } };
+// A barrier that orders LDS traffic only.  __syncthreads() also waits for vmcnt(0), i.e. for every output store the wave still has in
+// flight — the phase clocks showed a wave of the prepared-task kernel parked at the level barriers for 26 % of a workgroup's cycles on
+// the 99x165 map (most of it turned out to be the spread of the units' lengths, see the claims there; the stores' share is what this
+// form removes)
+struct LdsBarrier { __device__ __forceinline__ void operator()() const { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); } };
+
+// T_L from T_{L-1} (L >= 1), in place: every thread reads its pixels' two spans (thread t owns table pixels t + k * NT, in column
+// xk[k]), barrier, writes, barrier
+template <int NPL, int PXT, int NT, typename Barrier>
+__device__ __forceinline__ void advance_level(u32x4* tab, int npl_px, int npx_t, int W, int L, const int (&xk)[PXT], Barrier barrier) {
+  const int tid = threadIdx.x;
+  const int d = 1 << (L - 1);
+  u32x4 nv[PXT][NPL];
+#pragma unroll
+  for (int k = 0; k < PXT; ++k) {
+    const int px = tid + k * NT;
+    if (px < npx_t) {
+      const bool two = xk[k] + d < W;                               // the second span starts inside the row
+#pragma unroll
+      for (int pl = 0; pl < NPL; ++pl) {
+        const u32x4 a = tab[pl * npl_px + px];
+        const u32x4 b = two ? tab[pl * npl_px + px + d] : a;
+        nv[k][pl] = u32x4{max(a[0], b[0]), max(a[1], b[1]), max(a[2], b[2]), max(a[3], b[3])};
+      }
+    }
+  }
+  barrier();
+#pragma unroll
+  for (int k = 0; k < PXT; ++k) {
+    const int px = tid + k * NT;
+    if (px < npx_t) {
+#pragma unroll
+      for (int pl = 0; pl < NPL; ++pl) tab[pl * npl_px + px] = nv[k][pl];
+    }
+  }
+  barrier();
+}
+
+// One (task, bin column) item: the best candidates of window rows [hs, he) x columns [ws, we) over the level-L table (span = 2^L) of
+// map rows [y0, y1).  Returns whether the bin is empty.
+template <int CB, bool BAND>
+__device__ __forceinline__ bool scan_window(unsigned int (&best)[CB], const u32x4* tab, int npl_px, const unsigned short* __restrict__ fimg,
+                                            int C, int W, int y0, int y1, int span, int hs, int he, int ws, int we) {
+  constexpr int NPL = CB / 4;
+  const bool empty = (he <= hs) || (we <= ws);
+#pragma unroll
+  for (int q = 0; q < CB; ++q) best[q] = KEY_INIT;
+  if (!empty) {
+    const int bw = we - ws;
+    const int he_lds = BAND ? min(he, y1) : he;
+    int cold_from = BAND ? max(hs, y1) : he;                        // first window row read from global memory
+    if (bw >= span) {
+      const int offB = bw - span;
+      // two window rows per step (the second clamped to the last row: re-reading a row cannot change a maximum): all 4 * NPL
+      // reads of a step are issued before the first use — one LDS round trip per row PAIR instead of per row (rocprof, one row
+      // per step: the waves of this kernel were parked at s_waitcnt / barriers 53 % of their time, VALU and LDS both < 50 % busy)
+      const int last = (he_lds - 1 - y0) * W + ws;
+      for (int hh = hs; hh < he_lds; hh += 2) {
+        const int i0 = (hh - y0) * W + ws, i1 = min(i0 + W, last);
+        u32x4 a0[NPL], b0[NPL], a1[NPL], b1[NPL];
+#pragma unroll
+        for (int pl = 0; pl < NPL; ++pl) {
+          a0[pl] = tab[pl * npl_px + i0]; b0[pl] = tab[pl * npl_px + i0 + offB];
+          a1[pl] = tab[pl * npl_px + i1]; b1[pl] = tab[pl * npl_px + i1 + offB];
+        }
+#pragma unroll
+        for (int pl = 0; pl < NPL; ++pl)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            best[4 * pl + e] = max(max(max(max(best[4 * pl + e], a0[pl][e]), b0[pl][e]), a1[pl][e]), b1[pl][e]);     // 2 x v_max3_u32
+        if (2 * span < bw) {                                        // only when the level was capped (SP_NLEV): spans in between
+          for (int rr = 0; rr < 2; ++rr) {
+            const int ib = rr ? i1 : i0;
+            for (int x = span; x < offB; x += span) {
+#pragma unroll
+              for (int pl = 0; pl < NPL; ++pl) {
+                const u32x4 a = tab[pl * npl_px + ib + x];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) best[4 * pl + e] = max(best[4 * pl + e], a[e]);
+              }
+            }
+          }
+        }
+      }
+    } else if (we == W) {                                           // clipped by the map's right edge: the span at ws ends at W
+      for (int hh = hs; hh < he_lds; ++hh) {
+        const int i0 = (hh - y0) * W + ws;
+#pragma unroll
+        for (int pl = 0; pl < NPL; ++pl) {
+          const u32x4 a = tab[pl * npl_px + i0];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) best[4 * pl + e] = max(best[4 * pl + e], a[e]);
+        }
+      }
+    } else {
+      cold_from = hs;                                               // narrower than the ROI's span for another reason: pixel loop
+    }
+    for (int hh = cold_from; hh < he; ++hh)
+      for (int x = ws; x < we; ++x) {
+        const int gi = hh * W + x;
+        const unsigned int inv0 = 0xFFFEu - (unsigned)gi;
+        unsigned int u[CB / 2];
+        load_pixel_words<CB>(fimg + (long)gi * C, u);
+#pragma unroll
+        for (int i = 0; i < CB / 2; ++i) {
+          best[2 * i] = max(best[2 * i], (key16_of(u[i] & 0xFFFFu) << 16) | inv0);
+          best[2 * i + 1] = max(best[2 * i + 1], (key16_of(u[i] >> 16) << 16) | inv0);
+        }
+      }
+  }
+  return empty;
+}
+
+// Dynamic LDS of the sparse-table kernel: table planes + the image's sorted ROI list + one chunk's tables; built from the same
+// arguments by the kernel (pointers) and its launcher (bytes).  table_bytes = 0 gives the bytes beside the table.
+struct SparseLds {
+  size_t lvl, r, mul, hb, wb, task, bytes;
+  __host__ __device__ SparseLds(size_t table_bytes, int R, int chunk, int PH, int PW, bool band) {
+    size_t o = table_bytes;                                         // [CB / 4][pixels] u32x4
+    lvl = o; o += (size_t)((R + 1) & ~1) * 2;                       // [R] u16: ROI rows of this image, by class
+    r = o; o += (size_t)chunk * 4;                                  // [chunk] ROI row of the chunk's entries
+    mul = o; o += (size_t)chunk * 4;                                // [chunk] output scale
+    hb = o; o += (size_t)chunk * PH * 2;                            // [chunk][PH] bin row range  start | end << 8
+    wb = o; o += (size_t)chunk * PW * 2;                            // [chunk][PW]
+    task = (o + 3) & ~(size_t)3; o += 4;                            // BAND: [chunk * PH] owned (entry << 8 | bin row)
+    if (band) o += (size_t)chunk * PH * 4;
+    bytes = o + 16;                                                 // + alignment of the dynamic segment
+  }
+};
 
 template <typename IT, int CB, bool BAND, int PFIX = 0>
 __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W, int C, long ld, int PH_, int PW_, float scale,
@@ -692,38 +929,26 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int s_start[SP_NCLS + 1], s_fill[SP_NCLS];
   __shared__ int s_ntask, s_claim;
+  const BandGeom bg{band_S, band_rows, n_bands, false};
   const int band = BAND ? (int)(blockIdx.z % n_bands) : 0, zfirst = BAND ? (int)(blockIdx.z / n_bands) : (int)blockIdx.z;
-  const int y0 = BAND ? band * band_S : 0, y1 = BAND ? min(H, y0 + band_rows) : H;      // map rows [y0, y1) live in LDS
-  const int lds_rows = BAND ? band_rows : H;
-  const int npl_px = lds_rows * W;                                  // pixels per plane (allocated)
+  const int y0 = BAND ? bg.y0(band, H) : 0, y1 = BAND ? bg.y1(band, H) : H;             // map rows [y0, y1) live in LDS
+  const int npl_px = (BAND ? band_rows : H) * W;                    // pixels per plane (allocated)
   const int npx_t = (y1 - y0) * W;                                  // pixels held
+  const SparseLds lds((size_t)NPL * npl_px * 16, R, SP_CHK, PH, PW, BAND);
   u32x4* tab = (u32x4*)smem;                                        // [NPL][npl_px]
-  unsigned short* s_lvl = (unsigned short*)(smem + (size_t)NPL * npl_px * 16);          // [R] ROI rows of this image, by class
-  const int r_even = (R + 1) & ~1;
-  int* s_r = (int*)(s_lvl + r_even);                                // [CH] ROI row of the chunk's entries
-  float* s_mul = (float*)(s_r + SP_CHK);                            // [CH] output scale
-  unsigned short* s_hb = (unsigned short*)(s_mul + SP_CHK);         // [CH][PH] bin row range  start | end << 8
-  unsigned short* s_wb = s_hb + SP_CHK * PH;                        // [CH][PW]
-  unsigned int* s_task = (unsigned int*)(s_wb + SP_CHK * PW + ((SP_CHK * (PH + PW)) & 1));   // BAND: [CH * PH] owned (entry << 8 | bin row)
+  unsigned short* s_lvl = (unsigned short*)(smem + lds.lvl);
+  int* s_r = (int*)(smem + lds.r);
+  float* s_mul = (float*)(smem + lds.mul);
+  unsigned short* s_hb = (unsigned short*)(smem + lds.hb);
+  unsigned short* s_wb = (unsigned short*)(smem + lds.wb);
+  unsigned int* s_task = (unsigned int*)(smem + lds.task);
   const int c0 = xcd_grouped_slab() * CB, img = blockIdx.y;
   const int tid = threadIdx.x;
   const int nb = PH * PW;
   const unsigned short* fimg = feat + (long)img * H * W * C + c0;
 
   // ---- 1. this image's ROIs sorted by (level, height class): counting sort, two passes over the ROI geometry
-  auto roi_class = [&](int r) {
-    const RoiGeom g = roi_geom(rois + (long)r * 5, scale, PH, PW);
-    int m = 1 << 30;                                                // narrowest UNCLIPPED window of the ROI
-    for (int pw = 0; pw < PW; ++pw) {
-      const int ws = (int)floorf(__fmul_rn((float)pw, g.bin_w)), we = (int)ceilf(__fmul_rn((float)(pw + 1), g.bin_w));
-      m = min(m, we - ws);
-    }
-    m = max(m, 1);
-    const int L = min(31 - __clz(m), SP_NLEV - 1);
-    const float b = g.bin_h;
-    const int hc = b < 1.f ? 0 : b < 2.f ? 1 : b < 3.f ? 2 : b < 4.f ? 3 : b < 6.f ? 4 : b < 8.f ? 5 : 6;
-    return L * SP_NHC + hc;
-  };
+  auto roi_class = [&](int r) { return roi_level_class(roi_geom(rois + (long)r * 5, scale, PH, PW), PW); };
   // The n_zsplit workgroups of one (slab, image, band) split the ROIs by ROW BLOCK (128 consecutive rows of `rois` each, dealt
   // round-robin), not by position in the sorted list: the order inside a class is whatever the atomics give, so a list position means
   // something to the workgroup that built the list only.  BAND: only ROIs with a bin row that STARTS in this band's own rows enter
@@ -736,8 +961,8 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
         if (BAND) {
           const RoiGeom g = roi_geom(rois + (long)r * 5, scale, PH, PW);
           const int h_first = min(max(g.start_h, 0), H);
-          const int h_last = min(max((int)floorf(__fmul_rn((float)(PH - 1), g.bin_h)) + g.start_h, 0), H);
-          if (min(h_first / band_S, n_bands - 1) > band || min(h_last / band_S, n_bands - 1) < band) continue;
+          const int h_last = bin_rows(g, PH - 1, H).s;
+          if (bg.owner(h_first) > band || bg.owner(h_last) < band) continue;
         }
         fn(r);
       }
@@ -763,87 +988,27 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
     xk[k] = px < npx_t ? px - (px / W) * W : -1;
     if (px < npx_t) {
       const int gpx = y0 * W + px;
-      const unsigned int inv = 0xFFFEu - (unsigned)gpx;
       unsigned int u[CB / 2];
-      if (CB == 8) { const u32x4 w = *(const u32x4*)(fimg + (long)gpx * C); u[0] = w[0]; u[1] = w[1]; u[2] = w[2]; u[3] = w[3]; }
-      else { const u32x2 w = *(const u32x2*)(fimg + (long)gpx * C); u[0] = w[0]; u[1] = w[1]; }
-#pragma unroll
-      for (int pl = 0; pl < NPL; ++pl) {
-        u32x4 t;
-        t[0] = (key16_of(u[2 * pl] & 0xFFFFu) << 16) | inv;     t[1] = (key16_of(u[2 * pl] >> 16) << 16) | inv;
-        t[2] = (key16_of(u[2 * pl + 1] & 0xFFFFu) << 16) | inv; t[3] = (key16_of(u[2 * pl + 1] >> 16) << 16) | inv;
-        tab[pl * npl_px + px] = t;
-      }
+      load_pixel_words<CB>(fimg + (long)gpx * C, u);
+      store_level0<CB>(tab, npl_px, px, 0xFFFEu - (unsigned)gpx, u);
     }
   }
-  constexpr unsigned KEY_INIT = 0x007FFFFFu;                        // key(-inf) << 16 | 0xFFFF
   for (int L = 0; L < SP_NLEV; ++L) {
     const int c_lo = s_start[L * SP_NHC], c_hi = s_start[(L + 1) * SP_NHC];
     if (c_lo >= n_rois) break;                                      // no ROI at this or a higher level
     __syncthreads();                                                // level L - 1 fully scanned (L = 0: table and list written)
-    if (L > 0) {
-      // ---- 3. T_L from T_{L-1}, in place: every thread reads its pixels' two spans, barrier, writes
-      const int d = 1 << (L - 1);
-      u32x4 nv[PXT][NPL];
-#pragma unroll
-      for (int k = 0; k < PXT; ++k) {
-        const int px = tid + k * NT;
-        if (px < npx_t) {
-          const bool two = xk[k] + d < W;                           // the second span starts inside the row
-#pragma unroll
-          for (int pl = 0; pl < NPL; ++pl) {
-            const u32x4 a = tab[pl * npl_px + px];
-            const u32x4 b = two ? tab[pl * npl_px + px + d] : a;
-            nv[k][pl] = u32x4{max(a[0], b[0]), max(a[1], b[1]), max(a[2], b[2]), max(a[3], b[3])};
-          }
-        }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < PXT; ++k) {
-        const int px = tid + k * NT;
-        if (px < npx_t) {
-#pragma unroll
-          for (int pl = 0; pl < NPL; ++pl) tab[pl * npl_px + px] = nv[k][pl];
-        }
-      }
-      __syncthreads();
-    }
+    if (L > 0) advance_level<NPL, PXT, NT>(tab, npl_px, npx_t, W, L, xk, BlockBarrier());      // ---- 3. T_L from T_{L-1}
     const int span = 1 << L;
     for (int cs = c_lo; cs < c_hi; cs += SP_CHK) {
       const int cnt = min(SP_CHK, c_hi - cs);
       __syncthreads();                                              // the previous chunk's tables are no longer read
       if (tid == 0) { s_ntask = 0; s_claim = 0; }
-      for (int i = tid; i < cnt * (PH + PW); i += NT) {
-        const int li = i / (PH + PW), k = i - li * (PH + PW);
-        const int r = s_lvl[cs + li];
-        const RoiGeom g = roi_geom(rois + (long)r * 5, scale, PH, PW);
-        if (k == 0) { s_r[li] = r; s_mul[li] = row_scale ? (row_scale[r] + row_scale_add) : 1.0f; }
-        if (k < PH) {
-          int hs = (int)floorf(__fmul_rn((float)k, g.bin_h)), he = (int)ceilf(__fmul_rn((float)(k + 1), g.bin_h));
-          hs = min(max(hs + g.start_h, 0), H); he = min(max(he + g.start_h, 0), H);
-          s_hb[li * PH + k] = (unsigned short)(hs | (he << 8));
-        } else {
-          const int pw = k - PH;
-          int ws = (int)floorf(__fmul_rn((float)pw, g.bin_w)), we = (int)ceilf(__fmul_rn((float)(pw + 1), g.bin_w));
-          ws = min(max(ws + g.start_w, 0), W); we = min(max(we + g.start_w, 0), W);
-          s_wb[li * PW + pw] = (unsigned short)(ws | (we << 8));
-        }
-      }
+      fill_bin_tables<NT, true>(cnt, PH, PW, H, W, scale, rois, row_scale, row_scale_add, [&](int li) { return (int)s_lvl[cs + li]; }, s_hb,
+                                s_wb, s_mul, s_r);
       __syncthreads();
       int ntask = cnt * PH;                                         // (ROI, bin row) pairs this workgroup works on
       if (BAND) {
-        const int lane = tid & 63;
-        for (int e0 = 0; e0 < cnt * PH; e0 += NT) {
-          const int e = e0 + tid;
-          bool mine = false;
-          if (e < cnt * PH) mine = min((int)(s_hb[e] & 0xFF) / band_S, n_bands - 1) == band;
-          const unsigned long long mk = __ballot(mine);
-          int base = 0;
-          if (lane == 0 && mk) base = atomicAdd(&s_ntask, __popcll(mk));
-          base = __shfl(base, 0);
-          if (mine) { const int li_ = e / PH; s_task[base + __popcll(mk & ((1ull << lane) - 1))] = (unsigned)(li_ << 8) | (unsigned)(e - li_ * PH); }
-        }
+        compact_owned_pairs<NT>(cnt * PH, PH, s_hb, bg, band, s_task, &s_ntask);
         __syncthreads();
         ntask = s_ntask;
       }
@@ -862,97 +1027,11 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
         const int b = ph * PW + pw;
         const int r = s_r[li];
         const int hb = s_hb[li * PH + ph], wb = s_wb[li * PW + pw];
-        const int hs = hb & 0xFF, he = hb >> 8, ws = wb & 0xFF, we = wb >> 8;
-        const bool empty = (he <= hs) || (we <= ws);
         unsigned int best[CB];
-#pragma unroll
-        for (int q = 0; q < CB; ++q) best[q] = KEY_INIT;
-        if (!empty) {
-          const int bw = we - ws;
-          const int he_lds = BAND ? min(he, y1) : he;
-          int cold_from = BAND ? max(hs, y1) : he;                  // first window row read from global memory
-          if (bw >= span) {
-            const int offB = bw - span;
-            // two window rows per step (the second clamped to the last row: re-reading a row cannot change a maximum): all 4 * NPL
-            // reads of a step are issued before the first use — one LDS round trip per row PAIR instead of per row (rocprof, one row
-            // per step: the waves of this kernel were parked at s_waitcnt / barriers 53 % of their time, VALU and LDS both < 50 % busy)
-            const int last = (he_lds - 1 - y0) * W + ws;
-            for (int hh = hs; hh < he_lds; hh += 2) {
-              const int i0 = (hh - y0) * W + ws, i1 = min(i0 + W, last);
-              u32x4 a0[NPL], b0[NPL], a1[NPL], b1[NPL];
-#pragma unroll
-              for (int pl = 0; pl < NPL; ++pl) {
-                a0[pl] = tab[pl * npl_px + i0]; b0[pl] = tab[pl * npl_px + i0 + offB];
-                a1[pl] = tab[pl * npl_px + i1]; b1[pl] = tab[pl * npl_px + i1 + offB];
-              }
-#pragma unroll
-              for (int pl = 0; pl < NPL; ++pl)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                  best[4 * pl + e] = max(max(max(max(best[4 * pl + e], a0[pl][e]), b0[pl][e]), a1[pl][e]), b1[pl][e]);     // 2 x v_max3_u32
-              if (2 * span < bw) {                                  // only when the level was capped (SP_NLEV): spans in between
-                for (int rr = 0; rr < 2; ++rr) {
-                  const int ib = rr ? i1 : i0;
-                  for (int x = span; x < offB; x += span) {
-#pragma unroll
-                    for (int pl = 0; pl < NPL; ++pl) {
-                      const u32x4 a = tab[pl * npl_px + ib + x];
-#pragma unroll
-                      for (int e = 0; e < 4; ++e) best[4 * pl + e] = max(best[4 * pl + e], a[e]);
-                    }
-                  }
-                }
-              }
-            }
-          } else if (we == W) {                                     // clipped by the map's right edge: the span at ws ends at W
-            for (int hh = hs; hh < he_lds; ++hh) {
-              const int i0 = (hh - y0) * W + ws;
-#pragma unroll
-              for (int pl = 0; pl < NPL; ++pl) {
-                const u32x4 a = tab[pl * npl_px + i0];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) best[4 * pl + e] = max(best[4 * pl + e], a[e]);
-              }
-            }
-          } else {
-            cold_from = hs;                                         // narrower than the ROI's span for another reason: pixel loop
-          }
-          for (int hh = cold_from; hh < he; ++hh)
-            for (int x = ws; x < we; ++x) {
-              const int gi = hh * W + x;
-              const unsigned int inv0 = 0xFFFEu - (unsigned)gi;
-              unsigned int u[CB / 2];
-              if (CB == 8) { const u32x4 w = *(const u32x4*)(fimg + (long)gi * C); u[0] = w[0]; u[1] = w[1]; u[2] = w[2]; u[3] = w[3]; }
-              else { const u32x2 w = *(const u32x2*)(fimg + (long)gi * C); u[0] = w[0]; u[1] = w[1]; }
-#pragma unroll
-              for (int i = 0; i < CB / 2; ++i) {
-                best[2 * i] = max(best[2 * i], (key16_of(u[i] & 0xFFFFu) << 16) | inv0);
-                best[2 * i + 1] = max(best[2 * i + 1], (key16_of(u[i] >> 16) << 16) | inv0);
-              }
-            }
-        }
-        // candidate -> (bf16 bits, pixel): as in the scan form above
+        const bool empty = scan_window<CB, BAND>(best, tab, npl_px, fimg, C, W, y0, y1, span, hb & 0xFF, hb >> 8, wb & 0xFF, wb >> 8);
         float mv[CB]; int mi[CB];
-        unsigned int lowest = best[0];
-#pragma unroll
-        for (int q = 0; q < CB; ++q) {
-          const unsigned int m = (unsigned int)((int)best[q] >> 31);
-          mv[q] = __uint_as_float((best[q] & 0xFFFF0000u) ^ (0x80000000u | (~m & 0x7FFF0000u)));
-          mi[q] = (int)(0xFFFEu - (best[q] & 0xFFFFu));
-          lowest = min(lowest, best[q]);
-        }
-        if (lowest == KEY_INIT) {
-#pragma unroll
-          for (int q = 0; q < CB; ++q)
-            if (best[q] == KEY_INIT) mv[q] = empty ? 0.f : -FLT_MAX;
-        }
-        const float mul = s_mul[li];
-        const long o = (long)r * ld + (long)c0 * nb + b;
-#pragma unroll
-        for (int q = 0; q < CB; ++q) {
-          Elem<unsigned short>::store(out + o + (long)q * nb, __fmul_rn(mv[q], mul));
-          argmax[o + (long)q * nb] = ArgIdx<IT>::enc(mi[q]);
-        }
+        decode_candidates<CB>(best, empty, mv, mi);
+        store_task<unsigned short, IT, CB>(out, argmax, (long)r * ld + (long)c0 * nb + b, nb, mv, mi, s_mul[li]);
       }
     }   // chunks of the level
   }     // levels
@@ -969,23 +1048,10 @@ __global__ __launch_bounds__(SP_NT) void roi_pool_fwd_sparse_kernel(int H, int W
 // filed under (image, row band of its first window row, class = level x window-height class) — a counting sort in ONE workgroup
 // per image.  The pooling kernel then only builds its table and walks the levels; at each level its lanes stream the (task, bin
 // column) items of that level straight from the list (records of the next item requested before the current one is scanned):
-// no chunks, no per-chunk barriers, one barrier per level.  Arithmetic, table and scan are the sparse kernel's, results
-// identical bit for bit.
+// no chunks, no per-chunk barriers, one barrier per level.  Class rule, table and scan are the shared pieces above: the results
+// are the sparse kernel's bit for bit.
 constexpr int TK_MAXB = 16;                                         // row bands per map at most (4 bits in RoiGeo::bands)
 constexpr int TK_SEG = SP_NCLS + 1;                                 // offsets per (image, band)
-
-__device__ __forceinline__ int tk_roi_class(const RoiGeom& g, int PW) {
-  int m = 1 << 30;                                                  // narrowest UNCLIPPED window of the ROI
-  for (int pw = 0; pw < PW; ++pw) {
-    const int ws = (int)floorf(__fmul_rn((float)pw, g.bin_w)), we = (int)ceilf(__fmul_rn((float)(pw + 1), g.bin_w));
-    m = min(m, we - ws);
-  }
-  m = max(m, 1);
-  const int L = min(31 - __clz(m), SP_NLEV - 1);
-  const float b = g.bin_h;
-  const int hc = b < 1.f ? 0 : b < 2.f ? 1 : b < 3.f ? 2 : b < 4.f ? 3 : b < 6.f ? 4 : b < 8.f ? 5 : 6;
-  return L * SP_NHC + hc;
-}
 
 // The list is built by two small launches, 256 ROIs per workgroup, thread = ROI (one workgroup per image took 25 us per 4000 ROIs,
 // all of it the ROI geometry on four SIMDs):
@@ -1017,32 +1083,28 @@ __global__ __launch_bounds__(TK_PREP_NT) void roi_pool_geo_kernel(int nimg, int 
     for (int k = 0; k < 4; ++k) { o.hb[k] = 0u; o.wb[k] = 0u; }
     o.mul = row_scale ? (row_scale[r] + row_scale_add) : 1.0f;
     if (img >= 0 && img < nimg) {
-      o.cell0 = img * n_bands * SP_NCLS + tk_roi_class(g, PW);
-      for (int pw = 0; pw < PW; ++pw) {
-        int ws = (int)floorf(__fmul_rn((float)pw, g.bin_w)), we = (int)ceilf(__fmul_rn((float)(pw + 1), g.bin_w));
-        ws = min(max(ws + g.start_w, 0), W); we = min(max(we + g.start_w, 0), W);
-        o.wb[pw >> 1] |= (unsigned)(ws | (we << 8)) << (16 * (pw & 1));
-      }
+      o.cell0 = img * n_bands * SP_NCLS + roi_level_class(g, PW);
+      for (int pw = 0; pw < PW; ++pw) o.wb[pw >> 1] |= bin_cols(g, pw, W).packed() << (16 * (pw & 1));
       int row_lo = H, row_hi = 0;                                   // map rows any non-empty bin of the ROI reads
       for (int ph = 0; ph < PH; ++ph) {
-        int hs = (int)floorf(__fmul_rn((float)ph, g.bin_h)), he = (int)ceilf(__fmul_rn((float)(ph + 1), g.bin_h));
-        hs = min(max(hs + g.start_h, 0), H); he = min(max(he + g.start_h, 0), H);
-        o.hb[ph >> 1] |= (unsigned)(hs | (he << 8)) << (16 * (ph & 1));
-        if (he > hs) { row_lo = min(row_lo, hs); row_hi = max(row_hi, he); }
+        const BinRange rh = bin_rows(g, ph, H);
+        o.hb[ph >> 1] |= rh.packed() << (16 * (ph & 1));
+        if (rh.e > rh.s) { row_lo = min(row_lo, rh.s); row_hi = max(row_hi, rh.e); }
       }
       // A ROI whose rows all lie inside ONE band's rows goes there whole: its 7 x 7 outputs per channel are then written by one
       // workgroup as one 98-byte run, as on a map that fits LDS.  Bin rows of the other ROIs go to the band that owns the bin's first
       // row (the 14-byte pieces of a channel's run then come from up to n_bands workgroups at different times: the partly written
       // lines leave the L2 in between — 99x165 map / 8000 ROIs: 235 us of the call, tools/roi_tasks_forms.py with ROI_MAXH).
+      const BandGeom bg{band_S, band_rows, n_bands, true};
       int whole = -1;
       for (int b = 0; b < n_bands && whole < 0; ++b) {
-        const int y0 = min(b * band_S, max(0, H - band_rows));
+        const int y0 = bg.y0(b, H);
         if (row_lo >= row_hi || (row_lo >= y0 && row_hi <= y0 + band_rows)) whole = b;
       }
       int prev = -1, run = 0;
       for (int ph = 0; ph < PH; ++ph) {
         const int hs = (int)((o.hb[ph >> 1] >> (16 * (ph & 1))) & 0xFFu);
-        const int b = whole >= 0 ? whole : min(hs / band_S, n_bands - 1);                // (non-decreasing in ph)
+        const int b = whole >= 0 ? whole : bg.owner(hs);                                 // (non-decreasing in ph)
         o.bands |= (unsigned)b << (4 * ph);
         if (b != prev) { if (run) atomicAdd(&s_cnt[o.cell0 + prev * SP_NCLS], run); prev = b; run = 0; }
         ++run;
@@ -1108,6 +1170,18 @@ __global__ __launch_bounds__(TK_PREP_NT) void roi_pool_tasks_kernel(int nimg, in
   }
 }
 
+// Dynamic LDS of the prepared-task kernel: the table of 16-byte pixels, then every wave's ring of two record slots; built from the same
+// arguments by the kernel and its launcher.  rows = 0 gives the bytes beside the table.
+struct TasksLds {
+  int n_rec, slot;                                                  // records a wave's 64 consecutive items can touch, bytes of a slot
+  size_t ring, bytes;
+  __host__ __device__ TasksLds(int rows, int W, int PW, int n_waves) {
+    n_rec = (62 + PW) / PW + 1; slot = n_rec * 32;
+    ring = ((size_t)rows * W * 16 + 15) & ~(size_t)15;
+    bytes = ring + (size_t)n_waves * 2 * (size_t)slot;
+  }
+};
+
 template <typename IT, int CB, int NT, int PFIX = 0>
 __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, int C, long ld, int PH_, int PW_,
                                                                 const unsigned short* __restrict__ feat,
@@ -1116,20 +1190,20 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
                                                                 int band_S, int band_rows, int n_bands, int n_zsplit) {
   static_assert(CB == 4 && NT == 1024, "launch_fwd_tasks runs 4 channels per lane, one 1024-thread workgroup per CU");
   const int PH = PFIX ? PFIX : PH_, PW = PFIX ? PFIX : PW_;
-  constexpr int EW = 4;                                             // channels per table entry (16 bytes)
-  constexpr int NPL = CB / EW;                                      // planes of entries
-  typedef u32x4 TE;
+  constexpr int NPL = CB / 4;                                       // planes of 16-byte entries
   constexpr int PXT = 10;                                           // table pixels per thread (host: rows * W <= PXT * NT)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int s_seg[TK_SEG], s_next[SP_NLEV];                  // s_next[L]: units of level L claimed so far
   // (band = blockIdx.z % n_bands keeps the 8 slabs of a 64-channel group, which write neighbouring runs of every ROI row, in the same
   // band at the same time on one XCD; dealing the bands so that the workgroups of a round differ in length — to take the chip out of
   // step: tables, then stores, everywhere at once — was slower: 99x165 / 8000 ROIs 486 -> 520 us per 8-slab group, 613 per slab)
+  const BandGeom bg{band_S, band_rows, n_bands, true};
   const int band = (int)(blockIdx.z % n_bands), zfirst = (int)(blockIdx.z / n_bands);
-  const int y0 = min(band * band_S, max(0, H - band_rows)), y1 = min(H, y0 + band_rows);        // map rows [y0, y1) live in LDS
+  const int y0 = bg.y0(band, H), y1 = bg.y1(band, H);               // map rows [y0, y1) live in LDS
   const int npl_px = band_rows * W;                                 // pixels per plane (allocated)
   const int npx_t = (y1 - y0) * W;                                  // pixels held
-  TE* tab = (TE*)smem;                                              // [NPL][npl_px]
+  const TasksLds lds(band_rows, W, PW, NT / 64);
+  u32x4* tab = (u32x4*)smem;                                        // [NPL][npl_px]
   const int c0 = xcd_grouped_slab() * CB, img = blockIdx.y;
   const int tid = threadIdx.x;
   const int nb = PH * PW;
@@ -1151,66 +1225,20 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
     xk[k] = px < npx_t ? px - (px / W) * W : -1;
 #pragma unroll
     for (int j = 0; j < CB / 2; ++j) raw[k][j] = 0u;
-    if (px < npx_t) {
-      const unsigned short* src = fimg + (long)(y0 * W + px) * C;
-      const u32x2 w = *(const u32x2*)src; raw[k][0] = w[0]; raw[k][1] = w[1];
-    }
+    if (px < npx_t) load_pixel_words<CB>(fimg + (long)(y0 * W + px) * C, raw[k]);
   }
 #pragma unroll
   for (int k = 0; k < PXT; ++k) {
     const int px = tid + k * NT;
-    if (px < npx_t) {
-      const unsigned int inv = 0xFFFEu - (unsigned)(y0 * W + px);
-#pragma unroll
-      for (int pl = 0; pl < NPL; ++pl) {
-        TE t;
-#pragma unroll
-        for (int e = 0; e < EW; ++e) {
-          const unsigned int w2 = raw[k][(EW * pl + e) >> 1];
-          t[e] = (key16_of((e & 1) ? (w2 >> 16) : (w2 & 0xFFFFu)) << 16) | inv;
-        }
-        tab[pl * npl_px + px] = t;
-      }
-    }
+    if (px < npx_t) store_level0<CB>(tab, npl_px, px, 0xFFFEu - (unsigned)(y0 * W + px), raw[k]);
   }
-  // Barriers of the level walk order LDS traffic only (table reads of level L - 1 before the advance writes, writes before the reads of
-  // level L): __syncthreads() also waits for vmcnt(0), i.e. for every output store the wave still has in flight — the phase clocks showed
-  // a wave parked at the level barriers for 26 % of a workgroup's cycles on the 99x165 map (most of it turned out to be the spread of
-  // the units' lengths, see the claims below; the stores' share is what this form removes)
-  auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-  constexpr unsigned KEY_INIT = 0x007FFFFFu;                        // key(-inf) << 16 | 0xFFFF
+  // the level walk needs LDS-only barriers (table reads of level L - 1 before the advance writes, writes before the reads of level L)
+  const LdsBarrier lds_barrier;
   for (int L = 0; L < SP_NLEV; ++L) {
     const int t_lo = s_seg[L * SP_NHC], t_hi = s_seg[(L + 1) * SP_NHC];
     if (t_lo >= n_tasks_end) break;                                 // no task at this or a higher level
     lds_barrier();                                                // level L - 1 fully scanned (L = 0: table written)
-    if (L > 0) {
-      const int d = 1 << (L - 1);
-      TE nv[PXT][NPL];
-#pragma unroll
-      for (int k = 0; k < PXT; ++k) {
-        const int px = tid + k * NT;
-        if (px < npx_t) {
-          const bool two = xk[k] + d < W;
-#pragma unroll
-          for (int pl = 0; pl < NPL; ++pl) {
-            const TE a = tab[pl * npl_px + px];
-            const TE b = two ? tab[pl * npl_px + px + d] : a;
-#pragma unroll
-            for (int e = 0; e < EW; ++e) nv[k][pl][e] = max(a[e], b[e]);
-          }
-        }
-      }
-      lds_barrier();
-#pragma unroll
-      for (int k = 0; k < PXT; ++k) {
-        const int px = tid + k * NT;
-        if (px < npx_t) {
-#pragma unroll
-          for (int pl = 0; pl < NPL; ++pl) tab[pl * npl_px + px] = nv[k][pl];
-        }
-      }
-      lds_barrier();
-    }
+    if (L > 0) advance_level<NPL, PXT, NT>(tab, npl_px, npx_t, W, L, xk, lds_barrier);
     const int span = 1 << L;
     const int n_lvl = t_hi - t_lo, total = n_lvl * PW;
     // Items (task, bin column) of the level, in units of 64 consecutive ones per wave and iteration.
@@ -1230,8 +1258,8 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
     if (n_units > 0) {
     const u32x4* lvl = my + 2 * (long)t_lo;
     const int lane = tid & 63;
-    const int n_rec = (62 + PW) / PW + 1, slot = n_rec * 32;        // records a wave's 64 consecutive items can touch (7 columns: 10)
-    char* wbuf = smem + ((((size_t)NPL * npl_px * sizeof(TE)) + 15) & ~(size_t)15) + (size_t)(tid >> 6) * (2 * slot);
+    const int n_rec = lds.n_rec, slot = lds.slot;                   // records a wave's 64 consecutive items can touch (7 columns: 10)
+    char* wbuf = smem + lds.ring + (size_t)(tid >> 6) * (2 * slot);
     auto claim = [&]() {                                            // j-th claim of the workgroup -> first item of that unit, or -1
       int j = 0;
       if (lane == 0) j = atomicAdd(&s_next[L], 1);
@@ -1259,91 +1287,11 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_tasks_kernel(int H, int W, in
       const int hs = (int)(q0[1] & 0xFFu), he = (int)(q0[1] >> 8);
       const int ws = (int)(wb & 0xFFu), we = (int)(wb >> 8);
       const int b = ph * PW + pw;
-      const bool empty = (he <= hs) || (we <= ws);
       unsigned int best[CB];
-#pragma unroll
-      for (int q = 0; q < CB; ++q) best[q] = KEY_INIT;
-      if (!empty) {
-        const int bw = we - ws;
-        const int he_lds = min(he, y1);
-        int cold_from = max(hs, y1);                                // first window row read from global memory
-        if (bw >= span) {
-          const int offB = bw - span;
-          const int last = (he_lds - 1 - y0) * W + ws;
-          for (int hh = hs; hh < he_lds; hh += 2) {
-            const int i0 = (hh - y0) * W + ws, i1 = min(i0 + W, last);
-            TE a0[NPL], b0[NPL], a1[NPL], b1[NPL];
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) {
-              a0[pl] = tab[pl * npl_px + i0]; b0[pl] = tab[pl * npl_px + i0 + offB];
-              a1[pl] = tab[pl * npl_px + i1]; b1[pl] = tab[pl * npl_px + i1 + offB];
-            }
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl)
-#pragma unroll
-              for (int e = 0; e < EW; ++e)
-                best[EW * pl + e] = max(max(max(max(best[EW * pl + e], a0[pl][e]), b0[pl][e]), a1[pl][e]), b1[pl][e]);
-            if (2 * span < bw) {                                    // only when the level was capped (SP_NLEV): spans in between
-              for (int rr = 0; rr < 2; ++rr) {
-                const int ib = rr ? i1 : i0;
-                for (int x = span; x < offB; x += span) {
-#pragma unroll
-                  for (int pl = 0; pl < NPL; ++pl) {
-                    const TE a = tab[pl * npl_px + ib + x];
-#pragma unroll
-                    for (int e = 0; e < EW; ++e) best[EW * pl + e] = max(best[EW * pl + e], a[e]);
-                  }
-                }
-              }
-            }
-          }
-        } else if (we == W) {                                       // clipped by the map's right edge: the span at ws ends at W
-          for (int hh = hs; hh < he_lds; ++hh) {
-            const int i0 = (hh - y0) * W + ws;
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl) {
-              const TE a = tab[pl * npl_px + i0];
-#pragma unroll
-              for (int e = 0; e < EW; ++e) best[EW * pl + e] = max(best[EW * pl + e], a[e]);
-            }
-          }
-        } else {
-          cold_from = hs;                                           // narrower than the ROI's span for another reason: pixel loop
-        }
-        for (int hh = cold_from; hh < he; ++hh)
-          for (int x = ws; x < we; ++x) {
-            const int gi = hh * W + x;
-            const unsigned int inv0 = 0xFFFEu - (unsigned)gi;
-            unsigned int u[CB / 2];
-            const u32x2 w = *(const u32x2*)(fimg + (long)gi * C); u[0] = w[0]; u[1] = w[1];
-#pragma unroll
-            for (int k = 0; k < CB / 2; ++k) {
-              best[2 * k] = max(best[2 * k], (key16_of(u[k] & 0xFFFFu) << 16) | inv0);
-              best[2 * k + 1] = max(best[2 * k + 1], (key16_of(u[k] >> 16) << 16) | inv0);
-            }
-          }
-      }
+      const bool empty = scan_window<CB, true>(best, tab, npl_px, fimg, C, W, y0, y1, span, hs, he, ws, we);
       float mv[CB]; int mi[CB];
-      unsigned int lowest = best[0];
-#pragma unroll
-      for (int q = 0; q < CB; ++q) {
-        const unsigned int m = (unsigned int)((int)best[q] >> 31);
-        mv[q] = __uint_as_float((best[q] & 0xFFFF0000u) ^ (0x80000000u | (~m & 0x7FFF0000u)));
-        mi[q] = (int)(0xFFFEu - (best[q] & 0xFFFFu));
-        lowest = min(lowest, best[q]);
-      }
-      if (lowest == KEY_INIT) {
-#pragma unroll
-        for (int q = 0; q < CB; ++q)
-          if (best[q] == KEY_INIT) mv[q] = empty ? 0.f : -FLT_MAX;
-      }
-      const float mul = __uint_as_float(q0[2]);
-      const long o = (long)r * ld + (long)c0 * nb + b;
-#pragma unroll
-      for (int q = 0; q < CB; ++q) {
-        Elem<unsigned short>::store(out + o + (long)q * nb, __fmul_rn(mv[q], mul));
-        argmax[o + (long)q * nb] = ArgIdx<IT>::enc(mi[q]);
-      }
+      decode_candidates<CB>(best, empty, mv, mi);
+      store_task<unsigned short, IT, CB>(out, argmax, (long)r * ld + (long)c0 * nb + b, nb, mv, mi, __uint_as_float(q0[2]));
       if (lane < 2 * n_rec) *(u32x4*)(wbuf + ((k + 1) & 1) * slot + lane * 16) = r1;     // iteration k + 1's records (fetched at k - 2)
       r1 = r2; r2 = r3;
       un0 = un1; un1 = un2; un2 = un3; un3 = un4;
@@ -1385,6 +1333,36 @@ __global__ void absmax_kernel(long n, const T* __restrict__ x, float* __restrict
 }  // namespace
 
 namespace {
+// One launch: the dynamic-LDS attribute where the size needs it, the launch, its status (0 = launched).
+template <typename K, typename... A>
+int launch(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, A... args) {
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+  return (int)hipGetLastError();
+}
+
+// Row bands (BandGeom) of a map of H rows when LDS holds `fit` of them.  A bin window of a ROI inside the image is at most
+// halo = ceil(H / PH) + 1 rows tall, so a band owns fit - halo rows and holds fit.  What the forms do differently:
+struct BandRule {
+  int min_own;              // fewest rows a band must own for the form to be worth running
+  bool equal_bands;         // even the own rows out over the bands (the band still holds all the rows LDS has: more ROIs lie inside one band)
+  bool clamp_last;          // BandGeom::clamp_last
+  bool whole_if_fits;       // fit >= H: one band of the whole map
+};
+constexpr BandRule PLANE_BANDS{8, false, false, false}, SPARSE_BANDS{8, false, false, true}, TASK_BANDS{4, true, true, true};
+inline bool band_geometry(int H, int PH, int fit, const BandRule& rule, BandGeom* bg) {
+  if (rule.whole_if_fits && fit >= H) { *bg = BandGeom{H, H, 1, rule.clamp_last}; return true; }
+  const int halo = (H + PH - 1) / PH + 1;
+  if (fit - halo < rule.min_own) return false;
+  int S = fit - halo;
+  if (rule.equal_bands) { const int n = (H + S - 1) / S; S = (H + n - 1) / n; }
+  *bg = BandGeom{S, fit, (H + S - 1) / S, rule.clamp_last};
+  return true;
+}
+
 // workgroups per (slab, image, band) = how many ways the ROI chunks are dealt out: enough workgroups to fill the chip a few times
 // over (the chunks differ in work), no more (each one fetches its slab of the map)
 inline int fwd_zsplit(int wg_per_z, int n_chunks, size_t lds) {
@@ -1396,72 +1374,33 @@ inline int fwd_zsplit(int wg_per_z, int n_chunks, size_t lds) {
   return nz > n_chunks ? n_chunks : nz;
 }
 
-template <typename T, int CB, typename IT>
+// plane form: the whole map (bg = one band of H rows) or, BAND, row bands of 16-byte bf16 pixels
+constexpr int PLANE_NT = 1024, PLANE_CHUNK = 256;
+template <typename T, int CB, typename IT, bool BAND>
 int launch_fwd_plane(int nimg, int H, int W, int C, long ld, int PH, int PW, float scale, const void* feat, const float* rois, int R,
-                     const float* row_scale, float row_scale_add, void* out, void* argmax, hipStream_t stream) {
-  constexpr int NT = 1024, CHUNK = 256;
-  const size_t lds = (((size_t)H * W * CB * sizeof(T) + 15) & ~(size_t)15) + (size_t)CHUNK * (4 + 2 * (PH + PW)) + 4 + (size_t)CHUNK * 4;
+                     const float* row_scale, float row_scale_add, void* out, void* argmax, const BandGeom& bg, hipStream_t stream) {
+  const size_t lds = PlaneLds(bg.rows, W, CB * (int)sizeof(T), PLANE_CHUNK, PH, PW, BAND).bytes;
   const bool key = sizeof(T) == 2 && (long)H * W < 65535;
-  auto kern = key ? roi_pool_fwd_plane_kernel<T, CB, NT, IT, (sizeof(T) == 2)> : roi_pool_fwd_plane_kernel<T, CB, NT, IT, false>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  const int nz = fwd_zsplit((C / CB) * nimg, (R + CHUNK - 1) / CHUNK, lds);
-  dim3 grid(C / CB, nimg, nz), block(NT);
-  hipLaunchKernelGGL(kern, grid, block, lds, stream, H, W, C, ld, PH, PW, scale, (const T*)feat, rois, R, CHUNK, row_scale,
-                     row_scale_add, (T*)out, (IT*)argmax, H, H, 1, nz);
-  SW_CHECK_LAUNCH();
-  return 0;
+  auto kern = key ? roi_pool_fwd_plane_kernel<T, CB, PLANE_NT, IT, (sizeof(T) == 2), BAND>
+                  : roi_pool_fwd_plane_kernel<T, CB, PLANE_NT, IT, false, false>;
+  const int nz = fwd_zsplit((C / CB) * nimg * bg.n_bands, (R + PLANE_CHUNK - 1) / PLANE_CHUNK, lds);
+  if ((long)bg.n_bands * nz > 65535) return -6;
+  return launch(kern, dim3(C / CB, nimg, bg.n_bands * nz), dim3(PLANE_NT), lds, stream, H, W, C, ld, PH, PW, scale, (const T*)feat, rois, R,
+                PLANE_CHUNK, row_scale, row_scale_add, (T*)out, (IT*)argmax, bg.S, bg.rows, bg.n_bands, nz);
 }
-
 // band form (bf16, 8 channels per lane): rows per band from the LDS left beside the ROI tables and the owned-pair list
-constexpr int BAND_CHUNK = 256;
-inline size_t band_tables_bytes(int PH, int PW) {
-  return (size_t)BAND_CHUNK * (4 + 2 * (PH + PW)) + 4 + (size_t)BAND_CHUNK * 4 + (size_t)BAND_CHUNK * PH * 4;
-}
-inline bool band_geometry(int H, int W, int PH, int PW, int* S, int* rows) {
-  const size_t budget = 160 * 1024 - 1024 - band_tables_bytes(PH, PW);     // 1 KiB: the kernel's static LDS + alignment
-  const int fit = (int)(budget / ((size_t)W * 16));
-  const int halo = (H + PH - 1) / PH + 1;          // a bin window of a ROI inside the image: <= ceil(H / PH) + 1 rows
-  if (fit - halo < 8 || PH > 255) return false;
-  *S = fit - halo; *rows = fit;
-  return true;
-}
-template <typename IT>
-int launch_fwd_band(int nimg, int H, int W, int C, long ld, int PH, int PW, float scale, const void* feat, const float* rois, int R,
-                    const float* row_scale, float row_scale_add, void* out, void* argmax, int S, int rows, hipStream_t stream) {
-  constexpr int NT = 1024, CB = 8;
-  typedef unsigned short T;
-  const size_t lds = (((size_t)rows * W * 16 + 15) & ~(size_t)15) + band_tables_bytes(PH, PW);
-  auto kern = roi_pool_fwd_plane_kernel<T, CB, NT, IT, true, true>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  const int n_bands = (H + S - 1) / S, n_chunks = (R + BAND_CHUNK - 1) / BAND_CHUNK;
-  const int nz = fwd_zsplit((C / CB) * nimg * n_bands, n_chunks, lds);
-  if ((long)n_bands * nz > 65535) return -6;
-  dim3 grid(C / CB, nimg, n_bands * nz), block(NT);
-  hipLaunchKernelGGL(kern, grid, block, lds, stream, H, W, C, ld, PH, PW, scale, (const T*)feat, rois, R, BAND_CHUNK, row_scale,
-                     row_scale_add, (T*)out, (IT*)argmax, S, rows, n_bands, nz);
-  SW_CHECK_LAUNCH();
-  return 0;
+inline bool plane_band_geometry(int H, int W, int PH, int PW, BandGeom* bg) {
+  const size_t budget = 160 * 1024 - 1024 - PlaneLds(0, W, 16, PLANE_CHUNK, PH, PW, true).bytes;      // 1 KiB: the kernel's static LDS + alignment
+  return PH <= 255 && band_geometry(H, PH, (int)(budget / ((size_t)W * 16)), PLANE_BANDS, bg);
 }
 
-// sparse-table form: LDS = table planes + the image's sorted ROI list + one chunk's tables
-inline size_t sparse_tables_bytes(int R, int PH, int PW, bool band, int chunk) {
-  return (size_t)((R + 1) & ~1) * 2 + (size_t)chunk * (4 + 4 + 2 * (PH + PW)) + 4 + (band ? (size_t)chunk * PH * 4 : 0) + 16;
-}
 template <typename IT, int CB, bool BAND>
-int launch_sparse_kernel(dim3 grid, size_t lds, int H, int W, int C, long ld, int PH, int PW, float scale, const void* feat, const float* rois,
-                         int R, const float* row_scale, float row_scale_add, void* out, void* argmax, int S, int rows, int n_bands, int nz,
-                         int chunk, hipStream_t stream) {
+int launch_sparse_kernel(int nimg, int H, int W, int C, long ld, int PH, int PW, float scale, const void* feat, const float* rois, int R,
+                         const float* row_scale, float row_scale_add, void* out, void* argmax, const BandGeom& bg, int nz, size_t lds,
+                         hipStream_t stream) {
   auto kern = (PH == 7 && PW == 7) ? roi_pool_fwd_sparse_kernel<IT, CB, BAND, 7> : roi_pool_fwd_sparse_kernel<IT, CB, BAND, 0>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, grid, dim3(SP_NT), lds, stream, H, W, C, ld, PH, PW, scale, (const unsigned short*)feat, rois, R, row_scale,
-                     row_scale_add, (unsigned short*)out, (IT*)argmax, S, rows, n_bands, nz, chunk);
-  SW_CHECK_LAUNCH();
-  return 0;
+  return launch(kern, dim3(C / CB, nimg, bg.n_bands * nz), dim3(SP_NT), lds, stream, H, W, C, ld, PH, PW, scale, (const unsigned short*)feat,
+                rois, R, row_scale, row_scale_add, (unsigned short*)out, (IT*)argmax, bg.S, bg.rows, bg.n_bands, nz, SP_CH);
 }
 
 template <typename IT>
@@ -1480,32 +1419,25 @@ int launch_fwd_sparse(int nimg, int H, int W, int C, long ld, int PH, int PW, fl
   // barrier behind a scan; profiles/r06_roi_phases.txt) suggested larger chunks; measured, they are slower on every map (99x165 / 8000
   // ROIs: 672 us at 128, 684 at 256, 792 at 512, 1041 at 1024 — their tables take LDS from the band's rows;
   // profiles/r06_roi_chunk_sweep.txt)
-  const size_t plane8 = (size_t)H * W * 32 + sparse_tables_bytes(R, PH, PW, false, SP_CH);
-  if (plane8 <= LDS_MAX && (long)H * W <= 5 * SP_NT) {
-    const int nz = zsplit((C / 8) * nimg);
-    return launch_sparse_kernel<IT, 8, false>(dim3(C / 8, nimg, nz), plane8, H, W, C, ld, PH, PW, scale, feat, rois, R, row_scale,
-                                              row_scale_add, out, argmax, H, H, 1, nz, SP_CH, stream);
-  }
+  const size_t plane8 = SparseLds((size_t)H * W * 32, R, SP_CH, PH, PW, false).bytes;
+  if (plane8 <= LDS_MAX && (long)H * W <= 5 * SP_NT)
+    return launch_sparse_kernel<IT, 8, false>(nimg, H, W, C, ld, PH, PW, scale, feat, rois, R, row_scale, row_scale_add, out, argmax,
+                                              BandGeom{H, H, 1, false}, zsplit((C / 8) * nimg), plane8, stream);
   // row bands: 4 channels per lane (16 B per pixel).  8 channels (32 B per pixel: a third of the rows per band) measured slower on
   // every banded map (99x165 / 8000 ROIs: 956 vs 669 us with 9 vs 3 bands; 125x167: 525 vs 383; 76x114: 245 vs 219) — the bands'
   // redundant ROI tables and slab fetches outweigh the halved task count
-  const size_t tb = sparse_tables_bytes(R, PH, PW, true, SP_CH);
+  const size_t tb = SparseLds(0, R, SP_CH, PH, PW, true).bytes;
   if (PH > 255) return -100;
-  const int halo = (H + PH - 1) / PH + 1;
   constexpr int cb = 4, pxb = 16, pxt = 10;
   if (tb + (size_t)W * pxb * 8 > LDS_MAX) return -100;
   int fit = (int)((LDS_MAX - tb) / ((size_t)W * pxb));
   if ((long)fit * W > (long)pxt * SP_NT) fit = pxt * SP_NT / W;
-  int S, rows;
-  if (fit >= H) { S = H; rows = H; }                                // the whole map fits: one band
-  else { if (fit - halo < 8) return -100; S = fit - halo; rows = fit; }
-  const int n_bands = (H + S - 1) / S;
-  const size_t lds = (size_t)rows * W * pxb + tb;
-  const int nz = zsplit((C / cb) * nimg * n_bands);
-  if ((long)n_bands * nz > 65535) return -100;
-  dim3 grid(C / cb, nimg, n_bands * nz);
-  return launch_sparse_kernel<IT, cb, true>(grid, lds, H, W, C, ld, PH, PW, scale, feat, rois, R, row_scale, row_scale_add, out, argmax,
-                                            S, rows, n_bands, nz, SP_CH, stream);
+  BandGeom bg;
+  if (!band_geometry(H, PH, fit, SPARSE_BANDS, &bg)) return -100;
+  const int nz = zsplit((C / cb) * nimg * bg.n_bands);
+  if ((long)bg.n_bands * nz > 65535) return -100;
+  return launch_sparse_kernel<IT, cb, true>(nimg, H, W, C, ld, PH, PW, scale, feat, rois, R, row_scale, row_scale_add, out, argmax, bg, nz,
+                                            SparseLds((size_t)bg.rows * W * pxb, R, SP_CH, PH, PW, true).bytes, stream);
 }
 
 // prepared-task form (sw_roi_pool_fwd with a workspace): workspace = [nimg][TK_MAXB][TK_SEG] ints, then [nimg][R * PH] task records of 32 bytes
@@ -1519,18 +1451,6 @@ inline bool tasks_shape_ok(int dtype, int nimg, int H, int W, int C, int PH, int
          (((uintptr_t)feat) & 15) == 0;
 }
 
-template <typename IT, int CB, int NT>
-int launch_tasks_kernel(dim3 grid, size_t lds, int H, int W, int C, long ld, int PH, int PW, const void* feat, const u32x4* tasks,
-                        const int* seg, long cap, void* out, void* argmax, int S, int rows, int n_bands, int nz, hipStream_t stream) {
-  auto kern = (PH == 7 && PW == 7) ? roi_pool_fwd_tasks_kernel<IT, CB, NT, 7> : roi_pool_fwd_tasks_kernel<IT, CB, NT, 0>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, grid, dim3(NT), lds, stream, H, W, C, ld, PH, PW, (const unsigned short*)feat, tasks, seg, cap,
-                     (unsigned short*)out, (IT*)argmax, S, rows, n_bands, nz);
-  SW_CHECK_LAUNCH();
-  return 0;
-}
-
 template <typename IT>
 int launch_fwd_tasks(int nimg, int H, int W, int C, long ld, int PH, int PW, float scale, const void* feat, const float* rois, int R,
                      const float* row_scale, float row_scale_add, void* out, void* argmax, void* workspace, hipStream_t stream) {
@@ -1542,38 +1462,31 @@ int launch_fwd_tasks(int nimg, int H, int W, int C, long ld, int PH, int PW, flo
   u32x4* tasks = (u32x4*)((char*)hist + tasks_hist_bytes(nimg, R));
   const long cap = (long)R * PH;
   if (PW < 3) return -100;                                          // a wave's 64 items then span more records than it has lanes to fetch
-  const size_t ring = (size_t)(NT / 64) * 2 * (size_t)(((62 + PW) / PW + 1) * 32);   // the waves' record rings
+  const size_t ring = TasksLds(0, W, PW, NT / 64).bytes;            // the waves' record rings
   // maps that fit LDS whole at 8 channels per lane: the sparse kernel's per-chunk work is small there (63x63 / 4000 ROIs: 151 us against
   // 155 + 18 us of list building), so they stay with it
   if ((size_t)H * W * 32 + ring <= LDS_ALL && (long)H * W <= 5 * 1024) return -100;
   // row bands of 16-byte pixels
   int fit = (int)((LDS_ALL - ring) / ((size_t)W * CB * 4));
   if ((long)fit * W > 10L * NT) fit = 10 * NT / W;
-  int S, rows, n_bands;
-  if (fit >= H) { S = H; rows = H; n_bands = 1; }
-  else {
-    const int halo = (H + PH - 1) / PH + 1;
-    if (fit - halo < 4) return -100;
-    n_bands = (H + (fit - halo) - 1) / (fit - halo);
-    S = (H + n_bands - 1) / n_bands;                                // equal bands
-    n_bands = (H + S - 1) / S;
-    rows = fit;                                                     // all the rows LDS holds: more ROIs lie inside one band
-    if (n_bands > TK_MAXB) return -100;
-  }
-  if (nimg * n_bands > 64) return -100;
+  BandGeom bg;
+  if (!band_geometry(H, PH, fit, TASK_BANDS, &bg) || bg.n_bands > TK_MAXB) return -100;
+  if (nimg * bg.n_bands > 64) return -100;
   const int prep_wgs = (R + TK_PREP_NT - 1) / TK_PREP_NT;
-  hipLaunchKernelGGL(roi_pool_geo_kernel, dim3(prep_wgs), dim3(TK_PREP_NT), 0, stream, nimg, H, W, PH, PW, scale, rois, R, row_scale,
-                     row_scale_add, S, rows, n_bands, geo, hist);
-  hipLaunchKernelGGL(roi_pool_tasks_kernel, dim3(prep_wgs), dim3(TK_PREP_NT), 0, stream, nimg, PH, R, n_bands, (const RoiGeo*)geo,
-                     (const int*)hist, tasks, seg, cap);
-  SW_CHECK_LAUNCH();
-  const size_t lds = ((((size_t)rows * W * CB * 4) + 15) & ~(size_t)15) + ring;
-  const int slabs = (C / CB) * nimg * n_bands;
+  int rc = launch(roi_pool_geo_kernel, dim3(prep_wgs), dim3(TK_PREP_NT), 0, stream, nimg, H, W, PH, PW, scale, rois, R, row_scale,
+                  row_scale_add, bg.S, bg.rows, bg.n_bands, geo, hist);
+  if (rc == 0)
+    rc = launch(roi_pool_tasks_kernel, dim3(prep_wgs), dim3(TK_PREP_NT), 0, stream, nimg, PH, R, bg.n_bands, (const RoiGeo*)geo,
+                (const int*)hist, tasks, seg, cap);
+  if (rc != 0) return rc;
+  const int slabs = (C / CB) * nimg * bg.n_bands;
   int nz = (256 + slabs / 2) / slabs;                               // 256 workgroups
   nz = nz < 1 ? 1 : nz;
-  if ((long)n_bands * nz > 65535) return -6;
-  dim3 grid(C / CB, nimg, n_bands * nz);
-  return launch_tasks_kernel<IT, CB, NT>(grid, lds, H, W, C, ld, PH, PW, feat, tasks, seg, cap, out, argmax, S, rows, n_bands, nz, stream);
+  if ((long)bg.n_bands * nz > 65535) return -6;
+  auto kern = (PH == 7 && PW == 7) ? roi_pool_fwd_tasks_kernel<IT, CB, NT, 7> : roi_pool_fwd_tasks_kernel<IT, CB, NT, 0>;
+  return launch(kern, dim3(C / CB, nimg, bg.n_bands * nz), dim3(NT), TasksLds(bg.rows, W, PW, NT / 64).bytes, stream, H, W, C, ld, PH, PW,
+                (const unsigned short*)feat, (const u32x4*)tasks, (const int*)seg, cap, (unsigned short*)out, (IT*)argmax, bg.S, bg.rows,
+                bg.n_bands, nz);
 }
 
 template <typename IT>
@@ -1596,14 +1509,14 @@ int roi_fwd_dispatch(int dtype, int nimg, int H, int W, int C, long ld, int PH, 
       const int rc = launch_fwd_sparse<IT>(nimg, H, W, C, ld, PH, PW, spatial_scale, feat, rois, R, row_scale, row_scale_add, out, argmax, stream);
       if (rc != -100) return rc;                                                   // -100: shape not covered, use the forms below
     }
-    int bS = 0, brows = 0;
+    BandGeom bg;
     if (dtype == SW_BF16 && pxb < 16 && (C % 8) == 0 && (long)H * W < 65535 &&
-        band_geometry(H, W, PH, PW, &bS, &brows))
-      return launch_fwd_band<IT>(nimg, H, W, C, ld, PH, PW, spatial_scale, feat, rois, R, row_scale, row_scale_add, out, argmax,
-                                 bS, brows, stream);
+        plane_band_geometry(H, W, PH, PW, &bg))
+      return launch_fwd_plane<unsigned short, 8, IT, true>(nimg, H, W, C, ld, PH, PW, spatial_scale, feat, rois, R, row_scale, row_scale_add,
+                                                           out, argmax, bg, stream);
     if (pxb) {
-#define SW_FWD_PLANE(T, CB) return launch_fwd_plane<T, CB, IT>(nimg, H, W, C, ld, PH, PW, spatial_scale, feat, rois, R, row_scale, \
-                                                               row_scale_add, out, argmax, stream)
+#define SW_FWD_PLANE(T, CB) return launch_fwd_plane<T, CB, IT, false>(nimg, H, W, C, ld, PH, PW, spatial_scale, feat, rois, R, row_scale, \
+                                                                      row_scale_add, out, argmax, BandGeom{H, H, 1, false}, stream)
       if (dtype == SW_BF16) {
         if (pxb == 16) SW_FWD_PLANE(unsigned short, 8);
         if (pxb == 8) SW_FWD_PLANE(unsigned short, 4);
@@ -1623,13 +1536,10 @@ int roi_fwd_dispatch(int dtype, int nimg, int H, int W, int C, long ld, int PH, 
   if (lds > 64 * 1024) return -6;
   dim3 grid(R, (C + ch - 1) / ch), block(256);
   if (dtype == SW_BF16)
-    hipLaunchKernelGGL((roi_pool_fwd_kernel<unsigned short, 2, IT>), grid, block, lds, stream, H, W, C, ld, PH, PW, spatial_scale,
-                       (const unsigned short*)feat, rois, row_scale, row_scale_add, (unsigned short*)out, (IT*)argmax);
-  else
-    hipLaunchKernelGGL((roi_pool_fwd_kernel<float, 1, IT>), grid, block, lds, stream, H, W, C, ld, PH, PW, spatial_scale,
-                       (const float*)feat, rois, row_scale, row_scale_add, (float*)out, (IT*)argmax);
-  SW_CHECK_LAUNCH();
-  return 0;
+    return launch(roi_pool_fwd_kernel<unsigned short, 2, IT>, grid, block, lds, stream, H, W, C, ld, PH, PW, spatial_scale,
+                  (const unsigned short*)feat, rois, row_scale, row_scale_add, (unsigned short*)out, (IT*)argmax);
+  return launch(roi_pool_fwd_kernel<float, 1, IT>, grid, block, lds, stream, H, W, C, ld, PH, PW, spatial_scale, (const float*)feat, rois,
+                row_scale, row_scale_add, (float*)out, (IT*)argmax);
 }
 
 template <typename T, typename IT>
@@ -1653,20 +1563,9 @@ int roi_bwd_dispatch(int nimg, int H, int W, int C, long ld, int PH, int PW, con
   if (cbx >= 4 && nsplit <= 16 && dout_absmax != nullptr && (((uintptr_t)dout & 7) == 0) && (((uintptr_t)argmax & 15) == 0) && (ld % 4) == 0) {
     const int px_per = (H * W + nsplit - 1) / nsplit;
     const size_t ldsx = (size_t)px_per * cbx * ab + FX_CHUNK * 8;
-    dim3 gridx(C / cbx, nimg, nsplit), blockx(1024);
-    hipError_t ex;
-#define SW_BWD_FX(MODE)                                                                                                       \
-    {                                                                                                                           \
-      auto k = roi_pool_bwd_fx_kernel<T, IT, MODE>;                                                                             \
-      ex = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsx);                          \
-      if (ex != hipSuccess) return (int)ex;                                                                                     \
-      hipLaunchKernelGGL(k, gridx, blockx, ldsx, stream, H, W, C, ld, PH * PW, cbx, (const T*)dout, (const IT*)argmax, rois, R, \
-                         row_scale, row_scale_add, dout_absmax, (const T*)relu_ref, (T*)dfeat, spatial_scale);                  \
-    }
-    if (accmode == 2) SW_BWD_FX(2) else SW_BWD_FX(0)
-#undef SW_BWD_FX
-    SW_CHECK_LAUNCH();
-    return 0;
+    auto k = accmode == 2 ? roi_pool_bwd_fx_kernel<T, IT, 2> : roi_pool_bwd_fx_kernel<T, IT, 0>;
+    return launch(k, dim3(C / cbx, nimg, nsplit), dim3(1024), ldsx, stream, H, W, C, ld, PH * PW, cbx, (const T*)dout, (const IT*)argmax, rois,
+                  R, row_scale, row_scale_add, dout_absmax, (const T*)relu_ref, (T*)dfeat, spatial_scale);
   }
   // float-atomic path: channel slab per workgroup a power of two, H*W*CB*4 <= 64 KiB (two 1024-thread workgroups per
   // CU) and enough slabs to give every CU work (C/CB * nimg >= 512 where the map allows)
@@ -1674,14 +1573,8 @@ int roi_bwd_dispatch(int nimg, int H, int W, int C, long ld, int PH, int PW, con
   while (CB > 1 && ((size_t)H * W * CB * 4 > 64 * 1024 || (C % CB) || (C / CB) * nimg < 512)) CB >>= 1;
   const size_t lds = (size_t)H * W * CB * 4;
   if (lds > 160 * 1024) return -6;
-  dim3 grid(C / CB, nimg), block(1024);
-  auto k = roi_pool_bwd_kernel<T, IT>;
-  hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(k, grid, block, lds, stream, H, W, C, ld, PH * PW, CB, (const T*)dout, (const IT*)argmax, rois, R, row_scale,
-                     row_scale_add, (const T*)relu_ref, (T*)dfeat);
-  SW_CHECK_LAUNCH();
-  return 0;
+  return launch(roi_pool_bwd_kernel<T, IT>, dim3(C / CB, nimg), dim3(1024), lds, stream, H, W, C, ld, PH * PW, CB, (const T*)dout,
+                (const IT*)argmax, rois, R, row_scale, row_scale_add, (const T*)relu_ref, (T*)dfeat);
 }
 }  // namespace
 

@@ -693,24 +693,45 @@ def test_roi_pool_ties_and_special_values(ops, dtype):
         assert np.array_equal(got, want, equal_nan=True)
 
 
-@pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("H,W", [(100, 120), (125, 167)])
-def test_roi_pool_forward_slab_widths_of_large_maps(ops, dtype, H, W):
-    """maps whose whole plane does not fit LDS with 16-byte pixels: bf16 runs the band form (row bands of 8-channel slabs; ROIs
-    reaching far outside the image exercise its beyond-the-band rows), f32 the narrower slabs — bins, argmax and values still
-    bit-exact vs the C oracle"""
-    n, C, R = 2, 16, 120
+@pytest.mark.parametrize("dtype,H,W,C,PH,PW,adt,roi_set", [
+    # maps whose whole plane does not fit LDS with 16-byte pixels, 16 channels, 7 x 7
+    pytest.param(torch.float32, 100, 120, 16, 7, 7, None, "far", id="100-120-dtype0"),
+    pytest.param(torch.bfloat16, 100, 120, 16, 7, 7, None, "far", id="100-120-dtype1"),
+    pytest.param(torch.float32, 125, 167, 16, 7, 7, None, "far", id="125-167-dtype0"),
+    pytest.param(torch.bfloat16, 125, 167, 16, 7, 7, None, "far", id="125-167-dtype1"),
+    # bf16 plane kernel, packed-key scan: C % 8 != 0 keeps the sparse and task kernels out; 4 and 2 channels per lane
+    pytest.param(torch.bfloat16, 24, 30, 12, 7, 7, torch.int32, "edge", id="key-C12-int32"),
+    pytest.param(torch.bfloat16, 24, 30, 12, 7, 7, torch.int16, "edge", id="key-C12-int16"),
+    pytest.param(torch.bfloat16, 24, 30, 6, 7, 7, torch.int32, "edge", id="key-C6-int32"),
+    pytest.param(torch.bfloat16, 24, 30, 6, 7, 7, torch.int16, "edge", id="key-C6-int16"),
+    # bf16 plane kernel, row bands: PH > 8 keeps the sparse and task kernels out, 16-byte pixels do not fit the plane: two bands
+    pytest.param(torch.bfloat16, 100, 120, 8, 9, 7, None, "far", id="band-9x7"),
+])
+def test_roi_pool_forward_slab_widths_of_large_maps(ops, dtype, H, W, C, PH, PW, adt, roi_set):
+    """the feature-stationary plane kernel in every slab width and form.  Maps whose whole plane does not fit LDS with 16-byte
+    pixels: f32 runs the plane kernel at 2 and 1 channels per lane; bf16 with C % 8 == 0 runs the sparse-table or the prepared-task
+    kernel (row bands).  The bf16 plane kernel itself takes what those two decline: C % 8 != 0 (packed-key scan, 4 and 2 channels
+    per lane) and pooled sizes above 8 (its row-band form: ROIs reaching far outside the image have clipped bins taller than a band
+    and exercise its beyond-the-band rows).  Bins, argmax and values bit-exact vs the C oracle"""
+    n, R = 2, 120
     feat = _rand((n, C, H, W), 61, dtype).float()
-    views, _ = O.make_views(H * 8, W * 8, R, tag="slab")
-    boxes = views[0]["boxes"].copy()
-    boxes[:6] = [[0, 0, 1e4, 1e4], [-900, -700, 8 * W + 500, 8 * H + 900], [40, -3000, 300, 5000], [-50, -50, -10, -10],
-                 [8 * W - 9, 8 * H - 9, 8 * W + 40, 8 * H + 40], [0, 8 * H - 200, 8 * W, 8 * H - 1]]   # bins taller than a band's overlap
+    if roi_set == "far":
+        views, _ = O.make_views(H * 8, W * 8, R, tag="slab")
+        boxes = views[0]["boxes"].copy()
+        boxes[:6] = [[0, 0, 1e4, 1e4], [-900, -700, 8 * W + 500, 8 * H + 900], [40, -3000, 300, 5000], [-50, -50, -10, -10],
+                     [8 * W - 9, 8 * H - 9, 8 * W + 40, 8 * H + 40], [0, 8 * H - 200, 8 * W, 8 * H - 1]]   # bins taller than a band's overlap
+    else:
+        views, _ = O.make_views(H * 8, W * 8, R, tag="rp")
+        boxes = views[0]["boxes"].copy()
+        boxes[:5] = [[0, 0, 1e4, 1e4], [-50, -50, -10, -10], [100, 100, 90, 90], [8 * W - 1, 8 * H - 1, 8 * W + 40, 8 * H + 40],
+                     [3.9, 3.9, 4.1, 4.1]]                       # clipped / outside / malformed / edge / tiny
     rois = np.concatenate([(np.arange(R) % n)[:, None].astype(np.float32), boxes], 1).astype(np.float32)
-    ref_out, ref_arg = O.roi_pool_fwd(feat.numpy(), rois, 1.0 / 8)
+    ref_out, ref_arg = O.roi_pool_fwd(feat.numpy(), rois, 1.0 / 8, PH, PW)
+    assert (ref_arg < 0).any() and (ref_arg >= 0).any()           # empty and non-empty bins
     f = _nhwc(feat).to(dtype).cuda()
-    out = torch.empty(R, C * 49, device="cuda", dtype=dtype)
-    arg = torch.empty(R, C * 49, device="cuda", dtype=ops.roi_argmax_dtype(H, W))
-    ops.roi_pool_fwd(f, torch.from_numpy(rois).cuda(), out, arg, 1.0 / 8, 7, 7)
+    out = torch.empty(R, C * PH * PW, device="cuda", dtype=dtype)
+    arg = torch.empty(R, C * PH * PW, device="cuda", dtype=adt or ops.roi_argmax_dtype(H, W))
+    ops.roi_pool_fwd(f, torch.from_numpy(rois).cuda(), out, arg, 1.0 / 8, PH, PW)
     assert np.array_equal(ops.argmax_to_int32(arg).cpu().numpy().reshape(ref_arg.shape), ref_arg)
     assert torch.equal(out.cpu().float().reshape(ref_out.shape), torch.from_numpy(ref_out).to(dtype).float())
 
@@ -782,22 +803,27 @@ def test_roi_pool_forward_row_sparse_table_form_other_pooled_sizes(ops, ws):
         assert torch.equal(out.cpu().float().reshape(ref_out.shape), torch.from_numpy(ref_out))
 
 
-def test_roi_pool_large_map_uses_gather_form(ops):
-    """a map whose H*W plane does not fit LDS falls back to the gather kernel; > 65534 pixels needs int32 indices"""
-    n, C, H, W, R = 1, 8, 260, 256, 64
-    feat = _rand((n, C, H, W), 33, torch.float32)
+@pytest.mark.parametrize("dtype", DT)
+def test_roi_pool_large_map_uses_gather_form(ops, dtype):
+    """a map the plane kernels do not take falls back to the gather kernel.  f32: an H*W plane that does not fit LDS; > 65534 pixels
+    needs int32 indices.  bf16 (two channels per lane): a map more than 255 rows high, with both index widths"""
+    n, C, R = 1, 8, 64
+    H, W = (260, 256) if dtype == torch.float32 else (260, 40)
+    feat = _rand((n, C, H, W), 33, dtype).float()
     views, _ = O.make_views(H * 8, W * 8, R, tag="big")
     rois = np.concatenate([np.zeros((R, 1), np.float32), views[0]["boxes"]], 1).astype(np.float32)
     ref_out, ref_arg = O.roi_pool_fwd(feat.numpy(), rois, 1.0 / 8)
-    f = _nhwc(feat).cuda()
-    out = torch.empty(R, C * 49, device="cuda"); arg = torch.empty(R, C * 49, device="cuda", dtype=torch.int32)
-    ops.roi_pool_fwd(f, torch.from_numpy(rois).cuda(), out, arg, 1.0 / 8, 7, 7)
-    assert np.array_equal(arg.cpu().numpy().reshape(ref_arg.shape), ref_arg)
-    assert np.array_equal(out.cpu().numpy().reshape(ref_out.shape), ref_out)
-    assert ops.roi_argmax_dtype(H, W) == torch.int32
-    with pytest.raises(Exception):
-        ops.roi_pool_fwd(f, torch.from_numpy(rois).cuda(), out, torch.empty(R, C * 49, device="cuda", dtype=torch.int16),
-                         1.0 / 8, 7, 7)
+    f = _nhwc(feat).to(dtype).cuda()
+    for adt in (torch.int32,) if dtype == torch.float32 else (torch.int32, torch.int16):
+        out = torch.empty(R, C * 49, device="cuda", dtype=dtype); arg = torch.empty(R, C * 49, device="cuda", dtype=adt)
+        ops.roi_pool_fwd(f, torch.from_numpy(rois).cuda(), out, arg, 1.0 / 8, 7, 7)
+        assert np.array_equal(ops.argmax_to_int32(arg).cpu().numpy().reshape(ref_arg.shape), ref_arg)
+        assert np.array_equal(out.cpu().float().numpy().reshape(ref_out.shape), ref_out)
+    if dtype == torch.float32:
+        assert ops.roi_argmax_dtype(H, W) == torch.int32
+        with pytest.raises(Exception):
+            ops.roi_pool_fwd(f, torch.from_numpy(rois).cuda(), out, torch.empty(R, C * 49, device="cuda", dtype=torch.int16),
+                             1.0 / 8, 7, 7)
 
 
 @pytest.mark.parametrize("dtype", DT)

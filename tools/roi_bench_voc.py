@@ -1,4 +1,5 @@
-"""ROIPool forward / backward at a given map size (env RH, RW, RR; default the VOC-sized 76 x 114 map, 4000 ROIs on 2 images)."""
+"""ROIPool forward / backward at a given map size (env RH, RW, RR; default the VOC-sized 76 x 114 map, 4000 ROIs on 2 images).
+env RN: launches per timed window (default 10; an A/B between two libraries wants windows of >= 0.5 s)."""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import sos_wsod_amd.ops as ops
@@ -11,7 +12,7 @@ rois = torch.stack([(torch.arange(R) >= R // 2).float(), x1, y1, (x1 + bw).clamp
 feat = torch.randn(2, H, W, C, device=dev).relu().to(dt); obj = torch.rand(R, device=dev)
 out = torch.empty(R, C * 49, device=dev, dtype=dt); arg = torch.empty(R, C * 49, device=dev, dtype=torch.int16)
 dout = torch.randn(R, C * 49, device=dev).to(dt); dfeat = torch.empty_like(feat)
-def t(fn, n=10):
+def t(fn, n=int(os.environ.get('RN', 10))):
     for _ in range(2): fn()
     torch.cuda.synchronize(); a = torch.cuda.Event(enable_timing=True); b = torch.cuda.Event(enable_timing=True)
     a.record(); [fn() for _ in range(n)]; b.record(); torch.cuda.synchronize(); return a.elapsed_time(b) / n

@@ -1,6 +1,7 @@
 """ROIPool forward: sw_roi_pool_fwd with a workspace (the prepared-task form) against the same entry without one.
     python tools/roi_tasks_forms.py                     # all shapes: no workspace | prepared tasks
-Each shape runs in its own child process; prints the time and checks that values and argmax equal the no-workspace form's bit for bit."""
+Each shape runs in its own child process; prints the time and checks that values and argmax equal the no-workspace form's bit for bit.
+env RN: launches per timed window (default 20)."""
 import os, subprocess, sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 SHAPES = [(63, 63, 4000), (76, 114, 4000), (99, 165, 8000), (104, 139, 4000), (125, 167, 4000), (150, 200, 4000), (47, 62, 4000)]
@@ -22,13 +23,13 @@ def one(H, W, R):
     out0, arg0, out, arg = mk(dt), mk(torch.int16), mk(dt), mk(torch.int16)
     ops.roi_pool_fwd(feat, rois, out0, arg0, 0.125, 7, 7, row_scale=obj, row_scale_add=1.0, workspace=None)
     ws = ops.roi_pool_fwd_workspace(2, R, 7, 7, dev)
-    res = []
+    res, n_launch = [], int(os.environ.get("RN", 20))
     for w in (None, ws):
         fn = lambda: ops.roi_pool_fwd(feat, rois, out, arg, 0.125, 7, 7, row_scale=obj, row_scale_add=1.0, workspace=w)
         for _ in range(3): fn()
         torch.cuda.synchronize(); a = torch.cuda.Event(enable_timing=True); b = torch.cuda.Event(enable_timing=True)
-        a.record(); [fn() for _ in range(20)]; b.record(); torch.cuda.synchronize()
-        res.append(a.elapsed_time(b) / 20 * 1e3)
+        a.record(); [fn() for _ in range(n_launch)]; b.record(); torch.cuda.synchronize()
+        res.append(a.elapsed_time(b) / n_launch * 1e3)
     same = torch.equal(out.view(torch.int16), out0.view(torch.int16)) and torch.equal(arg, arg0)
     alg = R * 25088 * 4 + 2 * H * W * C * 2
     print(f"{H}x{W} map, {R} ROIs: no workspace {res[0]:7.1f} us | prepared tasks {res[1]:7.1f} us = {alg / res[1] / 1e6 / 8:.3f} of 8 TB/s"
