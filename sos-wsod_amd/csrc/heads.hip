@@ -390,10 +390,16 @@ __device__ __forceinline__ unsigned int orderable(float f) {
   const unsigned int u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+__device__ __forceinline__ float from_orderable(unsigned int o) {
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
 // ascending sort of this key == descending score, ascending index (the oracle's tie rule)
 __device__ __forceinline__ unsigned long long make_key(float score, unsigned int idx) {
   return ((unsigned long long)(~orderable(score)) << 32) | idx;
 }
+// a make_key key taken apart: its index, and its score bit for bit
+__device__ __forceinline__ int key_index(unsigned long long key) { return (int)(unsigned int)(key & 0xFFFFFFFFu); }
+__device__ __forceinline__ float key_score(unsigned long long key) { return from_orderable(~(unsigned int)(key >> 32)); }
 
 // WAVE_LOCAL (keys in LDS): a pass whose partner distance j is < 128 stays inside one aligned block of 128 keys.  A wave owns
 // such a block (lane = the pair whose lower index has bit j clear) and runs all the remaining passes of the stage on it back to
@@ -439,7 +445,8 @@ __device__ void bitonic_sort(unsigned long long* keys, int N, int nseg = 1) {
   }
 }
 
-__device__ __forceinline__ int next_pow2(int n) { int p = 64; while (p < n) p <<= 1; return p; }
+// smallest power of two >= n, at least 64 (a wave): the length a list of n keys is padded to for bitonic_sort, on both sides of a launch
+__host__ __device__ __forceinline__ int next_pow2(int n) { int p = 64; while (p < n) p <<= 1; return p; }
 
 __device__ __forceinline__ float box_area(const float* b) { return __fmul_rn(b[2] - b[0], b[3] - b[1]); }
 
@@ -465,10 +472,6 @@ __device__ __forceinline__ float iou_pair(const float* gtb, const float* pb) {
   const float h = fmaxf(fminf(gtb[3], pb[3]) - fmaxf(gtb[1], pb[1]), 0.f);
   const float inter = __fmul_rn(w, h);
   return inter > 0.f ? __fdiv_rn(inter, __fadd_rn(box_area(gtb), box_area(pb)) - inter) : 0.f;
-}
-
-__device__ __forceinline__ float from_orderable(unsigned int o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
 }
 
 // STAGED (the usual case: the sort keys + 25 bytes per (rank, class) slot fit LDS): the slot lists live in LDS, the NMS sort keys
@@ -526,8 +529,8 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
     for (int i = tid; i < top_k * nb; i += blockDim.x) {
       const int b = i / top_k, rank = i - b * top_k;
       const unsigned long long key = keys[b * NPR + rank];
-      slot_idx[rank * G + g0 + b] = (int)(unsigned int)(key & 0xFFFFFFFFu);
-      slot_score[rank * G + g0 + b] = from_orderable(~(unsigned int)(key >> 32));     // the key holds the score bit for bit
+      slot_idx[rank * G + g0 + b] = key_index(key);
+      slot_score[rank * G + g0 + b] = key_score(key);
     }
     __syncthreads();
   }
@@ -570,7 +573,7 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
   int nk = 0;
   if (STAGED) {
     for (int t = tid; t < n; t += blockDim.x) {
-      const int row = slot_idx[(int)(keys[t] & 0xFFFFFFFFu)];
+      const int row = slot_idx[key_index(keys[t])];
       sbox[t] = *(const float4*)(boxes + (long)row * 4);
       sup[t] = 0;
     }
@@ -594,22 +597,22 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
       __syncthreads();                         // flags final; everybody holds box t in registers
       if (tid == 0) {                          // the kept boxes are the prefix of the sorted list (nk <= t: slots already consumed)
         const unsigned long long key = keys[t];
-        const int slot = (int)(key & 0xFFFFFFFFu);
+        const int slot = key_index(key);
         sbox[nk] = bp;
         pgt_index[nk] = slot_idx[slot]; pgt_class[nk] = gt_classes[slot % G];
-        pgt_score[nk] = from_orderable(~(unsigned int)(key >> 32));
+        pgt_score[nk] = key_score(key);
       }
       ++nk; ++t;
     }
   } else {
     for (int t = 0; t < n; ++t) {
-      const int p = (int)(keys[t] & 0xFFFFFFFFu);
+      const int p = key_index(keys[t]);
       if (sup[p]) continue;                                               // uniform across the workgroup
       if (tid == 0) { pgt_index[nk] = c_idx[p]; pgt_class[nk] = c_cls[p]; pgt_score[nk] = c_score[p]; }
       ++nk;
       const float* bp = boxes + (long)c_idx[p] * 4;
       for (int u = t + 1 + tid; u < n; u += blockDim.x) {
-        const int q = (int)(keys[u] & 0xFFFFFFFFu);
+        const int q = key_index(keys[u]);
         if (!sup[q] && iou_nms(bp, boxes + (long)c_idx[q] * 4) > nms_thresh) sup[q] = 1;
       }
       __syncthreads();
@@ -688,6 +691,86 @@ __device__ __forceinline__ float clipf(float v, float hi) { return fminf(fmaxf(v
 // sw_detect_postprocess as +0.0.
 __device__ __forceinline__ float det_score(float s) { return s == 0.f ? 0.f : s; }
 
+// ---------------------------------------------------------------- what the chunked NMS forms share
+// (det_class_nms_kernel: a workgroup per class; det_mask_kernel + det_resolve_kernel: the chip per class; tta_merge_kernel: a wave per class)
+// proposal `row`'s class-c box clipped to the image, and a box moved by its class's offset as torchvision batched_nms forms it
+__device__ __forceinline__ float4 det_box(const float* __restrict__ boxes, long row, int K, int c, float imw, float imh) {
+  const float* b = boxes + row * 4 * K + 4 * c;
+  return make_float4(clipf(b[0], imw), clipf(b[1], imh), clipf(b[2], imw), clipf(b[3], imh));
+}
+__device__ __forceinline__ float4 offset_box(float4 b, float off) {
+  return make_float4(__fadd_rn(b.x, off), __fadd_rn(b.y, off), __fadd_rn(b.z, off), __fadd_rn(b.w, off));
+}
+// IoU(a, b) > thresh; pos_thresh = (thresh >= 0) is the caller's, worked out once per kernel
+__device__ __forceinline__ bool nms_over(float4 a, float4 b, float thresh, bool pos_thresh) {
+  return pos_thresh ? iou_nms_above((const float*)&a, (const float*)&b, thresh) : iou_nms((const float*)&a, (const float*)&b) > thresh;
+}
+// lane k's box to every lane (k wave-uniform): v_readlane, no LDS access
+__device__ __forceinline__ float4 lane_box(float4 v, int k) {
+  return make_float4(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.x), k)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.y), k)),
+                     __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.z), k)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.w), k)));
+}
+// compaction by ballot: the slot of an `ok` lane in a list whose length *count is (LDS); any order, one atomic per wave
+__device__ __forceinline__ int compact_slot(bool ok, int* count) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long m = __ballot(ok);
+  int base = 0;
+  if (lane == 0 && m) base = atomicAdd(count, __popcll(m));
+  base = __shfl(base, 0);
+  return base + __popcll(m & ((1ull << lane) - 1));
+}
+// serial walk over a chunk of 64 sorted candidates on wave-uniform 64-bit masks (scalar registers): take the first live candidate, drop
+// what its row suppresses (bit j of myrow in lane i: candidate i suppresses candidate j > i); row i lives in lane i and is fetched by
+// v_readlane.  Returns the kept candidates.  CUT: at most `room` of them (the callers that stop at topk).
+template <bool CUT>
+__device__ __forceinline__ unsigned long long resolve_chunk(unsigned long long alive, unsigned long long myrow, int room = 0) {
+  unsigned long long kept = 0;
+  const int row_lo = (int)(unsigned int)myrow, row_hi = (int)(unsigned int)(myrow >> 32);
+  int n = 0;                                                          // CUT only (counted up: one scalar instruction less per step than room--)
+  while (alive && (!CUT || n < room)) {
+    const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(alive));
+    const unsigned long long ri = (unsigned long long)(unsigned int)__builtin_amdgcn_readlane(row_lo, i) |
+                                  ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane(row_hi, i) << 32);
+    kept |= 1ull << i;
+    if (CUT) ++n;
+    alive &= ~(ri | (1ull << i));
+  }
+  return kept;
+}
+// a chunk's kept candidates to the class's list behind the nk0 already there; *key (this lane's sort key) is read by kept lanes only
+__device__ __forceinline__ void emit_kept(unsigned long long kept, int lane, const unsigned long long* key, int* __restrict__ rows,
+                                          float* __restrict__ scores, int nk0) {
+  if ((kept >> lane) & 1ull) {
+    const int o = nk0 + __popcll(kept & ((1ull << lane) - 1));
+    rows[o] = key_index(*key);
+    scores[o] = key_score(*key);                                      // the key holds the score bit for bit
+  }
+}
+// later candidates against a chunk's kept boxes: a lane holds one candidate (64 per wave and pass: u0 = first, first + stride, .. < end),
+// the kept boxes come out of the registers of the lanes that hold the chunk (kv, v_readlane): no LDS access and no divergence inside the
+// loop over the kept boxes.  (A wave-per-candidate form — one broadcast LDS read, 64 tests, one ballot — was bound by the LDS latency of
+// each step: 23 us per chunk against 1 us for the chunk's own 64 x 64 matrix.)  c0: any valid position, read by lanes with nothing to test
+__device__ __forceinline__ void suppress_later(float4 kv, unsigned long long kept, const float4* sb, unsigned char* sup, int c0, int first,
+                                               int end, int stride, float thresh, bool pos_thresh) {
+  const int lane = threadIdx.x & 63;
+  const unsigned int klo = __builtin_amdgcn_readfirstlane((unsigned int)kept), khi = __builtin_amdgcn_readfirstlane((unsigned int)(kept >> 32));
+  for (int u0 = first; u0 < end; u0 += stride) {
+    const int u = u0 + lane;
+    const bool live = u < end && !sup[u];
+    if (!__ballot(live)) continue;
+    const float4 b = sb[live ? u : c0];
+    bool hit = false;
+#pragma unroll
+    for (int half = 0; half < 2; ++half)
+      for (unsigned int m = half ? khi : klo; m; m &= m - 1) {
+        const int k = __builtin_amdgcn_readfirstlane(__builtin_ctz(m)) + 32 * half;
+        const float4 a = lane_box(kv, k);
+        hit = hit || nms_over(a, b, thresh, pos_thresh);
+      }
+    if (live && hit) sup[u] = 1;
+  }
+}
+
 // max coordinate over the clipped boxes that pass the score filter (boxes.max() inside batched_nms)
 __global__ void det_maxcoord_kernel(int R, int K, float thresh, float imw, float imh, const float* __restrict__ scores,
                                     const float* __restrict__ boxes, float* __restrict__ out) {
@@ -696,8 +779,8 @@ __global__ void det_maxcoord_kernel(int R, int K, float thresh, float imw, float
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const long r = i / K; const int c = (int)(i - r * K);
     if (scores[r * (K + 1) + c] > thresh) {
-      const float* b = boxes + r * 4 * K + 4 * c;
-      m = fmaxf(m, fmaxf(fmaxf(clipf(b[0], imw), clipf(b[2], imw)), fmaxf(clipf(b[1], imh), clipf(b[3], imh))));
+      const float4 b = det_box(boxes, r, K, c, imw, imh);
+      m = fmaxf(m, fmaxf(fmaxf(b.x, b.z), fmaxf(b.y, b.w)));
     }
   }
   m = wave_reduce_max(m);
@@ -734,11 +817,8 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
   for (int i0 = 0; i0 < R; i0 += blockDim.x) {                      // compaction (any order: the keys are unique, the sort orders them)
     const int i = i0 + tid;
     const bool ok = i < R && scores[(long)i * (K + 1) + c] > thresh;
-    const unsigned long long m = __ballot(ok);
-    int base = 0;
-    if (lane == 0 && m) base = atomicAdd(&s_valid, __popcll(m));
-    base = __shfl(base, 0);
-    if (ok) keys[base + __popcll(m & ((1ull << lane) - 1))] = make_key(det_score(scores[(long)i * (K + 1) + c]), (unsigned)i);
+    const int slot = compact_slot(ok, &s_valid);
+    if (ok) keys[slot] = make_key(det_score(scores[(long)i * (K + 1) + c]), (unsigned)i);
     if (i < R) sup[i] = 0;
   }
   __syncthreads();
@@ -753,11 +833,8 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
     if (nv >= mask_min) {
       for (int u = tid; u < nv; u += blockDim.x) {
         const unsigned long long key = keys[u];
-        const int q = (int)(key & 0xFFFFFFFFu);
-        const float* bq = boxes + (long)q * 4 * K + 4 * c;
         skeys[(long)c * R + u] = key;
-        sboxes[(long)c * R + u] = make_float4(__fadd_rn(clipf(bq[0], imw), off), __fadd_rn(clipf(bq[1], imh), off),
-                                              __fadd_rn(clipf(bq[2], imw), off), __fadd_rn(clipf(bq[3], imh), off));
+        sboxes[(long)c * R + u] = offset_box(det_box(boxes, key_index(key), K, c, imw, imh), off);
       }
       if (tid == 0) nvalid[c] = nv;
       return;
@@ -767,85 +844,33 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
   if ((long)nv * 16 + 16 <= (long)(NP - nv) * 8) {
     float4* sb = (float4*)(((uintptr_t)(keys + nv) + 15) & ~(uintptr_t)15);
     for (int u = tid; u < nv; u += blockDim.x) {
-      const int q = (int)(keys[u] & 0xFFFFFFFFu);
-      const float* bq = boxes + (long)q * 4 * K + 4 * c;
-      sb[u] = make_float4(__fadd_rn(clipf(bq[0], imw), off), __fadd_rn(clipf(bq[1], imh), off), __fadd_rn(clipf(bq[2], imw), off),
-                          __fadd_rn(clipf(bq[3], imh), off));
+      sb[u] = offset_box(det_box(boxes, key_index(keys[u]), K, c, imw, imh), off);
       sup[u] = 0;                                                   // here the flags go by sorted position
     }
     __syncthreads();
     for (int c0 = 0; c0 < nv; c0 += 64) {
       if (s_nk >= topk) break;                                      // uniform (s_nk is written before the barriers below)
       const int cn = min(64, nv - c0);
+      const bool in = lane < cn;
+      const float4 bv = sb[c0 + (in ? lane : 0)];
       // chunk matrix: bit j of s_row[i] = IoU(box c0+i, box c0+j) > nms_thresh
-      {
-        const bool in = lane < cn;
-        const float4 bv = sb[c0 + (in ? lane : 0)];
-        float b[4] = {bv.x, bv.y, bv.z, bv.w};
-        for (int r = 0; r < 4; ++r) {
-          const int i = wave * 4 + r;
-          if (i < cn) {                                             // wave-uniform
-            const float4 av = sb[c0 + i];
-            float a[4] = {av.x, av.y, av.z, av.w};
-            const unsigned long long m = __ballot(in && lane > i && (pos_thresh ? iou_nms_above(a, b, nms_thresh) : iou_nms(a, b) > nms_thresh));
-            if (lane == 0) s_row[i] = m;
-          }
+      for (int r = 0; r < 4; ++r) {
+        const int i = wave * 4 + r;
+        if (i < cn) {                                               // wave-uniform
+          const unsigned long long m = __ballot(in && lane > i && nms_over(sb[c0 + i], bv, nms_thresh, pos_thresh));
+          if (lane == 0) s_row[i] = m;
         }
       }
       __syncthreads();
       if (wave == 0) {
-        // serial walk over the chunk on wave-uniform 64-bit masks (scalar registers): take the first live candidate, drop what
-        // its row suppresses; row i lives in lane i and is fetched by v_readlane
-        unsigned long long alive = __ballot(lane < cn && !sup[c0 + lane]);
-        unsigned long long kept = 0;
         const int nk0 = __builtin_amdgcn_readfirstlane(s_nk);
-        int nk = nk0;
-        const unsigned long long myrow = lane < cn ? s_row[lane] : 0ull;
-        const int row_lo = (int)(unsigned int)myrow, row_hi = (int)(unsigned int)(myrow >> 32);
-        while (alive && nk < topk) {
-          const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(alive));
-          const unsigned long long ri = (unsigned long long)(unsigned int)__builtin_amdgcn_readlane(row_lo, i) |
-                                        ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane(row_hi, i) << 32);
-          kept |= 1ull << i; ++nk;
-          alive &= ~(ri | (1ull << i));
-        }
-        if ((kept >> lane) & 1ull) {
-          const int o = nk0 + __popcll(kept & ((1ull << lane) - 1));
-          const unsigned long long key = keys[c0 + lane];
-          cls_rows[c * topk + o] = (int)(key & 0xFFFFFFFFu);
-          cls_scores[c * topk + o] = from_orderable(~(unsigned int)(key >> 32));            // the key holds the score bit for bit
-        }
-        if (lane == 0) { s_kept = kept; s_nk = nk; }
+        const unsigned long long kept = resolve_chunk<true>(__ballot(in && !sup[c0 + lane]), in ? s_row[lane] : 0ull, topk - nk0);
+        emit_kept(kept, lane, keys + c0 + lane, cls_rows + c * topk, cls_scores + c * topk, nk0);
+        if (lane == 0) { s_kept = kept; s_nk = nk0 + __popcll(kept); }
       }
       __syncthreads();
       const unsigned long long kept = s_kept;
-      if (kept && s_nk < topk) {
-        // later candidates against the chunk's kept boxes: a lane holds one candidate (64 per wave and pass), the kept boxes
-        // come out of the registers of the lanes that hold the chunk (v_readlane): no LDS access and no divergence inside the
-        // loop over the kept boxes.  (A wave-per-candidate form — one broadcast LDS read, 64 tests, one ballot — was bound by
-        // the LDS latency of each step: 23 us per chunk against 1 us for the chunk's own 64 x 64 matrix.)
-        const unsigned int klo = __builtin_amdgcn_readfirstlane((unsigned int)kept), khi = __builtin_amdgcn_readfirstlane((unsigned int)(kept >> 32));
-        const float4 kv = sb[c0 + (lane < cn ? lane : 0)];
-        for (int u0 = c0 + 64 + wave * 64; u0 < nv; u0 += 16 * 64) {
-          const int u = u0 + lane;
-          const bool live = u < nv && !sup[u];
-          if (!__ballot(live)) continue;
-          const float4 bv = sb[live ? u : c0];
-          float b[4] = {bv.x, bv.y, bv.z, bv.w};
-          bool hit = false;
-#pragma unroll
-          for (int half = 0; half < 2; ++half)
-            for (unsigned int m = half ? khi : klo; m; m &= m - 1) {
-              const int k = __builtin_amdgcn_readfirstlane(__builtin_ctz(m)) + 32 * half;
-              float a[4] = {__int_as_float(__builtin_amdgcn_readlane(__float_as_int(kv.x), k)),
-                            __int_as_float(__builtin_amdgcn_readlane(__float_as_int(kv.y), k)),
-                            __int_as_float(__builtin_amdgcn_readlane(__float_as_int(kv.z), k)),
-                            __int_as_float(__builtin_amdgcn_readlane(__float_as_int(kv.w), k))};
-              hit = hit || (pos_thresh ? iou_nms_above(a, b, nms_thresh) : iou_nms(a, b) > nms_thresh);
-            }
-          if (live && hit) sup[u] = 1;
-        }
-      }
+      if (kept && s_nk < topk) suppress_later(bv, kept, sb, sup, c0, c0 + 64 + wave * 64, nv, 16 * 64, nms_thresh, pos_thresh);
       __syncthreads();
     }
     if (tid == 0) cls_count[c] = s_nk;
@@ -853,20 +878,16 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
   }
   int nk = 0;
   for (int t = 0; t < nv && nk < topk; ++t) {
-    const int p = (int)(keys[t] & 0xFFFFFFFFu);
+    const int p = key_index(keys[t]);
     if (sup[p]) continue;
     if (tid == 0) { cls_rows[c * topk + nk] = p; cls_scores[c * topk + nk] = det_score(scores[(long)p * (K + 1) + c]); }
     ++nk;
-    const float* bp = boxes + (long)p * 4 * K + 4 * c;
-    float a[4] = {__fadd_rn(clipf(bp[0], imw), off), __fadd_rn(clipf(bp[1], imh), off), __fadd_rn(clipf(bp[2], imw), off),
-                  __fadd_rn(clipf(bp[3], imh), off)};
+    const float4 a = offset_box(det_box(boxes, p, K, c, imw, imh), off);
     for (int u = t + 1 + tid; u < nv; u += blockDim.x) {
-      const int q = (int)(keys[u] & 0xFFFFFFFFu);
+      const int q = key_index(keys[u]);
       if (sup[q]) continue;
-      const float* bq = boxes + (long)q * 4 * K + 4 * c;
-      float b[4] = {__fadd_rn(clipf(bq[0], imw), off), __fadd_rn(clipf(bq[1], imh), off), __fadd_rn(clipf(bq[2], imw), off),
-                    __fadd_rn(clipf(bq[3], imh), off)};
-      if (iou_nms(a, b) > nms_thresh) sup[q] = 1;
+      const float4 b = offset_box(det_box(boxes, q, K, c, imw, imh), off);
+      if (iou_nms((const float*)&a, (const float*)&b) > nms_thresh) sup[q] = 1;
     }
     __syncthreads();
   }
@@ -907,15 +928,11 @@ __global__ __launch_bounds__(64) void det_mask_kernel(int R, int K, float nms_th
     s_col[lane] = j0 + lane < nv ? sb[j0 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
     if (i < nv) {
-      const float4 av = sb[i];
-      float a[4] = {av.x, av.y, av.z, av.w};
+      const float4 a = sb[i];
       const int jn = min(64, nv - j0);
       unsigned long long bits = 0;
-      for (int jj = max(0, i + 1 - j0); jj < jn; ++jj) {
-        const float4 bv = s_col[jj];
-        float b[4] = {bv.x, bv.y, bv.z, bv.w};
-        if (pos_thresh ? iou_nms_above(a, b, nms_thresh) : iou_nms(a, b) > nms_thresh) bits |= 1ull << jj;
-      }
+      for (int jj = max(0, i + 1 - j0); jj < jn; ++jj)
+        if (nms_over(a, s_col[jj], nms_thresh, pos_thresh)) bits |= 1ull << jj;
       MT[((long)c * NB + cb) * R + i] = bits;
     }
   }
@@ -958,24 +975,10 @@ __global__ __launch_bounds__(256) void det_resolve_kernel(int R, int K, int topk
                                          (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)lo);
       const int i = w * 64 + lane;
       const unsigned long long myrow = i < nv ? (i < RES_CAP ? buf[i] : col[(long)w * R + i]) : 0ull;
-      unsigned long long alive = __ballot(i < nv) & ~removed;
-      unsigned long long kept = 0;
       const int nk0 = __builtin_amdgcn_readfirstlane(s_nk);
-      int nk = nk0;
-      const int row_lo = (int)(unsigned int)myrow, row_hi = (int)(unsigned int)(myrow >> 32);
-      while (alive && nk < topk) {
-        const int b = __builtin_amdgcn_readfirstlane(__builtin_ctzll(alive));
-        const unsigned long long ri = (unsigned long long)(unsigned int)__builtin_amdgcn_readlane(row_lo, b) |
-                                      ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane(row_hi, b) << 32);
-        kept |= 1ull << b; ++nk;
-        alive &= ~(ri | (1ull << b));
-      }
-      if ((kept >> lane) & 1ull) {
-        const int o = nk0 + __popcll(kept & ((1ull << lane) - 1));
-        const unsigned long long key = skeys[(long)c * R + i];
-        cls_rows[c * topk + o] = (int)(key & 0xFFFFFFFFu);
-        cls_scores[c * topk + o] = from_orderable(~(unsigned int)(key >> 32));
-      }
+      const unsigned long long kept = resolve_chunk<true>(__ballot(i < nv) & ~removed, myrow, topk - nk0);
+      emit_kept(kept, lane, skeys + (long)c * R + i, cls_rows + c * topk, cls_scores + c * topk, nk0);
+      const int nk = nk0 + __popcll(kept);
       if (lane == 0) { s_keptm[w & 255] = kept; s_nk = nk; s_stop = nk >= topk ? 1 : 0; }
     }
     __syncthreads();
@@ -1007,14 +1010,11 @@ __global__ __launch_bounds__(1024) void det_merge_kernel(int K, int topk, float 
   bitonic_sort<true>(keys, NP);
   const int n = min(s_n, topk);
   for (int t = tid; t < n; t += blockDim.x) {
-    const unsigned int pos = (unsigned int)(keys[t] & 0xFFFFFFFFu);
+    const unsigned int pos = (unsigned int)key_index(keys[t]);
     const int r = pos / K, c = pos - r * K;
-    const float* b = boxes + (long)r * 4 * K + 4 * c;
-    det_boxes[4 * t + 0] = clipf(b[0], imw); det_boxes[4 * t + 1] = clipf(b[1], imh);
-    det_boxes[4 * t + 2] = clipf(b[2], imw); det_boxes[4 * t + 3] = clipf(b[3], imh);
-    // score: recover from the sorted key (exact bits)
-    const unsigned int ob = ~(unsigned int)(keys[t] >> 32);
-    det_scores[t] = __uint_as_float((ob & 0x80000000u) ? (ob & 0x7FFFFFFFu) : ~ob);
+    const float4 b = det_box(boxes, r, K, c, imw, imh);
+    det_boxes[4 * t + 0] = b.x; det_boxes[4 * t + 1] = b.y; det_boxes[4 * t + 2] = b.z; det_boxes[4 * t + 3] = b.w;
+    det_scores[t] = key_score(keys[t]);
     det_classes[t] = c; det_rows[t] = r;
   }
   if (tid == 0) det_count[0] = n;
@@ -1033,11 +1033,25 @@ __global__ __launch_bounds__(1024) void det_merge_kernel(int K, int topk, float 
 // the survivors by score descending, then union index ascending, cut at topk (det_class_nms_kernel / det_merge_kernel's rule).
 // One sort key carries class | score bits | union index (10 + 32 + 11 bits: K <= 1024, V * T <= 2048), so ONE bitonic sort yields every class
 // segment in score order; the waves take the classes round-robin and resolve a segment in chunks of 64 sorted candidates (the chunk's
-// 64 x 64 matrix by ballots, the serial walk on wave-uniform masks, later candidates against the chunk's kept boxes out of registers: the
-// scheme of det_class_nms_kernel with a wave in the place of the workgroup, no barrier inside).  Survivors get a (score, union index)
-// key in place, a second sort orders them, the first topk are written (the box recomputed from its row: the LDS copy carries the class
-// offset).  A counts[v] outside [0, T] poisons the call: det_count = -1, nothing else written, nothing read beyond the arrays.
+// 64 x 64 matrix by ballots, then resolve_chunk and suppress_later as in det_class_nms_kernel, with a wave in the place of the workgroup and
+// no barrier inside).  Survivors get a (score, union index) key in place (tta_survivor_key), a second sort orders them, the first topk
+// are written (the box recomputed from its row: the LDS copy carries the class offset).  A counts[v] outside [0, T] poisons
+// the call: det_count = -1, nothing else written, nothing read beyond the arrays.
 constexpr int TTA_NMAX = 2048, TTA_KMAX = 1024;
+constexpr int bits_for(int n) { int b = 0; while ((1 << b) < n) ++b; return b; }       // values 0 .. n-1
+constexpr int TTA_INDEX_BITS = bits_for(TTA_NMAX), TTA_CLASS_BITS = bits_for(TTA_KMAX), TTA_CLASS_SHIFT = TTA_INDEX_BITS + 32;
+constexpr unsigned long long TTA_INDEX_MASK = (1ull << TTA_INDEX_BITS) - 1;
+static_assert(TTA_INDEX_BITS + 32 + TTA_CLASS_BITS <= 64 && TTA_NMAX <= (1 << TTA_INDEX_BITS) && TTA_KMAX <= (1 << TTA_CLASS_BITS),
+              "class | score bits | union index must fit one 64-bit sort key");
+__device__ __forceinline__ unsigned long long tta_key(int cls, float score, int i) {
+  return ((unsigned long long)cls << TTA_CLASS_SHIFT) | ((unsigned long long)(~orderable(score)) << TTA_INDEX_BITS) | (unsigned long long)i;
+}
+__device__ __forceinline__ int tta_key_class(unsigned long long key) { return (int)(key >> TTA_CLASS_SHIFT); }
+__device__ __forceinline__ int tta_key_index(unsigned long long key) { return (int)(key & TTA_INDEX_MASK); }
+// the class dropped: make_key's (score desc, union index asc) form
+__device__ __forceinline__ unsigned long long tta_survivor_key(unsigned long long key) {
+  return (((key >> TTA_INDEX_BITS) & 0xFFFFFFFFull) << 32) | (key & TTA_INDEX_MASK);
+}
 struct TtaRow { float b[4]; float score; int cls; bool keep; };
 __device__ __forceinline__ TtaRow tta_row(int i, int T, int K, const float* __restrict__ boxes, const float* __restrict__ scores,
                                           const int* __restrict__ classes, const float* __restrict__ view_tab, float imw, float imh) {
@@ -1095,13 +1109,9 @@ __global__ __launch_bounds__(1024) void tta_merge_kernel(int V, int T, int K, fl
       r = tta_row(i, T, K, boxes, scores, classes, view_tab, imw, imh);
       ok = r.keep;
     }
-    const unsigned long long bm = __ballot(ok);
-    int base = 0;
-    if (lane == 0 && bm) base = atomicAdd(&s_valid, __popcll(bm));
-    base = __shfl(base, 0);
+    const int slot = compact_slot(ok, &s_valid);
     if (ok) {
-      keys[base + __popcll(bm & ((1ull << lane) - 1))] =
-          ((unsigned long long)r.cls << 43) | ((unsigned long long)(~orderable(r.score)) << 11) | (unsigned long long)i;
+      keys[slot] = tta_key(r.cls, r.score, i);
       m = fmaxf(m, fmaxf(fmaxf(r.b[0], r.b[2]), fmaxf(r.b[1], r.b[3])));
     }
   }
@@ -1120,13 +1130,12 @@ __global__ __launch_bounds__(1024) void tta_merge_kernel(int V, int T, int K, fl
   const float maxp1 = __fadd_rn(__uint_as_float(s_max), 1.0f);
   for (int u = tid; u < nv; u += blockDim.x) {
     const unsigned long long key = keys[u];
-    const int c = (int)(key >> 43), i = (int)(key & 2047u);
-    const TtaRow r = tta_row(i, T, K, boxes, scores, classes, view_tab, imw, imh);
-    const float off = __fmul_rn((float)c, maxp1);
-    sb[u] = make_float4(__fadd_rn(r.b[0], off), __fadd_rn(r.b[1], off), __fadd_rn(r.b[2], off), __fadd_rn(r.b[3], off));
+    const int c = tta_key_class(key);
+    const TtaRow r = tta_row(tta_key_index(key), T, K, boxes, scores, classes, view_tab, imw, imh);
+    sb[u] = offset_box(make_float4(r.b[0], r.b[1], r.b[2], r.b[3]), __fmul_rn((float)c, maxp1));
     sup[u] = 0;
-    if (u == 0 || (int)(keys[u - 1] >> 43) != c) seg_lo[c] = (unsigned short)u;
-    if (u == nv - 1 || (int)(keys[u + 1] >> 43) != c) seg_hi[c] = (unsigned short)(u + 1);
+    if (u == 0 || tta_key_class(keys[u - 1]) != c) seg_lo[c] = (unsigned short)u;
+    if (u == nv - 1 || tta_key_class(keys[u + 1]) != c) seg_hi[c] = (unsigned short)(u + 1);
   }
   __syncthreads();
   int my_keep = 0;
@@ -1136,52 +1145,18 @@ __global__ __launch_bounds__(1024) void tta_merge_kernel(int V, int T, int K, fl
       const int cn = min(64, hi - c0);
       const bool in = lane < cn;
       const float4 bv = sb[c0 + (in ? lane : 0)];
-      float b[4] = {bv.x, bv.y, bv.z, bv.w};
-      unsigned long long alive = __ballot(in && !sup[c0 + lane]);
+      const unsigned long long alive = __ballot(in && !sup[c0 + lane]);
       unsigned long long myrow = 0ull;
       for (unsigned long long rem = alive; rem; rem &= rem - 1) {   // rows of the live candidates only: a dead one suppresses nothing
         const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(rem));
-        float a[4] = {__int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.x), i)),
-                      __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.y), i)),
-                      __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.z), i)),
-                      __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.w), i))};
-        const unsigned long long rm = __ballot(in && lane > i && (pos_thresh ? iou_nms_above(a, b, nms_thresh) : iou_nms(a, b) > nms_thresh));
+        const float4 a = lane_box(bv, i);
+        const unsigned long long rm = __ballot(in && lane > i && nms_over(a, bv, nms_thresh, pos_thresh));
         if (lane == i) myrow = rm;
       }
-      unsigned long long kept = 0;
-      const int row_lo = (int)(unsigned int)myrow, row_hi = (int)(unsigned int)(myrow >> 32);
-      while (alive) {
-        const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(alive));
-        const unsigned long long ri = (unsigned long long)(unsigned int)__builtin_amdgcn_readlane(row_lo, i) |
-                                      ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane(row_hi, i) << 32);
-        kept |= 1ull << i;
-        alive &= ~(ri | (1ull << i));
-      }
-      if (in) {                                                     // survivors: make_key's (score desc, union index asc) form
-        const unsigned long long key = keys[c0 + lane];
-        keys[c0 + lane] = ((kept >> lane) & 1ull) ? (((key >> 11) & 0xFFFFFFFFull) << 32) | (key & 2047ull) : ~0ull;
-      }
+      const unsigned long long kept = resolve_chunk<false>(alive, myrow);
+      if (in) keys[c0 + lane] = ((kept >> lane) & 1ull) ? tta_survivor_key(keys[c0 + lane]) : ~0ull;
       my_keep += __popcll(kept);
-      const unsigned int klo = __builtin_amdgcn_readfirstlane((unsigned int)kept), khi = __builtin_amdgcn_readfirstlane((unsigned int)(kept >> 32));
-      for (int u0 = c0 + 64; u0 < hi; u0 += 64) {                    // later candidates of the class against this chunk's kept boxes
-        const int u = u0 + lane;
-        const bool live = u < hi && !sup[u];
-        if (!__ballot(live)) continue;
-        const float4 lv = sb[live ? u : c0];
-        float q[4] = {lv.x, lv.y, lv.z, lv.w};
-        bool hit = false;
-#pragma unroll
-        for (int half = 0; half < 2; ++half)
-          for (unsigned int km = half ? khi : klo; km; km &= km - 1) {
-            const int k = __builtin_amdgcn_readfirstlane(__builtin_ctz(km)) + 32 * half;
-            float a[4] = {__int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.x), k)),
-                          __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.y), k)),
-                          __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.z), k)),
-                          __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv.w), k))};
-            hit = hit || (pos_thresh ? iou_nms_above(a, q, nms_thresh) : iou_nms(a, q) > nms_thresh);
-          }
-        if (live && hit) sup[u] = 1;
-      }
+      suppress_later(bv, kept, sb, sup, c0, c0 + 64, hi, 64, nms_thresh, pos_thresh);   // the class's later candidates only
       // the wave reads its own sup[] writes in the next chunk: the LDS serves one wave's requests in issue order
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -1192,8 +1167,7 @@ __global__ __launch_bounds__(1024) void tta_merge_kernel(int V, int T, int K, fl
   bitonic_sort<true>(keys, NP);
   const int n = min(s_keep, topk);
   for (int t = tid; t < n; t += blockDim.x) {
-    const unsigned long long key = keys[t];
-    const int i = (int)(key & 2047u);
+    const int i = key_index(keys[t]);
     const TtaRow r = tta_row(i, T, K, boxes, scores, classes, view_tab, imw, imh);
     det_boxes[4 * t + 0] = r.b[0]; det_boxes[4 * t + 1] = r.b[1]; det_boxes[4 * t + 2] = r.b[2]; det_boxes[4 * t + 3] = r.b[3];
     det_scores[t] = r.score; det_classes[t] = r.cls; det_src[t] = i;
@@ -1279,25 +1253,21 @@ extern "C" int sw_oicr_refine_loss(int V, int R, int K, int n_rounds, const floa
   return 0;
 }
 
-static int mine_np(int R, int top_k, int G) {
-  const long need = R > (long)top_k * G ? R : (long)top_k * G;
-  int np = 64;
-  while (np < need) np <<= 1;
-  return np;
-}
-static int mine_npr(int R) { int np = 64; while (np < R) np <<= 1; return np; }
+constexpr size_t LDS_BUDGET = 144 * 1024;        // dynamic LDS a mining launch may ask for (of the CU's 160 KB; the kernel has static LDS too)
+// (sw_oicr_mine_label refuses more than 2^22 rows or slots; the clamp keeps the size query defined beyond that)
+static int mine_np(int R, int top_k, int G) { return next_pow2((int)std::min(std::max((long)R, (long)top_k * G), 1L << 30)); }
 static size_t mine_staged_lds(int R, int top_k, int G, int batch = 1) {        // keys + 25 bytes per slot (mine_label_kernel<true>)
-  const size_t nkeys = std::max((size_t)mine_np(R, top_k, G), (size_t)batch * mine_npr(R));
+  const size_t nkeys = std::max((size_t)mine_np(R, top_k, G), (size_t)batch * next_pow2(R));
   return nkeys * 8 + (size_t)top_k * G * 25 + 16;
 }
-static bool mine_staged(int R, int top_k, int G) { return mine_staged_lds(R, top_k, G) <= 144 * 1024; }
+static bool mine_staged(int R, int top_k, int G) { return mine_staged_lds(R, top_k, G) <= LDS_BUDGET; }
 static int mine_class_batch(int R, int top_k, int G) {          // score columns sorted side by side: as many as LDS holds, <= 8
   int b = 1;
-  while (b < G && b < 8 && mine_staged_lds(R, top_k, G, b + 1) <= 144 * 1024) ++b;
+  while (b < G && b < 8 && mine_staged_lds(R, top_k, G, b + 1) <= LDS_BUDGET) ++b;
   return b;
 }
 static bool mine_keys_in_ws(int R, int top_k, int G) {
-  return !mine_staged(R, top_k, G) && (size_t)mine_np(R, top_k, G) * 8 + (size_t)top_k * G > 144 * 1024;
+  return !mine_staged(R, top_k, G) && (size_t)mine_np(R, top_k, G) * 8 + (size_t)top_k * G > LDS_BUDGET;
 }
 extern "C" long sw_mine_workspace_bytes(int R, int top_k, int G) {
   long b = (((long)top_k * G * 20 + 64) + 15) / 16 * 16;
@@ -1318,7 +1288,7 @@ extern "C" int sw_oicr_mine_label(int R, int ncol, int K, int n_rounds, const fl
   const int in_ws = mine_keys_in_ws(R, top_k, G) ? 1 : 0;
   const int batch = staged ? mine_class_batch(R, top_k, G) : 1;
   const size_t lds = staged ? mine_staged_lds(R, top_k, G, batch) : (in_ws ? 0 : (size_t)np * 8) + (size_t)top_k * G;
-  if (lds > 144 * 1024) return -6;
+  if (lds > LDS_BUDGET) return -6;
   auto kern = staged ? mine_label_kernel<true> : mine_label_kernel<false>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
@@ -1356,19 +1326,32 @@ extern "C" int sw_oicr_predict(int R, int K, int refine_k, const float* logits, 
 
 namespace {
 inline long align256(long v) { return (v + 255) / 256 * 256; }
-// workspace of the per-class form: maxcoord (+pad) | cls_count [K] | cls_rows [K][topk] | cls_scores [K][topk]; the mask form's part follows it
-inline long detect_base_bytes(int K, int topk) { return align256((long)K * topk * 8 + (long)K * 4 + 64); }
-// extra workspace of the mask form: nvalid[K] | sorted keys [K][R] | sorted boxes [K][R] float4 | MT [K][NB][R] u64; 0 = not offered
-inline long detect_mask_bytes(int R, int K) {
-  if (R < 1 || K < 1 || R > 16384) return 0;
-  const long NB = (R + 63) / 64;
-  if (NB > 256) return 0;
-  const long b = align256((long)K * 4) + align256((long)K * R * 8) + align256((long)K * R * 16) + (long)K * NB * R * 8;
-  return b <= (96L << 20) ? b : 0;
-}
+// The detection workspace, as byte offsets.  Per-class form: maxcoord (+pad to 64 B) | cls_count [K] | cls_rows [K][topk] | cls_scores [K][topk],
+// base_bytes in all; the mask form's part follows it, each array on a 256-byte boundary: nvalid [K] | skeys [K][R] u64 | sboxes [K][R] float4 |
+// MT [K][NB][R] u64, mask_bytes in all (0 = the mask form is not offered at this R, K)
+struct DetectWorkspace {
+  long cls_count, cls_rows, cls_scores, base_bytes, nvalid, skeys, sboxes, MT, mask_bytes;
+  DetectWorkspace(int R, int K, int topk) {
+    cls_count = 64;
+    cls_rows = cls_count + (long)K * 4;
+    cls_scores = cls_rows + (long)K * topk * 4;
+    base_bytes = align256(cls_scores + (long)K * topk * 4);
+    const bool offered = R >= 1 && K >= 1 && R <= 16384;             // at most 256 column blocks (det_resolve_kernel's s_keptm)
+    const long r = offered ? R : 0, NB = (r + 63) / 64;
+    nvalid = base_bytes;
+    skeys = nvalid + align256((long)K * 4);
+    sboxes = skeys + align256(K * r * 8);
+    MT = sboxes + align256(K * r * 16);
+    mask_bytes = MT + K * NB * r * 8 - base_bytes;
+    if (!offered || mask_bytes > (96L << 20)) mask_bytes = 0;
+  }
+};
 }  // namespace
 
-extern "C" long sw_detect_workspace_bytes(int R, int K, int topk) { return detect_base_bytes(K, topk) + detect_mask_bytes(R, K); }
+extern "C" long sw_detect_workspace_bytes(int R, int K, int topk) {
+  const DetectWorkspace w(R, K, topk);
+  return w.base_bytes + w.mask_bytes;
+}
 
 extern "C" int sw_detect_postprocess(int R, int K, const float* all_scores, const float* all_boxes, int img_h, int img_w,
                                      float score_thresh, float nms_thresh, int topk, int32_t* det_count, float* det_boxes,
@@ -1377,10 +1360,11 @@ extern "C" int sw_detect_postprocess(int R, int K, const float* all_scores, cons
   SW_ENTER();
   if (R > 16384 || (long)K * topk > 16384 || topk < 1) return -6;
   char* ws = (char*)workspace;
-  float* maxcoord = (float*)ws;                                    // [1] (+pad)
-  int* cls_count = (int*)(ws + 64);                                // [K]
-  int* cls_rows = cls_count + K;                                   // [K][topk]
-  float* cls_scores = (float*)(cls_rows + (long)K * topk);         // [K][topk]
+  const DetectWorkspace w(R, K, topk);
+  float* maxcoord = (float*)ws;
+  int* cls_count = (int*)(ws + w.cls_count);
+  int* cls_rows = (int*)(ws + w.cls_rows);
+  float* cls_scores = (float*)(ws + w.cls_scores);
   hipError_t e = hipMemsetAsync(maxcoord, 0, 64, stream);
   if (e != hipSuccess) return (int)e;
   if (R <= 0) return (int)hipMemsetAsync(det_count, 0, 4, stream);
@@ -1389,16 +1373,13 @@ extern "C" int sw_detect_postprocess(int R, int K, const float* all_scores, cons
   hipLaunchKernelGGL(det_maxcoord_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, R, K, score_thresh, (float)img_w,
                      (float)img_h, all_scores, all_boxes, maxcoord);
   SW_CHECK_LAUNCH();
-  int np = 64; while (np < R) np <<= 1;
   constexpr int mask_min = 256;
-  const long base = detect_base_bytes(K, topk), mask_need = detect_mask_bytes(R, K);
-  const bool mask = mask_need > 0 && workspace_bytes >= base + mask_need && R >= mask_min;
-  char* m = ws + base;
-  int* nvalid = mask ? (int*)m : nullptr; m += align256((long)K * 4);
-  unsigned long long* skeys = (unsigned long long*)m; m += align256((long)K * R * 8);
-  float4* sboxes = (float4*)m; m += align256((long)K * R * 16);
-  unsigned long long* MT = (unsigned long long*)m;
-  const size_t lds1 = (size_t)np * 8 + (size_t)R;
+  const bool mask = w.mask_bytes > 0 && workspace_bytes >= w.base_bytes + w.mask_bytes && R >= mask_min;
+  int* nvalid = mask ? (int*)(ws + w.nvalid) : nullptr;
+  unsigned long long* skeys = (unsigned long long*)(ws + w.skeys);
+  float4* sboxes = (float4*)(ws + w.sboxes);
+  unsigned long long* MT = (unsigned long long*)(ws + w.MT);
+  const size_t lds1 = (size_t)next_pow2(R) * 8 + (size_t)R;
   e = hipFuncSetAttribute((const void*)det_class_nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(det_class_nms_kernel, dim3(K), dim3(1024), lds1, stream, R, K, score_thresh, nms_thresh, topk,
@@ -1416,8 +1397,7 @@ extern "C" int sw_detect_postprocess(int R, int K, const float* all_scores, cons
                        cls_scores);
     SW_CHECK_LAUNCH();
   }
-  int np2 = 64; while (np2 < K * topk) np2 <<= 1;
-  const size_t lds2 = (size_t)np2 * 8;
+  const size_t lds2 = (size_t)next_pow2(K * topk) * 8;
   e = hipFuncSetAttribute((const void*)det_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(det_merge_kernel, dim3(1), dim3(1024), lds2, stream, K, topk, (float)img_w, (float)img_h, all_boxes,

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_tta_merge_cpu import CASES, load_case  # noqa: E402
+from test_tta_merge_cpu import CASES, edge_case, load_case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -92,6 +92,20 @@ def test_bad_count_and_limits_raise(ops, golden_dir):
     with pytest.raises(ValueError):
         ops.tta_merge(*ok, 100, 100, 0.5, 100, 1025)
     assert ops.tta_merge_count(ops.tta_merge(*ok, 100, 100, 0.5, 100, 1024)[0]) == 0           # at both limits, every count 0
+
+
+@pytest.mark.parametrize("name", ["negative_nms", "chunk_edges"])
+def test_edge_case_equals_the_restatement(ops, name):
+    """negative_nms: the plain `iou > thresh` of a threshold below zero, empty boxes included; chunk_edges: classes of 63, 64, 65 and 129
+    candidates through the wave-per-class resolver (test_tta_merge_cpu asserts what each case reaches).  Count, source rows, classes, score
+    bits and box bits, every element"""
+    c, want = edge_case(name)
+    cnt, boxes, scores, classes, src = run(ops, c)
+    assert ops.tta_merge_count(cnt) == int(want["count"][0])
+    assert np.array_equal(src.cpu().numpy(), want["src"])
+    assert np.array_equal(classes.cpu().numpy(), want["classes"])
+    assert np.array_equal(scores.cpu().numpy().view(np.uint32), want["scores"].view(np.uint32))
+    assert np.array_equal(boxes.cpu().numpy().view(np.uint32), want["boxes"].view(np.uint32))
 
 
 def test_one_class_at_the_row_limit(ops):
