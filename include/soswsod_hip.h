@@ -209,9 +209,12 @@ int sw_roi_pool_fwd(int dtype, int nimg, int H, int W, int C, int PH, int PW, fl
  * dout_absmax (device scalar >= max|dout|, e.g. from sw_absmax or a GEMM epilogue; may be NULL): selects the fixed-point LDS
  * accumulation (one 64-bit word per pixel-channel in f32 mode, a hi / lo pair of 32-bit words in bf16 mode: >= 25 bits per term;
  * bitwise reproducible, ~3x faster than LDS float atomics); NULL => f32 atomics.
+ * A NaN or Inf anywhere in dout (through dout_absmax) or in row_scale + row_scale_add makes the fixed-point path write NaN to
+ * every element of dfeat; the f32 atomics carry it to the elements it reaches.
  * ld_in: row pitch (elements) of dout AND argmax, 0 = C*PH*PW.
  * spatial_scale: the forward's scale, or 0.  With it, on maps whose accumulators need several pixel ranges per plane, a
- * workgroup streams only the ROIs whose rows reach its range (any value yields the same result; 0 streams all ROIs). */
+ * workgroup streams only the ROIs whose bin rows, formed as the forward forms them, reach its range (0 streams all ROIs; the
+ * forward's scale and 0 yield the same bits). */
 int sw_roi_pool_bwd(int dtype, int nimg, int H, int W, int C, int PH, int PW, const void* dout,
                     const void* argmax, int argmax_bits, long ld_in, const float* rois, int R, const float* row_scale,
                     float row_scale_add, const void* relu_ref, const float* dout_absmax, void* dfeat, float spatial_scale,

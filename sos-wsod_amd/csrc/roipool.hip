@@ -367,7 +367,7 @@ constexpr int FX_CHUNK = 1024;          // ROIs per compaction round of the fixe
 //      bits per term (27 at R_image = 2000, 25 at 4000: 2^-26 of the largest term against bf16's 2^-8 outputs), still without the
 //      emulated f32 -> i64 conversion (the kernel is VALU-issue bound: 88 M wave instructions per 4000 ROIs).
 template <typename T, typename IT, int ACCMODE>
-__global__ __launch_bounds__(1024) void roi_pool_bwd_fx_kernel(int H, int W, int C, long ld, int nb, int CB,
+__global__ __launch_bounds__(1024) void roi_pool_bwd_fx_kernel(int H, int W, int C, long ld, int PH, int PW, int CB,
                                                                const T* __restrict__ dout, const IT* __restrict__ argmax,
                                                                const float* __restrict__ rois, int R,
                                                                const float* __restrict__ row_scale, float row_scale_add,
@@ -379,7 +379,7 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_fx_kernel(int H, int W, int
   __shared__ int s_cnt;
   // large maps: the workgroup owns only the pixel range [p0, p1) of the plane (blockIdx.z); gradients whose argmax falls
   // outside are skipped (the other ranges' workgroups stream the same ROI data again)
-  const int npix_all = H * W;
+  const int npix_all = H * W, nb = PH * PW;
   const int px_per = (npix_all + gridDim.z - 1) / gridDim.z;
   const int p0 = blockIdx.z * px_per, p1 = min(npix_all, p0 + px_per);
   typedef typename std::conditional<ACCMODE == 0, unsigned long long, unsigned int>::type ACC;
@@ -391,13 +391,17 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_fx_kernel(int H, int W, int
   const int npix = max(p1 - p0, 0);
   for (int i = threadIdx.x; i < npix * CB * (ACCMODE == 2 ? 2 : 1); i += blockDim.x) acc[i] = (ACC)0;     // mode 2: hi words, then lo words
   float smax = 0.f;                                             // max |row_scale + add| (wave/block reduce, tiny)
-  if (row_scale) { for (int r = threadIdx.x; r < R; r += blockDim.x) smax = fmaxf(smax, fabsf(row_scale[r] + row_scale_add)); }
-  else smax = 1.f;
+  if (row_scale) {
+    for (int r = threadIdx.x; r < R; r += blockDim.x) {
+      const float m = fabsf(row_scale[r] + row_scale_add);
+      smax = fmaxf(smax, m != m ? INFINITY : m);                // fmaxf drops a NaN: it counts as Inf, and poisons the slab below
+    }
+  } else smax = 1.f;
   smax = block_reduce_max(smax, red);
   smax = __shfl(smax, 0, 64);
   const float bound = dout_absmax[0] * smax;
-  // A diverged gradient (NaN / Inf anywhere in dout: its |max| is then NaN or Inf) must stay visible: the integer conversion
-  // would turn NaN into 0 and saturate Inf, so the whole slab is written as NaN instead.
+  // A diverged gradient (NaN / Inf anywhere in dout: its |max| is then NaN or Inf) or row scale (smax is then Inf) must stay
+  // visible: the integer conversion would turn NaN into 0 and saturate Inf, so the whole slab is written as NaN instead.
   const bool poisoned = !(bound < 3.0e38f);
   // Terms per accumulator: a pixel-channel can be the argmax of EVERY bin of a ROI whose bins are smaller than a pixel (ROIs
   // narrower than PW feature pixels: MIN_SIZE 20 at stride 8), so the bound is nb per ROI of this image — not the 4 of
@@ -433,11 +437,12 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_fx_kernel(int H, int W, int
       if ((int)rois[(long)r * 5] == img) {
         if (gridDim.z > 1 && spatial_scale > 0.f) {
           // large maps (several pixel ranges per plane): a workgroup lists only the ROIs whose rows can reach its range — every
-          // argmax of a ROI lies in rows [rs, max(re, rs)] (ROILoopPool_cpu.cpp:36-52) — instead of streaming the gradients of
-          // ALL ROIs of the image once per range (99x165 map, 2 x 4000 ROIs, 4 ranges: 765 -> ~400 us)
-          const int rs = (int)roundf(__fmul_rn(rois[(long)r * 5 + 2], spatial_scale));
-          const int re = max((int)roundf(__fmul_rn(rois[(long)r * 5 + 4], spatial_scale)), rs);
-          if (re < p0 / W || rs > (p1 - 1) / W) continue;
+          // argmax of a ROI lies in the rows from its first bin's start to its last bin's end, as the forward forms them (the
+          // last bin's float32 end can lie a row past the ROI's own end row: heights 57, 114, 121, ... at 7 bins) — instead of
+          // streaming the gradients of ALL ROIs of the image once per range (99x165 map, 2 x 4000 ROIs, 4 ranges: 765 -> ~400 us)
+          const RoiGeom g = roi_geom(rois + (long)r * 5, spatial_scale, PH, PW);
+          const int row_lo = g.start_h + bin_unclipped(g.bin_h, 0).s, row_hi = g.start_h + bin_unclipped(g.bin_h, PH - 1).e;   // [lo, hi)
+          if (row_hi <= p0 / W || row_lo > (p1 - 1) / W) continue;
         }
         const int k = atomicAdd(&s_cnt, 1);
         s_r[k] = r;
@@ -452,8 +457,17 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_fx_kernel(int H, int W, int
         int crow[4];
         {
           const int q0 = (j * 4) / nb, rem0 = j * 4 - q0 * nb;
+          if (nb >= 4) {                                           // the lane's 4 elements span at most 2 channels
 #pragma unroll
-          for (int e = 0; e < 4; ++e) crow[e] = (q0 + (rem0 + e >= nb ? 1 : 0)) * npix;
+            for (int e = 0; e < 4; ++e) crow[e] = (q0 + (rem0 + e >= nb ? 1 : 0)) * npix;
+          } else {                                                 // up to 4 channels (nb = 1): carried element by element
+            int rem = rem0, row = q0 * npix;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              crow[e] = row;
+              if (++rem == nb) { rem = 0; row += npix; }
+            }
+          }
         }
         u32x4 av[8]; u32x4 dv[8];
 #pragma unroll
@@ -1546,6 +1560,7 @@ template <typename T, typename IT>
 int roi_bwd_dispatch(int nimg, int H, int W, int C, long ld, int PH, int PW, const void* dout, const void* argmax, const float* rois,
                      int R, const float* row_scale, float row_scale_add, const void* relu_ref, const float* dout_absmax,
                      void* dfeat, float spatial_scale, hipStream_t stream) {
+  // (tests/roipool_ref.py: bwd_plan mirrors this function; the backward's tests assert it before every launch — change both together)
   // fixed-point path: CB in {8, 4} with H*W*CB*8 bytes of LDS; needs max|dout| (device scalar)
   // bf16: a hi/lo pair of 32-bit accumulators (see the kernel) when PH*PW*R terms (every bin of every ROI on one pixel: the worst
   // case) leave >= 8 bits per word; fp32: one 64-bit word
@@ -1564,7 +1579,7 @@ int roi_bwd_dispatch(int nimg, int H, int W, int C, long ld, int PH, int PW, con
     const int px_per = (H * W + nsplit - 1) / nsplit;
     const size_t ldsx = (size_t)px_per * cbx * ab + FX_CHUNK * 8;
     auto k = accmode == 2 ? roi_pool_bwd_fx_kernel<T, IT, 2> : roi_pool_bwd_fx_kernel<T, IT, 0>;
-    return launch(k, dim3(C / cbx, nimg, nsplit), dim3(1024), ldsx, stream, H, W, C, ld, PH * PW, cbx, (const T*)dout, (const IT*)argmax, rois,
+    return launch(k, dim3(C / cbx, nimg, nsplit), dim3(1024), ldsx, stream, H, W, C, ld, PH, PW, cbx, (const T*)dout, (const IT*)argmax, rois,
                   R, row_scale, row_scale_add, dout_absmax, (const T*)relu_ref, (T*)dfeat, spatial_scale);
   }
   // float-atomic path: channel slab per workgroup a power of two, H*W*CB*4 <= 64 KiB (two 1024-thread workgroups per
