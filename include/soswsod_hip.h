@@ -667,6 +667,31 @@ int sw_det_loss_per_image(int n_img, long n_anchors, const float* rpn_logits, co
 int sw_pgf_keep(int n_img, const int64_t* det_off, const double* boxes, const double* scores, const int32_t* classes, int K,
                 const uint32_t* gt_mask, const uint32_t* diff_mask, double t_keep, double t_con, int use_diff, uint8_t* keep,
                 uint8_t* workspace, long long* counts, sw_stream_t stream);
+/* The same filter at every cell of a grid t_keep[nk] x t_con[nc], each cell's kept detections matched against the split's ground
+ * truth at iou[nt] and counted per class (replaces one run of the loops of tools/pgf.py pgf :221-271 per cell, and for the matching
+ * the detection loop of evaluation/pascal_voc_evaluation.py voc_eval :357-397, whose rule is used free of detection order).
+ * Detections, K, gt_mask, diff_mask and use_diff as for sw_pgf_keep (N: the number of rows); t_keep, t_con and iou are HOST
+ * arrays of finite values, in any order, repeats allowed.  Ground truth per image (CSR): image i owns rows [gt_off[i],
+ * gt_off[i + 1]) of gt_box [G][4] f64 corners (16-byte aligned), gt_cls [G] i32 and gt_ign [G] u8 (VOC difficult / COCO iscrowd),
+ * in annotation order.  xywh != 0: a detection row is [x, y, w, h] and its matching box (x, y, x + w, y + h); otherwise the row is
+ * a VOC record [x1 + 1, y1 + 1, x2, y2] and is its own matching box (the filter reads it as [x, y, w, h] in both modes, as the
+ * reference does).  plus_one != 0: extents are VOC's `+ 1.0`.  Cell (a, b) keeps exactly what sw_pgf_keep keeps at t_keep[a],
+ * t_con[b].  A kept detection's candidates are its image's objects of its class; ovmax / jmax are numpy's max / argmax of
+ * inters / (area_det + area_gt - inters) in voc_eval's f64 operations.  With ovmax > iou[t] it counts into ign when object jmax is
+ * ignored and claims the object otherwise.  Outputs, i64, 8-byte aligned, zeroed here: kept [nk][nc][K]; tp [nt][nk][nc][K],
+ * the claimed objects; ign [nt][nk][nc][K]; npos [K], the non-ignored objects.  Integer atomic adds only: the tables do not
+ * depend on launch order.  workspace [N][SW_PGF_SWEEP_WS_WORDS] u32: used by images of more than SW_PGF_LDS_CAP detections.
+ * Refused before anything is written: -4 a misaligned pointer, -5 a negative count, -6 K, -7 a grid size outside
+ * [1, SW_PGF_SWEEP_MAX_*] or a value that is not finite. */
+#define SW_PGF_SWEEP_MAX_KEEP 32
+#define SW_PGF_SWEEP_MAX_CON 32
+#define SW_PGF_SWEEP_MAX_IOU 10
+#define SW_PGF_SWEEP_WS_WORDS 12
+int sw_pgf_sweep(int n_img, long long N, const int64_t* det_off, const double* boxes, const double* scores, const int32_t* classes,
+                 int K, const uint32_t* gt_mask, const uint32_t* diff_mask, int use_diff, int nk, const double* t_keep, int nc,
+                 const double* t_con, int nt, const double* iou, const int64_t* gt_off, const double* gt_box, const int32_t* gt_cls,
+                 const uint8_t* gt_ign, int xywh, int plus_one, uint32_t* workspace, long long* kept, long long* tp, long long* ign,
+                 long long* npos, sw_stream_t stream);
 
 /* VOC AP and CorLoc of one split at the ten IoU thresholds (evaluation/pascal_voc_evaluation.py: the detection loops, cumulative
  * sums, precision / recall and voc_ap of voc_eval :295-408 and voc_ap :263-292, and the loop of voc_eval_corloc :411-505; these

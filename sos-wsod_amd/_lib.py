@@ -268,6 +268,9 @@ SIGNATURES = {
     # ---- Stage-2 pseudo labels (csrc/pseudo_labels.hip)
     "sw_pgf_keep": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double,
                             c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sw_pgf_sweep": (c_int, [c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                             c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # ---- VOC evaluation (csrc/evaluation.hip)
     "sw_voc_eval_workspace_bytes": (c_longlong, [c_int, c_int, c_longlong, c_longlong]),
     "sw_voc_eval": (c_int, [c_int, c_int, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1397,6 +1397,79 @@ def pgf_keep(det_off, boxes, scores, classes, K, gt_mask, diff_mask, t_keep, t_c
     return packed
 
 
+PGF_LDS_CAP, PGF_MAX_CLASSES = 256, 256                                 # SW_PGF_LDS_CAP / SW_PGF_MAX_CLASSES
+PGF_SWEEP_MAX_KEEP, PGF_SWEEP_MAX_CON, PGF_SWEEP_MAX_IOU = 32, 32, 10   # SW_PGF_SWEEP_MAX_*
+PGF_SWEEP_WS_WORDS = 12                                                 # SW_PGF_SWEEP_WS_WORDS
+
+
+def pgf_sweep_layout(nk, nc, nt, K, guard=0):
+    """Where the four tables of sw_pgf_sweep lie in the packed int64 tensor, `guard` untouched words before, between and after
+    them.  -> ({"kept": (offset, shape), "tp": ..., "ign": ..., "npos": ...}, total words)"""
+    shapes = (("kept", (nk, nc, K)), ("tp", (nt, nk, nc, K)), ("ign", (nt, nk, nc, K)), ("npos", (K,)))
+    at, out = guard, {}
+    for name, shape in shapes:
+        size = 1
+        for s in shape:
+            size *= s
+        out[name] = (at, shape)
+        at += size + guard
+    return out, at
+
+
+def pgf_sweep_unpack(host, nk, nc, nt, K, guard=0):
+    """the four tables as views of the packed tensor's host copy (a numpy int64 array)"""
+    layout, total = pgf_sweep_layout(nk, nc, nt, K, guard)
+    assert host.shape == (total,)
+    out = {}
+    for name, (at, shape) in layout.items():
+        size = 1
+        for s in shape:
+            size *= s
+        out[name] = host[at:at + size].reshape(shape)
+    return out
+
+
+def pgf_sweep(det_off, boxes, scores, classes, K, gt_mask, diff_mask, use_diff, t_keep, t_con, iou, gt_off, gt_box, gt_cls, gt_ign,
+              xywh, plus_one, guard=0, out=None):
+    """The Stage-2 filter at every cell of t_keep x t_con with voc_eval's matching at every iou, counted per cell and class
+    (sw_pgf_sweep).  Detections and masks as for pgf_keep; t_keep (<= 32), t_con (<= 32), iou (<= 10): sequences of finite floats;
+    gt_off [n_img + 1] i64, gt_box [G, 4] f64 corners, gt_cls [G] i32, gt_ign [G] u8 on the GPU.  `out` (int64, pgf_sweep_layout's
+    total words) may be passed in: tests fill it with sentinels around the tables.
+    -> packed int64 tensor on the GPU holding kept [nk, nc, K], tp [nt, nk, nc, K], ign [nt, nk, nc, K] and npos [K] — one tensor,
+    so the host reads everything with one copy; pgf_sweep_unpack splits its host copy."""
+    _need_gpu(det_off, boxes, scores, classes, gt_mask, diff_mask, gt_off, gt_box, gt_cls, gt_ign, out)
+    n_img, n, G = det_off.numel() - 1, boxes.shape[0], gt_box.shape[0]
+    words = (K + 31) // 32
+    assert det_off.dtype == torch.int64 and boxes.dtype == torch.float64 and scores.dtype == torch.float64
+    assert classes.dtype == torch.int32 and gt_mask.dtype == torch.int32 and diff_mask.dtype == torch.int32
+    assert gt_off.dtype == torch.int64 and gt_box.dtype == torch.float64 and gt_cls.dtype == torch.int32
+    assert gt_ign.dtype == torch.uint8
+    assert boxes.shape == (n, 4) and scores.shape == (n,) and classes.shape == (n,) and n_img >= 0
+    assert gt_mask.shape == (n_img, words) and diff_mask.shape == (words,)
+    assert gt_off.shape == (n_img + 1,) and gt_box.shape == (G, 4) and gt_cls.shape == (G,) and gt_ign.shape == (G,)
+    for t in (det_off, boxes, scores, classes, gt_mask, diff_mask, gt_off, gt_box, gt_cls, gt_ign):
+        assert t.is_contiguous()
+    nk, nc, nt = len(t_keep), len(t_con), len(iou)
+    # sizes the entry point refuses still need a tensor to pass: lay it out as if they were 1
+    layout, total = pgf_sweep_layout(max(nk, 1), max(nc, 1), max(nt, 1), max(int(K), 1), guard)
+    if out is None:
+        out = torch.empty(total, device=boxes.device, dtype=torch.int64)
+    assert out.dtype == torch.int64 and out.shape == (total,) and out.is_contiguous()
+    workspace = torch.empty(max(n, 1) * PGF_SWEEP_WS_WORDS, device=boxes.device, dtype=torch.int32)
+
+    def host(values):
+        return (ctypes.c_double * max(len(values), 1))(*[float(v) for v in values])
+
+    def table(name):
+        return ctypes.c_void_p(out.data_ptr() + 8 * layout[name][0])
+
+    check(lib.sw_pgf_sweep(n_img, n, _p(det_off), _p(boxes), _p(scores), _p(classes), int(K), _p(gt_mask), _p(diff_mask),
+                           int(bool(use_diff)), nk, host(t_keep), nc, host(t_con), nt, host(iou), _p(gt_off), _p(gt_box),
+                           _p(gt_cls), _p(gt_ign), int(bool(xywh)), int(bool(plus_one)), _p(workspace), table("kept"), table("tp"),
+                           table("ign"), table("npos"), _stream()), "sw_pgf_sweep")
+    return out
+
+
 VOC_THRESHOLDS = 10
 
 

@@ -50,13 +50,10 @@ def gt_classes(dataset_dicts, key=lambda image_id: image_id):
     return {i: _unique(a["category_id"] for a in ann) for i, ann in anns.items()}
 
 
-def filter_groups(groups, class_dict, t_con=T_CON, t_keep=T_KEEP, use_diff=False, diff_classes=()):
-    """Stages 3-5 of the reference (class_filter, then pgf) over {image_id: [detection dict]} on the GPU.
-    -> ({image_id: [kept detection dicts]} in the same order, stats dict)"""
-    import torch
-    from . import ops
-
-    t_con, t_keep = float(t_con), float(t_keep)
+def pack_groups(groups, class_dict, diff_classes=()):
+    """{image_id: [detection dict]} and {image_id: ground-truth classes} as the arrays the filter kernels read: detections back to
+    back in group order (CSR), the classes that occur renamed to dense indices 0..K-1, class bitmasks per image.
+    -> dict: ids, dets, off, boxes, scores, classes (dense i32), universe (the class id of each dense index), K, gt_mask, diff_mask"""
     ids = list(groups)
     dets = [d for i in ids for d in groups[i]]
     n = len(dets)
@@ -86,14 +83,27 @@ def filter_groups(groups, class_dict, t_con=T_CON, t_keep=T_KEEP, use_diff=False
         k = np.searchsorted(universe, c)
         if k < len(universe) and universe[k] == c:
             diff_mask[k >> 5] |= np.uint32(1) << np.uint32(k & 31)
+    return {"ids": ids, "dets": dets, "off": off, "boxes": boxes, "scores": scores, "universe": universe, "K": K,
+            "classes": np.searchsorted(universe, det_cls).astype(np.int32), "gt_mask": gt_mask, "diff_mask": diff_mask}
+
+
+def filter_groups(groups, class_dict, t_con=T_CON, t_keep=T_KEEP, use_diff=False, diff_classes=()):
+    """Stages 3-5 of the reference (class_filter, then pgf) over {image_id: [detection dict]} on the GPU.
+    -> ({image_id: [kept detection dicts]} in the same order, stats dict)"""
+    import torch
+    from . import ops
+
+    t_con, t_keep = float(t_con), float(t_keep)
+    g = pack_groups(groups, class_dict, diff_classes)
+    ids, dets, off, n = g["ids"], g["dets"], g["off"], len(g["dets"])
 
     dev = torch.device("cuda", torch.cuda.current_device())
 
     def up(a):
         return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
-    packed = ops.pgf_keep(up(off), up(boxes), up(scores), up(np.searchsorted(universe, det_cls).astype(np.int32)), K,
-                          up(gt_mask.view(np.int32)), up(diff_mask.view(np.int32)), t_keep, t_con, use_diff)
+    packed = ops.pgf_keep(up(off), up(g["boxes"]), up(g["scores"]), up(g["classes"]), g["K"], up(g["gt_mask"].view(np.int32)),
+                          up(g["diff_mask"].view(np.int32)), t_keep, t_con, use_diff)
     host = packed.cpu().numpy()                   # the split's one device-to-host copy
     stats = dict(zip(STAT_KEYS, (int(v) for v in host[:32].view(np.int64))))
     assert stats["before_class_filter"] == n, (stats, n)
