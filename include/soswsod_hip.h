@@ -265,13 +265,43 @@ int sw_oicr_mean_probs(int V, int R, int K, int n_rounds, const float* logits, l
  * top_k = max(int(R * MIST_P), 1) is computed by the host exactly as the reference does (:659-660).
  * workspace: >= n_rounds * sw_mine_workspace_bytes(R, top_k, G) bytes.  The sort keys live in LDS while R and top_k*G
  * are <= 16384; beyond that (COCO: PRECOMPUTED_PROPOSAL_TOPK_TRAIN 10000 with >= 17 image-level classes,
- * coco_oicr_plus.yaml:67) the workspace carries them.  Limits: R, top_k*G <= 2^22, top_k*G bytes of LDS (<= 144 KiB). */
+ * coco_oicr_plus.yaml:67) the workspace carries them.  Limits: R, top_k*G <= 2^22, top_k*G bytes of LDS (<= 144 KiB).
+ * The reference's other mining rules (all NULL / 0: the behaviour above, bit for bit, by the same kernel code):
+ *  cand_boxes, cand_from  OICRPLUS.BBOX_UPDATE True (roi_heads_oicrplus.py:398-425): class-specific candidate boxes
+ *              [n_rounds - cand_from][R][G][4] f32, 16-byte aligned (sw_oicr_update_boxes' output).  A round k >= cand_from
+ *              takes the box of the slot (rank, g) from cand_boxes[k - cand_from][row][g] instead of boxes[row]
+ *              (index_select + gather, :650-653, :675-678): the NMS runs on those boxes, and the labels' pairwise_iou is
+ *              taken between those pseudo boxes and the proposal boxes.  Rounds below cand_from read `boxes`.
+ *  seed_rule   0: top-p% + score threshold + NMS (WSL.REFINE_MIST True, get_pgt_mist :560-605).  1: WSL.REFINE_MIST False,
+ *              get_pgt_top_k with top_k = 1 (:320-323, :607-757): one seed per image-level class, the pseudo-GT list is
+ *              exactly G entries in CLASS order (score ties: lowest proposal index), score_thresh and nms_thresh are not
+ *              read and nothing is sorted by score; needs top_k == 1 (else -6).  Two classes that seed one proposal tie in
+ *              every IoU, and the first list entry = the lower class id wins the label (matcher.py: first maximum).
+ *  lab_box     [n_rounds][R][4] f32, 16-byte aligned, nullable: the matched pseudo box of every proposal, bit for bit the
+ *              box its IoU was taken with (label_and_sample_proposals' gt_boxes, roi_heads.py:327-330).
+ *  pgt_box     [n_rounds][top_k*G][4] f32, 16-byte aligned, nullable: the boxes of the kept list (first pgt_count rows).
+ * In these forms an IoU that is NaN (a pseudo box with a NaN coordinate) counts as 0, as the reference's NaN-propagating
+ * min / max / clamp and where(inter > 0, ., 0) make it (structures/boxes.py:329-361). */
 long sw_mine_workspace_bytes(int R, int top_k, int G);
 int sw_oicr_mine_label(int R, int ncol, int K, int n_rounds, const float* scores, const int32_t* gt_classes, int G,
                        const float* boxes, int top_k, float score_thresh, float nms_thresh, float iou_bg,
                        float iou_fg, int32_t* lab_class, float* lab_weight, int32_t* lab_index, int32_t* pgt_count,
                        int32_t* pgt_index, int32_t* pgt_class, float* pgt_score, void* workspace,
+                       const float* cand_boxes, int cand_from, int seed_rule, float* lab_box, float* pgt_box,
                        sw_stream_t stream);
+
+/* ---- box update: the candidate boxes of the next round (reference: OICRPLUS.BBOX_UPDATE roi_heads_oicrplus.py:398-425,
+ *      predict_boxes fast_rcnn_oicr.py, Box2BoxTransform.apply_deltas box_regression.py:73-110) ----------------------
+ * out[k][r][g][4] = apply_deltas(d, boxes[r]) for refinement head k in [0, n_heads), image-level class gt_classes[g],
+ * d = (d_0 -+ d_1 + ... -+ d_{V-1}) / V in float32, left to right, d_v = logits[(v*R+r)*ld + box_col + k*col_stride +
+ * 4*gt_classes[g] ..+4]; a view with dx_sign[v] < 0 (a flipped view) enters dx, and dx only, with a minus sign (:407-410).
+ * boxes [R][4]: view 0's proposals (the only decoded boxes the reference uses: :419-421 are dropped).  dx_sign: DEVICE
+ * int32[V] ({1,-1,1,-1}).  reg_weights4: HOST float[4]; dw, dh clamped to scale_clamp; the result is NOT clipped.
+ * Only the G image-level classes are decoded (the mining reads nothing else): out is n_heads*R*G*16 bytes, 16-byte
+ * aligned, and is sw_oicr_mine_label's cand_boxes with cand_from = 1.  A gt_classes[g] outside [0, K) gives a NaN box. */
+int sw_oicr_update_boxes(int V, int R, int K, int G, int n_heads, const float* logits, long ld, int box_col,
+                         int col_stride, const float* boxes, const int32_t* gt_classes, const int32_t* dx_sign,
+                         const float* reg_weights4, float scale_clamp, float* out, sw_stream_t stream);
 
 /* ---- OICR refinement losses + gradient (reference: OICROutputs.__init__/softmax_cross_entropy_loss/
  *      box_reg_loss fast_rcnn_oicr.py:157-226,258-273,276-352; get_deltas box_regression.py:38-71; cross-view
@@ -284,12 +314,16 @@ int sw_oicr_mine_label(int R, int ncol, int K, int n_rounds, const float* scores
  * dlogits (f32, may be NULL): the columns of every round are overwritten with
  * (grad_scale[2k]*dcls + grad_scale[2k+1]*dbox)/V; grad_scale is a DEVICE float[2*n_rounds]; reg_weights4 is a HOST
  * float[4] (BBOX_REG_WEIGHTS, a configuration constant passed by value into the launch); workspace:
- * n_rounds*2*V*R floats (per-row loss terms, summed in fixed order => deterministic losses). */
+ * n_rounds*2*V*R floats (per-row loss terms, summed in fixed order => deterministic losses).
+ * tgt_box0 (nullable; NULL: as above, bit for bit): [n_rounds][R][4] f32, the regression target box of view 0
+ * (sw_oicr_mine_label's lab_box).  With OICRPLUS.BBOX_UPDATE the matched pseudo box is a refined box and no row of the
+ * proposal list: view 0 regresses towards it (roi_heads.py:327-330), the other views keep boxes[v][lab_index]
+ * (roi_heads_oicrplus.py:327-371). */
 int sw_oicr_refine_loss(int V, int R, int K, int n_rounds, const float* logits, long ld, int cls_col, int box_col,
                         int col_stride, const float* boxes, const int32_t* lab_class, const float* lab_weight,
                         const int32_t* lab_index, const int32_t* pred_view, const float* reg_weights4,
                         float* loss_view, float* dlogits, long ld_d, const float* grad_scale, float* workspace,
-                        sw_stream_t stream);
+                        const float* tgt_box0, sw_stream_t stream);
 
 /* Stage-3 (Unbiased-Teacher) focal classification loss of the ROI heads, replaces FastRCNNFocalLoss.comput_focal_loss +
  * FocalLoss.forward (unbias/ubteacher/modeling/roi_heads/fast_rcnn.py:73-105):

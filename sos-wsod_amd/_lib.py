@@ -163,10 +163,12 @@ SIGNATURES = {
     "sw_mine_workspace_bytes": (c_long, [c_int, c_int, c_int]),
     "sw_oicr_mine_label": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_float,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_void_p]),
+                                   c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sw_oicr_update_boxes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p, _F4, c_float, c_void_p, c_void_p]),
     "sw_oicr_refine_loss": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, _F4, c_void_p, c_void_p, c_long, c_void_p,
-                                    c_void_p, c_void_p]),
+                                    c_void_p, c_void_p, c_void_p]),
     "sw_oicr_predict": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_int, c_int, c_void_p, _F4, c_float, c_void_p,
                                 c_void_p, c_void_p]),
     "sw_detect_workspace_bytes": (c_long, [c_int, c_int, c_int]),

@@ -237,6 +237,9 @@ __global__ __launch_bounds__(MP_ROWS * WS_VMAX) void mean_probs_kernel(int V, in
 // per row made every access a 4-byte strided one, 29 us for 13 MB) and serves every target view v with pred_view[v] == pv in
 // order, so the (reference-quirk) double use of view 2's logits needs no atomics.  Per-row loss terms go to a scratch array and
 // are summed in fixed order by refine_reduce_kernel (deterministic, no float atomics).
+// TGT0 (OICRPLUS.BBOX_UPDATE): view 0 regresses towards tgt_box0[round][r], the matched pseudo box itself — a refined box, no longer a
+// row of the proposal list (roi_heads.py:327-330); the other views keep their own proposal[gt_index] (roi_heads_oicrplus.py:327-371)
+template <bool TGT0>
 __global__ __launch_bounds__(256) void refine_loss_kernel(int V, int R, int K, const float* __restrict__ logits, long ld,
                                                           int cls_col, int box_col, const float* __restrict__ boxes,
                                                           const int* __restrict__ lab_class,
@@ -246,7 +249,8 @@ __global__ __launch_bounds__(256) void refine_loss_kernel(int V, int R, int K, c
                                                           float wx, float wy, float ww, float wh,
                                                           float* __restrict__ row_loss,
                                                           float* __restrict__ dlogits, long ld_d,
-                                                          const float* __restrict__ grad_scale, int col_stride) {
+                                                          const float* __restrict__ grad_scale, int col_stride,
+                                                          const float* __restrict__ tgt_box0) {
   const int pv = blockIdx.y, round = blockIdx.z;
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -282,7 +286,8 @@ __global__ __launch_bounds__(256) void refine_loss_kernel(int V, int R, int K, c
     if (fg) {                                                            // foreground: L1 on the gt-class deltas
       const float* B = boxes + (long)v * R * 4;
       const float* s = B + (long)r * 4;
-      const float* t = B + (long)lab_index[r] * 4;                       // target = this view's proposal[gt_index]
+      const float* t = (TGT0 && v == 0) ? tgt_box0 + ((long)round * R + r) * 4
+                                        : B + (long)lab_index[r] * 4;    // target = this view's proposal[gt_index]
       const float sw_ = s[2] - s[0], sh_ = s[3] - s[1];
       const float sx = s[0] + 0.5f * sw_, sy = s[1] + 0.5f * sh_;
       const float tw_ = t[2] - t[0], th_ = t[3] - t[1];
@@ -480,7 +485,25 @@ __device__ __forceinline__ float iou_pair(const float* gtb, const float* pb) {
 // (one step per kept box, ~25 at NMS 0.01) reads LDS only.  With the lists in the global workspace each kept box cost two
 // dependent L2 round trips per thread plus tid 0's three, and the label pass paid the same per pseudo box (116 us for R = 2000,
 // G = 2 — and the step waits on this kernel).  The workspace form stays for slot counts beyond LDS.
-template <bool STAGED>
+//
+// EXT (the reference's other mining rules; the EXT = false instantiations are the kernel as it was and read nothing of `ext`):
+//  - ext.cand: class-specific candidate boxes [n_rounds - cand_from][R][G][4] (sw_oicr_update_boxes' output).  A round >= cand_from
+//    takes the box of slot (rank, g) from [row][g] instead of the proposal list [row]: the NMS runs on those boxes and the labels'
+//    pairwise_iou is taken between those pseudo boxes and the PROPOSAL boxes (roi_heads_oicrplus.py:398-425, :650-653, :675-678).
+//  - ext.seed_rule 1: the classic OICR seeds, get_pgt_top_k with top_k = 1 (:320-323): the pseudo-GT list is the G rank-0 slots in
+//    class order — no threshold, no NMS sort, no NMS (the launch has top_k == 1, so every slot is a rank-0 slot).
+//  - ext.lab_box [n_rounds][R][4]: the matched pseudo box of every proposal, the very box its IoU was taken with (the regression
+//    target of view 0, roi_heads.py:327-330); ext.pgt_box [n_rounds][top_k*G][4]: the kept list's boxes.
+//  - an IoU that is NaN counts as 0, which is what the reference's NaN-propagating min / max / clamp and its where(inter > 0, ., 0)
+//    give for a pseudo box with a NaN coordinate (fminf / fmaxf drop the NaN instead, and the union then carries it)
+struct MineExt {
+  const float* cand;
+  float* lab_box;
+  float* pgt_box;
+  int cand_from, seed_rule;
+};
+
+template <bool STAGED, bool EXT>
 __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K, const float* __restrict__ scores,
                                                           const int* __restrict__ gt_classes, int G,
                                                           const float* __restrict__ boxes, int top_k, float score_thresh,
@@ -489,16 +512,29 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
                                                           int* __restrict__ lab_index, int* __restrict__ pgt_count,
                                                           int* __restrict__ pgt_index, int* __restrict__ pgt_class,
                                                           float* __restrict__ pgt_score, char* __restrict__ ws,
-                                                          long ws_stride, int keys_in_ws, int class_batch) {
+                                                          long ws_stride, int keys_in_ws, int class_batch, MineExt ext) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int n_slots = top_k * G;
+  const float* cand = nullptr;                  // EXT: this round's candidate boxes [R][G][4], or null = the proposal boxes
+  float4* lab_box = nullptr;
+  float4* pgt_box = nullptr;
+  const bool top1 = EXT && ext.seed_rule == 1;
   {                                             // one workgroup per refinement round, rounds laid out back to back
     const int round = blockIdx.x;
     scores += (long)round * R * ncol;
     lab_class += (long)round * R; lab_weight += (long)round * R; lab_index += (long)round * R;
     pgt_count += round; pgt_index += (long)round * n_slots; pgt_class += (long)round * n_slots;
     pgt_score += (long)round * n_slots; ws += (long)round * ws_stride;
+    if (EXT) {
+      if (ext.cand && round >= ext.cand_from) cand = ext.cand + (long)(round - ext.cand_from) * R * G * 4;
+      if (ext.lab_box) lab_box = (float4*)ext.lab_box + (long)round * R;
+      if (ext.pgt_box) pgt_box = (float4*)ext.pgt_box + (long)round * n_slots;
+    }
   }
+  // the candidate box of proposal `row` for image-level class number g
+  auto cand_box = [&](int row, int g) -> const float* {
+    return (EXT && cand) ? cand + ((long)row * G + g) * 4 : boxes + (long)row * 4;
+  };
   const int NP = next_pow2(R > n_slots ? R : n_slots);
   // sort keys: LDS while NP * 8 B + the suppression bytes fit (R, top_k*G <= 16384: every VOC / COCO recipe with up to 16
   // image-level classes), else a key array at the end of this round's workspace (COCO's 10000 proposals with >= 17 classes:
@@ -559,7 +595,8 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
   } else {
     for (int s = tid * per; s < min(n_slots, (tid + 1) * per); ++s) {
       if (s < G || slot_score[s] >= score_thresh) {
-        c_score[pos] = slot_score[s]; c_idx[pos] = slot_idx[s]; c_cls[pos] = gt_classes[s % G];
+        c_score[pos] = slot_score[s]; c_idx[pos] = slot_idx[s];
+        c_cls[pos] = EXT ? s % G : gt_classes[s % G];                    // EXT: the class NUMBER g (the candidate boxes' index)
         ++pos;
       }
     }
@@ -569,17 +606,25 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
   }
   if (tid == 0) s_nk = 0;
   __syncthreads();
-  if (!STAGED && keys_in_ws) bitonic_sort<false>(keys, NPN); else bitonic_sort<true>((unsigned long long*)smem, NPN);
+  if (top1) {}                                 // seed rule 1: list order is slot order, the keys stay as they were built
+  else if (!STAGED && keys_in_ws) bitonic_sort<false>(keys, NPN); else bitonic_sort<true>((unsigned long long*)smem, NPN);
   int nk = 0;
   if (STAGED) {
     for (int t = tid; t < n; t += blockDim.x) {
-      const int row = slot_idx[key_index(keys[t])];
-      sbox[t] = *(const float4*)(boxes + (long)row * 4);
+      const int slot = key_index(keys[t]);
+      const int row = slot_idx[slot];
+      sbox[t] = *(const float4*)(EXT ? cand_box(row, slot % G) : boxes + (long)row * 4);
       sup[t] = 0;
     }
     __syncthreads();
     const int lane = tid & 63;
     int t = 0;
+    if (top1) {                                // every slot is kept, in place: sbox[t] is already the list's t-th box
+      for (int s = tid; s < n; s += blockDim.x) {
+        pgt_index[s] = slot_idx[s]; pgt_class[s] = gt_classes[s % G]; pgt_score[s] = slot_score[s];
+      }
+      nk = n; t = n;
+    }
     while (true) {
       // next candidate not yet suppressed: every wave scans the same flags 64 at a time (uniform result, no barrier)
       while (t < n) {
@@ -605,21 +650,45 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
       ++nk; ++t;
     }
   } else {
-    for (int t = 0; t < n; ++t) {
+    if (top1) {
+      for (int s = tid; s < n; s += blockDim.x) {
+        pgt_index[s] = c_idx[s]; pgt_class[s] = gt_classes[c_cls[s]]; pgt_score[s] = c_score[s];
+      }
+      nk = n;
+    }
+    for (int t = top1 ? n : 0; t < n; ++t) {
       const int p = key_index(keys[t]);
       if (sup[p]) continue;                                               // uniform across the workgroup
-      if (tid == 0) { pgt_index[nk] = c_idx[p]; pgt_class[nk] = c_cls[p]; pgt_score[nk] = c_score[p]; }
+      if (tid == 0) { pgt_index[nk] = c_idx[p]; pgt_class[nk] = EXT ? gt_classes[c_cls[p]] : c_cls[p]; pgt_score[nk] = c_score[p]; }
       ++nk;
-      const float* bp = boxes + (long)c_idx[p] * 4;
+      const float* bp = EXT ? cand_box(c_idx[p], c_cls[p]) : boxes + (long)c_idx[p] * 4;
       for (int u = t + 1 + tid; u < n; u += blockDim.x) {
         const int q = key_index(keys[u]);
-        if (!sup[q] && iou_nms(bp, boxes + (long)c_idx[q] * 4) > nms_thresh) sup[q] = 1;
+        if (!sup[q] && iou_nms(bp, EXT ? cand_box(c_idx[q], c_cls[q]) : boxes + (long)c_idx[q] * 4) > nms_thresh) sup[q] = 1;
       }
       __syncthreads();
     }
   }
+  if (EXT) __threadfence();                    // seed rule 1 wrote the list with every thread
   if (tid == 0) { pgt_count[0] = nk; __threadfence(); }
   __syncthreads();
+  int* const kept_g = slot_idx;                // EXT workspace form: class number of every kept entry (the slot lists are dead by now)
+  if (EXT && !STAGED && cand) {
+    for (int j = tid; j < nk; j += blockDim.x) {
+      int g = 0;
+      while (g < G - 1 && gt_classes[g] != pgt_class[j]) ++g;
+      kept_g[j] = g;
+    }
+    __threadfence();
+    __syncthreads();
+  }
+  // the j-th kept pseudo box (workspace form: looked up again; STAGED: sbox[j])
+  auto kept_box = [&](int j) -> float4 {
+    if (STAGED) return sbox[j];
+    return *(const float4*)((EXT && cand) ? cand_box(pgt_index[j], kept_g[j]) : boxes + (long)pgt_index[j] * 4);
+  };
+  if (EXT && pgt_box)
+    for (int j = tid; j < nk; j += blockDim.x) pgt_box[j] = kept_box(j);
   // ---- 4. IoU matching + labels (pairwise_iou, Matcher [iou_bg, iou_fg] -> {0,-1,1}, roi_heads.py:225-257,266-375)
   for (int r = tid; r < R; r += blockDim.x) {
     const float4 pbv = *(const float4*)(boxes + (long)r * 4);
@@ -628,7 +697,9 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
     for (int j = 0; j < nk; ++j) {
       float v;
       if (STAGED) { const float4 gb = sbox[j]; v = iou_pair((const float*)&gb, pb); }
+      else if (EXT) { const float4 gb = kept_box(j); v = iou_pair((const float*)&gb, pb); }
       else v = iou_pair(boxes + (long)pgt_index[j] * 4, pb);
+      if (EXT && !(v == v)) v = 0.f;                                    // a NaN coordinate: where(inter > 0, ., 0) of a NaN inter
       if (v > best) { best = v; bj = j; }                               // first max = lowest pgt index
     }
     int cls; float w = 0.f; int gi = 0;
@@ -639,12 +710,30 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
       w = pgt_score[bj]; gi = pgt_index[bj];
     }
     lab_class[r] = cls; lab_weight[r] = w; lab_index[r] = gi;
+    if (EXT && lab_box) lab_box[r] = nk == 0 ? make_float4(0.f, 0.f, 0.f, 0.f) : kept_box(bj);
   }
 }
 
 // ------------------------------------------------------------------------------------------- inference (a23)
 // all_scores[r][j] = mean_k softmax(cls_score_k logits)[j]; all_boxes[r][4c..] = apply_deltas(mean_k deltas_k, proposal)
 // (predict_probs_K / predict_boxes_K fast_rcnn_oicr.py:674-735, Box2BoxTransform.apply_deltas box_regression.py:73-110)
+// Box2BoxTransform.apply_deltas (box_regression.py:73-110) against one proposal box: every multiplication and addition rounds on its
+// own, in the reference's order (the one copy of this arithmetic: predict_kernel and update_boxes_kernel decode with it)
+struct DecodeAnchor {
+  float w, h, cx, cy;
+  __device__ __forceinline__ explicit DecodeAnchor(const float* b) {
+    w = b[2] - b[0]; h = b[3] - b[1];
+    cx = b[0] + 0.5f * w; cy = b[1] + 0.5f * h;
+  }
+  __device__ __forceinline__ float4 apply(const float* d, float wx, float wy, float ww, float wh, float scale_clamp) const {
+    const float dx = __fdiv_rn(d[0], wx), dy = __fdiv_rn(d[1], wy);
+    const float dw = fminf(__fdiv_rn(d[2], ww), scale_clamp), dh = fminf(__fdiv_rn(d[3], wh), scale_clamp);
+    const float px = __fadd_rn(__fmul_rn(dx, w), cx), py = __fadd_rn(__fmul_rn(dy, h), cy);
+    const float pw = __fmul_rn(expf(dw), w), ph = __fmul_rn(expf(dh), h);
+    return make_float4(px - __fmul_rn(0.5f, pw), py - __fmul_rn(0.5f, ph), px + __fmul_rn(0.5f, pw), py + __fmul_rn(0.5f, ph));
+  }
+};
+
 __global__ __launch_bounds__(256) void predict_kernel(int R, int K, int RK, const float* __restrict__ logits, long ld,
                                                       int base_col, int round_stride, const float* __restrict__ boxes,
                                                       float wx, float wy, float ww, float wh, float scale_clamp,
@@ -664,9 +753,7 @@ __global__ __launch_bounds__(256) void predict_kernel(int R, int K, int RK, cons
     for (int j = 0; j < K1; ++j) S[j] += expf(x[j] - m) / z;
   }
   for (int j = 0; j < K1; ++j) S[j] = __fdiv_rn(S[j], (float)RK);
-  const float* b = boxes + (long)r * 4;
-  const float w = b[2] - b[0], h = b[3] - b[1];
-  const float cx = b[0] + 0.5f * w, cy = b[1] + 0.5f * h;
+  const DecodeAnchor a(boxes + (long)r * 4);
   float* O = all_boxes + (long)r * 4 * K;
   for (int c = 0; c < K; ++c) {
     float d[4];
@@ -675,13 +762,45 @@ __global__ __launch_bounds__(256) void predict_kernel(int R, int K, int RK, cons
       for (int k = 0; k < RK; ++k) acc += L[base_col + k * round_stride + K1 + 4 * c + q];   // sum in branch order (:691-693)
       d[q] = __fdiv_rn(acc, (float)RK);
     }
-    const float dx = __fdiv_rn(d[0], wx), dy = __fdiv_rn(d[1], wy);
-    const float dw = fminf(__fdiv_rn(d[2], ww), scale_clamp), dh = fminf(__fdiv_rn(d[3], wh), scale_clamp);
-    const float px = __fadd_rn(__fmul_rn(dx, w), cx), py = __fadd_rn(__fmul_rn(dy, h), cy);
-    const float pw = __fmul_rn(expf(dw), w), ph = __fmul_rn(expf(dh), h);
-    O[4 * c + 0] = px - __fmul_rn(0.5f, pw); O[4 * c + 1] = py - __fmul_rn(0.5f, ph);
-    O[4 * c + 2] = px + __fmul_rn(0.5f, pw); O[4 * c + 3] = py + __fmul_rn(0.5f, ph);
+    const float4 p = a.apply(d, wx, wy, ww, wh, scale_clamp);
+    O[4 * c + 0] = p.x; O[4 * c + 1] = p.y; O[4 * c + 2] = p.z; O[4 * c + 3] = p.w;
   }
+}
+
+// ------------------------------------------------------------------------------------------- box update (OICRPLUS.BBOX_UPDATE)
+// out[k][r][g] = apply_deltas(mean signed deltas of refinement head k over the V views, view 0's proposal r), class gt_classes[g]
+// (roi_heads_oicrplus.py:398-425): these are the class-specific candidate boxes round k+1 mines its pseudo ground truth from.  The mean
+// is the reference's float32 expression (d_0 -+ d_1 + d_2 -+ d_3) / V, left to right — a flipped view (dx_sign[v] < 0) enters dx with a
+// minus sign (:407), which is the addition of the exactly negated term — and depends on the logits only, so every round is decoded by
+// this one launch.  One thread per (head, row, image-level class); only the G image-level classes are ever read by the mining.
+__global__ __launch_bounds__(256) void update_boxes_kernel(int V, int R, int K, int G, const float* __restrict__ logits, long ld,
+                                                           int box_col, int col_stride, const float* __restrict__ boxes,
+                                                           const int* __restrict__ gt_classes, const int* __restrict__ dx_sign,
+                                                           float wx, float wy, float ww, float wh, float scale_clamp,
+                                                           float* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)R * G) return;
+  const int head = blockIdx.y, r = (int)(i / G), g = (int)(i - (long)r * G);
+  float4* o = (float4*)out + (long)head * R * G + i;
+  const int c = gt_classes[g];
+  if ((unsigned)c >= (unsigned)K) {                    // not a class of this head: no column to read; the box becomes NaN (matches nothing)
+    const float nan = __uint_as_float(0x7FC00000u);
+    *o = make_float4(nan, nan, nan, nan);
+    return;
+  }
+  const float* x = logits + (long)r * ld + box_col + head * col_stride + 4 * c;
+  float d[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    float acc = 0.f;
+    for (int v = 0; v < V; ++v) {
+      const float t = x[(long)v * R * ld + q];
+      const float s = (q == 0 && dx_sign[v] < 0) ? -t : t;
+      acc = v == 0 ? s : __fadd_rn(acc, s);
+    }
+    d[q] = __fdiv_rn(acc, (float)V);
+  }
+  *o = DecodeAnchor(boxes + (long)r * 4).apply(d, wx, wy, ww, wh, scale_clamp);
 }
 
 __device__ __forceinline__ float clipf(float v, float hi) { return fminf(fmaxf(v, 0.f), hi); }
@@ -1240,13 +1359,14 @@ extern "C" int sw_oicr_refine_loss(int V, int R, int K, int n_rounds, const floa
                                    int box_col, int col_stride, const float* boxes, const int32_t* lab_class,
                                    const float* lab_weight, const int32_t* lab_index, const int32_t* pred_view,
                                    const float* reg_weights4, float* loss_view, float* dlogits, long ld_d,
-                                   const float* grad_scale, float* workspace, hipStream_t stream) {
+                                   const float* grad_scale, float* workspace, const float* tgt_box0, hipStream_t stream) {
   SW_ENTER();
   // reg_weights4: HOST pointer (configuration constants BBOX_REG_WEIGHTS); workspace: n_rounds*2*V*R floats
   if (R <= 0 || n_rounds <= 0) return 0;
-  hipLaunchKernelGGL(refine_loss_kernel, dim3((R + 3) / 4, V, n_rounds), dim3(256), 0, stream, V, R, K, logits, ld,
-                     cls_col, box_col, boxes, lab_class, lab_weight, lab_index, pred_view, reg_weights4[0], reg_weights4[1],
-                     reg_weights4[2], reg_weights4[3], workspace, dlogits, ld_d, grad_scale, col_stride);
+  hipLaunchKernelGGL(tgt_box0 ? refine_loss_kernel<true> : refine_loss_kernel<false>, dim3((R + 3) / 4, V, n_rounds), dim3(256), 0,
+                     stream, V, R, K, logits, ld, cls_col, box_col, boxes, lab_class, lab_weight, lab_index, pred_view,
+                     reg_weights4[0], reg_weights4[1], reg_weights4[2], reg_weights4[3], workspace, dlogits, ld_d, grad_scale,
+                     col_stride, tgt_box0);
   SW_CHECK_LAUNCH();
   hipLaunchKernelGGL(refine_reduce_kernel, dim3(2 * V * n_rounds), dim3(256), 0, stream, R, workspace, loss_view);
   SW_CHECK_LAUNCH();
@@ -1279,22 +1399,28 @@ extern "C" int sw_oicr_mine_label(int R, int ncol, int K, int n_rounds, const fl
                                   int G, const float* boxes, int top_k, float score_thresh, float nms_thresh,
                                   float iou_bg, float iou_fg, int32_t* lab_class, float* lab_weight,
                                   int32_t* lab_index, int32_t* pgt_count, int32_t* pgt_index, int32_t* pgt_class,
-                                  float* pgt_score, void* workspace, hipStream_t stream) {
+                                  float* pgt_score, void* workspace, const float* cand_boxes, int cand_from, int seed_rule,
+                                  float* lab_box, float* pgt_box, hipStream_t stream) {
   SW_ENTER();
   if (R > (1 << 22) || (long)top_k * G > (1 << 22) || top_k > R || G < 1 || n_rounds < 1) return -6;
   if (((uintptr_t)boxes) & 15) return -4;                    // proposal boxes are read as float4
+  if ((((uintptr_t)cand_boxes) | ((uintptr_t)lab_box) | ((uintptr_t)pgt_box)) & 15) return -4;     // so are these, and written as float4
+  if (seed_rule < 0 || seed_rule > 1 || (seed_rule == 1 && top_k != 1) || cand_from < 0) return -6;
+  const bool ext = cand_boxes || seed_rule || lab_box || pgt_box;            // none of them: the kernel as it always was
   const int np = mine_np(R, top_k, G);
   const bool staged = mine_staged(R, top_k, G);
   const int in_ws = mine_keys_in_ws(R, top_k, G) ? 1 : 0;
   const int batch = staged ? mine_class_batch(R, top_k, G) : 1;
   const size_t lds = staged ? mine_staged_lds(R, top_k, G, batch) : (in_ws ? 0 : (size_t)np * 8) + (size_t)top_k * G;
   if (lds > LDS_BUDGET) return -6;
-  auto kern = staged ? mine_label_kernel<true> : mine_label_kernel<false>;
+  auto kern = ext ? (staged ? mine_label_kernel<true, true> : mine_label_kernel<false, true>)
+                  : (staged ? mine_label_kernel<true, false> : mine_label_kernel<false, false>);
+  const MineExt mx{cand_boxes, lab_box, pgt_box, cand_from, seed_rule};
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(kern, dim3(n_rounds), dim3(1024), lds, stream, R, ncol, K, scores, gt_classes, G, boxes,
                      top_k, score_thresh, nms_thresh, iou_bg, iou_fg, lab_class, lab_weight, lab_index, pgt_count,
-                     pgt_index, pgt_class, pgt_score, (char*)workspace, sw_mine_workspace_bytes(R, top_k, G), in_ws, batch);
+                     pgt_index, pgt_class, pgt_score, (char*)workspace, sw_mine_workspace_bytes(R, top_k, G), in_ws, batch, mx);
   SW_CHECK_LAUNCH();
   return 0;
 }
@@ -1320,6 +1446,20 @@ extern "C" int sw_oicr_predict(int R, int K, int refine_k, const float* logits, 
   hipLaunchKernelGGL(predict_kernel, dim3((R + 255) / 256), dim3(256), 0, stream, R, K, refine_k, logits, ld, base_col,
                      round_stride, boxes, reg_weights4[0], reg_weights4[1], reg_weights4[2], reg_weights4[3], scale_clamp,
                      all_scores, all_boxes);
+  SW_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sw_oicr_update_boxes(int V, int R, int K, int G, int n_heads, const float* logits, long ld, int box_col,
+                                    int col_stride, const float* boxes, const int32_t* gt_classes, const int32_t* dx_sign,
+                                    const float* reg_weights4, float scale_clamp, float* out, hipStream_t stream) {
+  SW_ENTER();
+  if (R <= 0 || n_heads <= 0) return 0;
+  if (V < 1 || G < 1 || K < 1 || R > (1 << 22) || (long)R * G > (1L << 30) || n_heads > 65535) return -6;
+  if (((uintptr_t)out) & 15) return -4;                      // one float4 store per (head, row, class)
+  hipLaunchKernelGGL(update_boxes_kernel, dim3((unsigned)(((long)R * G + 255) / 256), n_heads), dim3(256), 0, stream, V, R, K, G,
+                     logits, ld, box_col, col_stride, boxes, gt_classes, dx_sign, reg_weights4[0], reg_weights4[1],
+                     reg_weights4[2], reg_weights4[3], scale_clamp, out);
   SW_CHECK_LAUNCH();
   return 0;
 }

@@ -591,30 +591,56 @@ def mine_workspace_bytes(R, top_k, G, n_rounds=1):
 
 
 def oicr_mine_label(scores, gt_classes_i32, boxes, K, top_k, thresh, nms_thresh, iou_bg, iou_fg, lab_class, lab_weight,
-                    lab_index, pgt_count, pgt_index, pgt_class, pgt_score, workspace):
-    """scores [R][ncol] (one round) or [n_rounds][R][ncol]; the outputs carry the same leading dimension"""
+                    lab_index, pgt_count, pgt_index, pgt_class, pgt_score, workspace, *, cand_boxes=None, cand_from=0,
+                    seed_rule=0, lab_box=None, pgt_box=None):
+    """scores [R][ncol] (one round) or [n_rounds][R][ncol]; the outputs carry the same leading dimension.
+    cand_boxes [n_rounds - cand_from][R][G][4]: class-specific candidate boxes of the rounds >= cand_from (OICRPLUS.BBOX_UPDATE);
+    seed_rule 1: one seed per class in class order, no threshold, no NMS (WSL.REFINE_MIST False; top_k must be 1);
+    lab_box [n_rounds][R][4] / pgt_box [n_rounds][top_k*G][4]: the matched pseudo box of every proposal / the kept list's boxes"""
     _need_gpu(scores, gt_classes_i32, boxes)
     n_rounds = 1 if scores.dim() == 2 else scores.shape[0]
     R, ncol = scores.shape[-2:]
     G = gt_classes_i32.numel()
+    if cand_boxes is not None:
+        assert cand_boxes.dtype == torch.float32 and cand_boxes.is_contiguous() and \
+            cand_boxes.numel() == (n_rounds - cand_from) * R * G * 4, "cand_boxes is [n_rounds - cand_from][R][G][4] f32"
+    for t, rows in ((lab_box, R), (pgt_box, int(top_k) * G)):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_rounds * rows * 4)
     _launch("mine_label", lambda: check(
         lib.sw_oicr_mine_label(R, ncol, K, n_rounds, _p(scores), _p(gt_classes_i32), G, _p(boxes), int(top_k),
                                float(thresh), float(nms_thresh), float(iou_bg), float(iou_fg), _p(lab_class),
                                _p(lab_weight), _p(lab_index), _p(pgt_count), _p(pgt_index), _p(pgt_class), _p(pgt_score),
-                               _p(workspace), _stream()), "sw_oicr_mine_label"))
+                               _p(workspace), _p(cand_boxes), int(cand_from), int(seed_rule), _p(lab_box), _p(pgt_box),
+                               _stream()), "sw_oicr_mine_label"))
+
+
+def oicr_update_boxes(logits, V, R, K, n_heads, box_col, col_stride, boxes, gt_classes_i32, dx_sign, reg_weights, scale_clamp, out):
+    """out [n_heads][R][G][4] = apply_deltas(view-mean signed deltas of refinement head k, class gt_classes[g]; boxes [R][4] of view 0):
+    the next round's class-specific candidate boxes (OICRPLUS.BBOX_UPDATE).  dx_sign: device int32[V], -1 for a flipped view"""
+    _need_gpu(logits, boxes, gt_classes_i32, dx_sign, out)
+    G = gt_classes_i32.numel()
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n_heads * R * G * 4
+    assert dx_sign.dtype == torch.int32 and dx_sign.numel() == V and boxes.is_contiguous()
+    assert logits.shape[0] >= V * R and 0 <= box_col and box_col + (n_heads - 1) * col_stride + 4 * K <= logits.shape[1]
+    check(lib.sw_oicr_update_boxes(V, R, K, G, n_heads, _p(logits), logits.stride(0), box_col, col_stride, _p(boxes),
+                                   _p(gt_classes_i32), _p(dx_sign), _floats(reg_weights, 4), float(scale_clamp), _p(out),
+                                   _stream()), "sw_oicr_update_boxes")
+    return out
 
 
 def oicr_refine_loss(logits, V, R, K, cls_col, box_col, boxes, lab_class, lab_weight, lab_index, pred_view, reg_weights,
-                     loss_view, dlogits=None, grad_scale=None, workspace=None, n_rounds=1, col_stride=0):
+                     loss_view, dlogits=None, grad_scale=None, workspace=None, n_rounds=1, col_stride=0, tgt_box0=None):
     """n_rounds heads at columns cls_col/box_col + k*col_stride; lab_* [n_rounds][R]; loss_view [n_rounds][2][V];
-    grad_scale device float[2*n_rounds]"""
+    grad_scale device float[2*n_rounds]; tgt_box0 [n_rounds][R][4]: view 0's regression target boxes (OICRPLUS.BBOX_UPDATE:
+    the matched refined pseudo boxes) instead of boxes[0][lab_index]"""
     rw = _floats(reg_weights, 4)
     if workspace is None:
         workspace = torch.empty(n_rounds * 2 * V * R, device=logits.device, dtype=torch.float32)
+    assert tgt_box0 is None or (tgt_box0.dtype == torch.float32 and tgt_box0.is_contiguous() and tgt_box0.numel() == n_rounds * R * 4)
     check(lib.sw_oicr_refine_loss(V, R, K, n_rounds, _p(logits), logits.stride(0), cls_col, box_col, col_stride, _p(boxes),
                                   _p(lab_class), _p(lab_weight), _p(lab_index), _p(pred_view), rw, _p(loss_view),
                                   _p(dlogits), 0 if dlogits is None else dlogits.stride(0), _p(grad_scale), _p(workspace),
-                                  _stream()), "sw_oicr_refine_loss")
+                                  _p(tgt_box0), _stream()), "sw_oicr_refine_loss")
 
 
 def colsum(X, M, N, out, ld=None, accumulate=False):

@@ -31,6 +31,7 @@ from .box_head import DiscriminativeAdaptionNeck  # noqa: F401  (registers the b
 from .events import get_event_storage, has_event_storage
 from .fast_rcnn_oicr import OICROutputLayers
 from .fast_rcnn_wsddn import WSDDNOutputLayers
+from .inference import SCALE_CLAMP
 from .poolers import ROIPooler
 from .registry import ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY
 from .structures import ShapeSpec
@@ -209,9 +210,16 @@ class OICRPlusHeads(nn.Module):
                  cls_agnostic_bbox_reg: bool = False, pooler_type: str = "ROIPool", cfg=None, num_classes: int = 20,
                  iou_thresholds=(0.5, 0.6), iou_labels=(0, -1, 1), bbox_reg_weights=(10.0, 10.0, 5.0, 5.0),
                  test_score_thresh=1e-6, test_nms_thresh=0.3, test_topk_per_image=100,
-                 compute_dtype=torch.bfloat16, seed=-1, **unused):
+                 compute_dtype=torch.bfloat16, seed=-1, bbox_update: bool = False, **unused):
         super().__init__()
-        assert refine_mist and mist_type == "nms", "WSL.REFINE_MIST True / MIST_TYPE nms is the configured path"
+        # the reference's own get_pgt_mist_mist unpacks four values from a get_pgt_top_k call that returns five
+        # (roi_heads_oicrplus.py:484-493, :735-736) and raises on its first call: there is no behaviour to match
+        assert mist_type == "nms", \
+            "WSL.MIST_TYPE must be 'nms': 'wetectron' is refused because the reference's get_pgt_mist_mist raises on its first call " \
+            "(it unpacks four values from a get_pgt_top_k call that returns five), so there is nothing to reproduce"
+        # refine_mist True: top-p% + threshold + NMS (get_pgt_mist); False: one seed per image-level class (get_pgt_top_k, top_k = 1).
+        # bbox_update: every round >= 1 mines from the boxes the previous head's view-averaged deltas decode to (:398-425)
+        self.refine_mist, self.bbox_update = bool(refine_mist), bool(bbox_update)
         assert list(iou_labels) == [0, -1, 1] and len(iou_thresholds) == 2
         assert pooler_type == "ROIPool" and not cls_agnostic_bbox_reg
         self.box_in_features = box_in_features
@@ -306,7 +314,6 @@ class OICRPlusHeads(nn.Module):
     def from_config(cls, cfg, input_shape: Dict[str, ShapeSpec]):
         dtype = _dtype_from_cfg(cfg)
         # keys the reference acts on that this path does not implement: refuse instead of training with other numerics
-        assert not cfg.get("OICRPLUS", {}).get("BBOX_UPDATE", False), "OICRPLUS.BBOX_UPDATE True is not implemented"
         assert float(cfg.MODEL.ROI_BOX_HEAD.get("BBOX_REG_LOSS_WEIGHT", 1.0)) == 1.0, "BBOX_REG_LOSS_WEIGHT != 1 is not implemented"
         assert cfg.MODEL.ROI_BOX_HEAD.get("BBOX_REG_LOSS_TYPE", "smooth_l1") == "smooth_l1" and \
             float(cfg.MODEL.ROI_BOX_HEAD.get("SMOOTH_L1_BETA", 0.0)) == 0.0, "only smooth_l1 with beta 0 (= L1) is implemented"
@@ -331,7 +338,8 @@ class OICRPlusHeads(nn.Module):
                     bbox_reg_weights=cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS,
                     test_score_thresh=cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST,
                     test_nms_thresh=cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST,
-                    test_topk_per_image=cfg.TEST.DETECTIONS_PER_IMAGE, compute_dtype=dtype, seed=cfg.get("SEED", -1))
+                    test_topk_per_image=cfg.TEST.DETECTIONS_PER_IMAGE, compute_dtype=dtype, seed=cfg.get("SEED", -1),
+                    bbox_update=bool(cfg.get("OICRPLUS", {}).get("BBOX_UPDATE", False)))
 
     # ------------------------------------------------------------------ parameter packing
     def _flat_params(self):
@@ -526,21 +534,41 @@ class OICRPlusHeads(nn.Module):
             if RK > 1:
                 ops.oicr_mean_probs(lg, V, R, K, RK - 1, cols["cls_score0"], col_stride, mine_scores[1:])
             # --- K refinement rounds: mine pseudo-GT, label (one workgroup per round), then all rounds' losses at once
-            top_k = max(int(R * self.mist_p), 1)                      # roi_heads_oicrplus.py:659-660
+            # refine_mist: the top-p% of every image-level class (roi_heads_oicrplus.py:659-660); else one seed per class (:657-658)
+            top_k = max(int(R * self.mist_p), 1) if self.refine_mist else 1
             ws = torch.empty(ops.mine_workspace_bytes(R, top_k, G, RK), device=dev, dtype=torch.uint8)
             lab_c = torch.empty(RK, R, device=dev, dtype=torch.int32); lab_w = torch.empty(RK, R, device=dev, dtype=torch.float32)
             lab_i = torch.empty(RK, R, device=dev, dtype=torch.int32); cnt = torch.empty(RK, device=dev, dtype=torch.int32)
             pi = torch.empty(RK, top_k * G, device=dev, dtype=torch.int32); pc = torch.empty_like(pi)
             ps = torch.empty(RK, top_k * G, device=dev, dtype=torch.float32)
             boxes = inp["boxes"][b]                                   # (4, R, 4) f32
+            modes = {}                                                # the default rule passes nothing: the kernels as they always ran
+            lab_b = pb = cand = None
+            if self.bbox_update or not self.refine_mist:
+                lab_b = torch.empty(RK, R, 4, device=dev, dtype=torch.float32)
+                pb = torch.empty(RK, top_k * G, 4, device=dev, dtype=torch.float32)
+                modes = dict(seed_rule=0 if self.refine_mist else 1, lab_box=lab_b, pgt_box=pb)
+                if self.bbox_update and RK > 1:
+                    # round k+1's candidate boxes = head k's view-averaged deltas applied to view 1's proposals (:398-425): like its
+                    # scores they depend on the logits only, so one launch decodes every round and the rounds still mine side by side
+                    cand = torch.empty(RK - 1, R, G, 4, device=dev, dtype=torch.float32)
+                    ops.oicr_update_boxes(lg, V, R, K, RK - 1, cols["bbox_pred0"], col_stride, boxes[0], inp["gt_int32"][b],
+                                          inp["dx_sign"], self.bbox_reg_weights, SCALE_CLAMP, cand)
+                    modes.update(cand_boxes=cand, cand_from=1)
             ops.oicr_mine_label(mine_scores, inp["gt_int32"][b], boxes[0], K, top_k, self.mist_thre, 0.01,
-                                self.iou_thresholds[0], self.iou_thresholds[1], lab_c, lab_w, lab_i, cnt, pi, pc, ps, ws)
+                                self.iou_thresholds[0], self.iou_thresholds[1], lab_c, lab_w, lab_i, cnt, pi, pc, ps, ws, **modes)
+            # box update: view 1 regresses towards the matched refined pseudo box (roi_heads.py:327-330), the other views towards
+            # their own proposal[gt_index] as always
             ops.oicr_refine_loss(lg, V, R, K, cols["cls_score0"], cols["bbox_pred0"], boxes, lab_c, lab_w, lab_i,
                                  inp["pred_view"], self.bbox_reg_weights, loss_view[b, 1:], dl, ones, n_rounds=RK,
-                                 col_stride=col_stride)
+                                 col_stride=col_stride, tgt_box0=lab_b if cand is not None else None)
+            # lab_box / pgt_box: the matched pseudo box of every proposal and the kept list's boxes (None under the default rule, where
+            # they are boxes[0][lab_index] / boxes[0][pgt_index]); cand_boxes: the round's class-specific candidates (box update, k >= 1)
             images.append({"scores": scores, "mine_scores": mine_scores, "fc7": h2[off:off + V * R], "logits": lg,
                            "rounds": [dict(lab_class=lab_c[k], lab_weight=lab_w[k], lab_index=lab_i[k],
-                                           pgt_count=cnt[k:k + 1], pgt_index=pi[k], pgt_class=pc[k], pgt_score=ps[k])
+                                           pgt_count=cnt[k:k + 1], pgt_index=pi[k], pgt_class=pc[k], pgt_score=ps[k],
+                                           lab_box=None if lab_b is None else lab_b[k], pgt_box=None if pb is None else pb[k],
+                                           cand_boxes=None if cand is None or k == 0 else cand[k - 1])
                                       for k in range(RK)]})
         out = torch.empty(n_loss + 2, device=dev, dtype=torch.float32)     # losses | their sum | finite flag
         losses, total, finite = out[:n_loss], out[n_loss:n_loss + 1], out[n_loss + 1:]
@@ -747,7 +775,8 @@ class OICRPlusHeads(nn.Module):
         _, gt_ints, gt_oh = get_image_level_gt(targets1, K)
         if not hasattr(self, "_consts") or self._consts[0].device != device:
             self._consts = (torch.ones(max(2, 2 * self.refine_K), device=device),
-                            torch.tensor([0, 1, 2, 2], dtype=torch.int32, device=device))
+                            torch.tensor([0, 1, 2, 2], dtype=torch.int32, device=device),
+                            torch.tensor([1, -1, 1, -1], dtype=torch.int32, device=device))    # dx of a flipped view (:407)
         Rs, Gs, offs, boxes, obj, rois = [], [], [], [], [], []
         off = 0
         for b in range(B):
@@ -783,7 +812,7 @@ class OICRPlusHeads(nn.Module):
             gt_i32.append(devbuf[g0:g0 + Gs[b]].view(torch.int32)); g0 += Gs[b]
             gt_onehot.append(devbuf[nG + b * K: nG + (b + 1) * K])
         return dict(B=B, R=Rs, G=Gs, off=offs, M=off, boxes=boxes, obj=obj, rois=rois, gt_int32=gt_i32, gt_onehot=gt_onehot,
-                    ones=self._consts[0], pred_view=self._consts[1], need_grad=need_grad)
+                    ones=self._consts[0], pred_view=self._consts[1], dx_sign=self._consts[2], need_grad=need_grad)
 
     @staticmethod
     def _fill_label_host(host, gt_ints, gt_oh, nG):
