@@ -571,6 +571,7 @@ __device__ __forceinline__ typename PixWord<CB * (int)sizeof(T)>::type pix_to_ke
 
 // Dynamic LDS of the plane kernel: built from the same arguments by the kernel (which takes its pointers from it) and by the
 // launchers (which take the byte count).  rows = 0 gives the bytes beside the pixels.
+// (tests/roipool_ref.py mirrors this byte count; change both together)
 struct PlaneLds {
   size_t list, hb, wb, mul, task, bytes;
   __host__ __device__ PlaneLds(int rows, int W, int pxb, int chunk, int PH, int PW, bool band) {
@@ -912,6 +913,7 @@ __device__ __forceinline__ bool scan_window(unsigned int (&best)[CB], const u32x
 
 // Dynamic LDS of the sparse-table kernel: table planes + the image's sorted ROI list + one chunk's tables; built from the same
 // arguments by the kernel (pointers) and its launcher (bytes).  table_bytes = 0 gives the bytes beside the table.
+// (tests/roipool_ref.py mirrors this byte count; change both together)
 struct SparseLds {
   size_t lvl, r, mul, hb, wb, task, bytes;
   __host__ __device__ SparseLds(size_t table_bytes, int R, int chunk, int PH, int PW, bool band) {
@@ -1186,6 +1188,7 @@ __global__ __launch_bounds__(TK_PREP_NT) void roi_pool_tasks_kernel(int nimg, in
 
 // Dynamic LDS of the prepared-task kernel: the table of 16-byte pixels, then every wave's ring of two record slots; built from the same
 // arguments by the kernel and its launcher.  rows = 0 gives the bytes beside the table.
+// (tests/roipool_ref.py mirrors this byte count; change both together)
 struct TasksLds {
   int n_rec, slot;                                                  // records a wave's 64 consecutive items can touch, bytes of a slot
   size_t ring, bytes;
@@ -1367,6 +1370,7 @@ struct BandRule {
   bool whole_if_fits;       // fit >= H: one band of the whole map
 };
 constexpr BandRule PLANE_BANDS{8, false, false, false}, SPARSE_BANDS{8, false, false, true}, TASK_BANDS{4, true, true, true};
+// (tests/roipool_ref.py: fwd_plan mirrors this function; the forward's tests assert it before every launch — change both together)
 inline bool band_geometry(int H, int PH, int fit, const BandRule& rule, BandGeom* bg) {
   if (rule.whole_if_fits && fit >= H) { *bg = BandGeom{H, H, 1, rule.clamp_last}; return true; }
   const int halo = (H + PH - 1) / PH + 1;
@@ -1379,6 +1383,7 @@ inline bool band_geometry(int H, int PH, int fit, const BandRule& rule, BandGeom
 
 // workgroups per (slab, image, band) = how many ways the ROI chunks are dealt out: enough workgroups to fill the chip a few times
 // over (the chunks differ in work), no more (each one fetches its slab of the map)
+// (tests/roipool_ref.py: fwd_plan mirrors this function; the forward's tests assert it before every launch — change both together)
 inline int fwd_zsplit(int wg_per_z, int n_chunks, size_t lds) {
   // measured (tools/roi_bench_voc.py, workgroup target sweep): one-workgroup-per-CU slabs 512-1024 workgroups (150x200 map: 1.36 ms
   // at 1024, 1.52 at 4096), two-per-CU slabs flat from 512 to 4096
@@ -1388,8 +1393,9 @@ inline int fwd_zsplit(int wg_per_z, int n_chunks, size_t lds) {
   return nz > n_chunks ? n_chunks : nz;
 }
 
-// plane form: the whole map (bg = one band of H rows) or, BAND, row bands of 16-byte bf16 pixels
 constexpr int PLANE_NT = 1024, PLANE_CHUNK = 256;
+// plane form: the whole map (bg = one band of H rows) or, BAND, row bands of 16-byte bf16 pixels
+// (tests/roipool_ref.py: fwd_plan mirrors this function; the forward's tests assert it before every launch — change both together)
 template <typename T, int CB, typename IT, bool BAND>
 int launch_fwd_plane(int nimg, int H, int W, int C, long ld, int PH, int PW, float scale, const void* feat, const float* rois, int R,
                      const float* row_scale, float row_scale_add, void* out, void* argmax, const BandGeom& bg, hipStream_t stream) {
@@ -1403,9 +1409,12 @@ int launch_fwd_plane(int nimg, int H, int W, int C, long ld, int PH, int PW, flo
                 PLANE_CHUNK, row_scale, row_scale_add, (T*)out, (IT*)argmax, bg.S, bg.rows, bg.n_bands, nz);
 }
 // band form (bf16, 8 channels per lane): rows per band from the LDS left beside the ROI tables and the owned-pair list
+// (tests/roipool_ref.py: fwd_plan mirrors this function; the forward's tests assert it before every launch — change both together)
 inline bool plane_band_geometry(int H, int W, int PH, int PW, BandGeom* bg) {
-  const size_t budget = 160 * 1024 - 1024 - PlaneLds(0, W, 16, PLANE_CHUNK, PH, PW, true).bytes;      // 1 KiB: the kernel's static LDS + alignment
-  return PH <= 255 && band_geometry(H, PH, (int)(budget / ((size_t)W * 16)), PLANE_BANDS, bg);
+  // 1 KiB: the kernel's static LDS + alignment.  Signed: the tables of a tall pooled size (PH from about 100) are larger than a CU's
+  // LDS, and the form then declines instead of deriving a band count from a wrapped-around difference
+  const long budget = 160 * 1024 - 1024 - (long)PlaneLds(0, W, 16, PLANE_CHUNK, PH, PW, true).bytes;
+  return PH <= 255 && budget > 0 && band_geometry(H, PH, (int)(budget / ((long)W * 16)), PLANE_BANDS, bg);
 }
 
 template <typename IT, int CB, bool BAND>
@@ -1417,6 +1426,7 @@ int launch_sparse_kernel(int nimg, int H, int W, int C, long ld, int PH, int PW,
                 rois, R, row_scale, row_scale_add, (unsigned short*)out, (IT*)argmax, bg.S, bg.rows, bg.n_bands, nz, SP_CH);
 }
 
+// (tests/roipool_ref.py: fwd_plan mirrors this function; the forward's tests assert it before every launch — change both together)
 template <typename IT>
 int launch_fwd_sparse(int nimg, int H, int W, int C, long ld, int PH, int PW, float scale, const void* feat, const float* rois, int R,
                       const float* row_scale, float row_scale_add, void* out, void* argmax, hipStream_t stream) {
@@ -1460,11 +1470,13 @@ inline size_t tasks_geo_bytes(int R) { return (((size_t)R * sizeof(RoiGeo)) + 25
 inline size_t tasks_hist_bytes(int nimg, int R) {
   return ((((size_t)(R + TK_PREP_NT - 1) / TK_PREP_NT) * (size_t)nimg * TK_MAXB * SP_NCLS * 4) + 255) & ~(size_t)255;
 }
+// (tests/roipool_ref.py: fwd_plan mirrors this function; the forward's tests assert it before every launch — change both together)
 inline bool tasks_shape_ok(int dtype, int nimg, int H, int W, int C, int PH, int PW, int R, const void* feat) {
   return dtype == SW_BF16 && nimg > 0 && (C % 8) == 0 && (long)H * W < 65535 && H <= 255 && W <= 255 && R <= 65535 && PH <= 8 && PW <= 8 &&
          (((uintptr_t)feat) & 15) == 0;
 }
 
+// (tests/roipool_ref.py: fwd_plan mirrors this function; the forward's tests assert it before every launch — change both together)
 template <typename IT>
 int launch_fwd_tasks(int nimg, int H, int W, int C, long ld, int PH, int PW, float scale, const void* feat, const float* rois, int R,
                      const float* row_scale, float row_scale_add, void* out, void* argmax, void* workspace, hipStream_t stream) {
@@ -1503,6 +1515,7 @@ int launch_fwd_tasks(int nimg, int H, int W, int C, long ld, int PH, int PW, flo
                 bg.n_bands, nz);
 }
 
+// (tests/roipool_ref.py: fwd_plan mirrors this function; the forward's tests assert it before every launch — change both together)
 template <typename IT>
 int roi_fwd_dispatch(int dtype, int nimg, int H, int W, int C, long ld, int PH, int PW, float spatial_scale, const void* feat,
                      const float* rois, int R, const float* row_scale, float row_scale_add, void* out, void* argmax,
@@ -1515,8 +1528,12 @@ int roi_fwd_dispatch(int dtype, int nimg, int H, int W, int C, long ld, int PH, 
   const size_t es = dtype == SW_BF16 ? 2 : 4;
   if (nimg > 0 && (((uintptr_t)feat) & 15) == 0 && H <= 255 && W <= 255) {      // 8-bit bin tables
     int pxb = 0;
+    // (the ROI tables grow with the pooled size: 9 KiB at 7 x 7, 10 KiB at 9 x 7 — with a plane at the top of its 150 KiB that is 4 bytes
+    // more than a CU has, and the launch fails; 256: the kernel's 208 bytes of static LDS)
     for (int cand = 16; cand >= 4 && !pxb; cand >>= 1)
-      if ((C % (cand / (int)es)) == 0 && (size_t)H * W * cand <= 150 * 1024) pxb = cand;
+      if ((C % (cand / (int)es)) == 0 && (size_t)H * W * cand <= 150 * 1024 &&
+          PlaneLds(H, W, cand, PLANE_CHUNK, PH, PW, false).bytes <= 160 * 1024 - 256)
+        pxb = cand;
     // row sparse table form (bf16, packed candidates): the whole map at 32 B per pixel (8 channels per lane), else row bands at 16 B
     // per pixel (4 channels per lane)
     if (dtype == SW_BF16 && (C % 8) == 0 && (long)H * W < 65535 && R <= 16384 && PH <= 8 && PW <= 8) {
@@ -1593,11 +1610,13 @@ int roi_bwd_dispatch(int nimg, int H, int W, int C, long ld, int PH, int PW, con
 }
 }  // namespace
 
+// (tests/roipool_ref.py mirrors this byte count; change both together)
 extern "C" long sw_roi_pool_fwd_workspace_bytes(int nimg, int R, int PH, int PW) {
   if (nimg <= 0 || R <= 0 || PH <= 0 || PW <= 0) return 0;
   return (long)(tasks_seg_bytes(nimg) + tasks_geo_bytes(R) + tasks_hist_bytes(nimg, R)) + (long)nimg * R * PH * 32;
 }
 
+// (tests/roipool_ref.py: fwd_plan mirrors this function; the forward's tests assert it before every launch — change both together)
 extern "C" int sw_roi_pool_fwd(int dtype, int nimg, int H, int W, int C, int PH, int PW, float spatial_scale,
                                const void* feat, const float* rois, int R, const float* row_scale,
                                float row_scale_add, void* out, void* argmax, int argmax_bits, long ld_out,
