@@ -104,17 +104,11 @@ __device__ __forceinline__ void point_ops(int& r, int& g, int& b, const sw_aug_r
 // ---- erasing: byte(255 * n), n ~ N(0, 1) from a counter-based generator: four rounds of splitmix64 over
 // (seed, image key, erasing index * 4 + channel, (y - top) << 32 | (x - left)), two 24-bit uniforms, Box-Muller; the float is
 // truncated toward zero and wrapped modulo 256 (torch's CPU .byte()).  A sample depends on nothing but its coordinates.
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 __device__ __forceinline__ int erase_byte(const sw_aug_recipe& R, int e, int c, int dy, int dx) {
-  uint64_t h = splitmix64(R.seed);
-  h = splitmix64(h ^ R.key);
-  h = splitmix64(h ^ (uint64_t)(e * 4 + c));
-  h = splitmix64(h ^ (((uint64_t)(uint32_t)dy << 32) | (uint64_t)(uint32_t)dx));
+  uint64_t h = sw_splitmix64(R.seed);
+  h = sw_splitmix64(h ^ R.key);
+  h = sw_splitmix64(h ^ (uint64_t)(e * 4 + c));
+  h = sw_splitmix64(h ^ (((uint64_t)(uint32_t)dy << 32) | (uint64_t)(uint32_t)dx));
   const float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777216.0f);          // (0, 1]
   const float u2 = (float)(uint32_t)((h >> 16) & 0xFFFFFFu) * (1.0f / 16777216.0f);     // [0, 1)
   const float n = sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);

@@ -25,6 +25,58 @@ __device__ __forceinline__ unsigned short f32_to_bf16_bits(float f) {
   return __builtin_bit_cast(unsigned short, h);
 }
 
+// two floats as one word of two bf16 (a in the low half)
+__device__ __forceinline__ unsigned int pack_bf16x2(float a, float b) {
+  return (unsigned)f32_to_bf16_bits(a) | ((unsigned)f32_to_bf16_bits(b) << 16);
+}
+
+// Hash dropout: element i of a tensor is kept when dropout_uniform(splitmix64(seed) + offset, i) >= p.  The keep-mask kernel and the
+// GEMM epilogues draw from this one definition, the host pre-mixes the seed with the same splitmix64.
+__host__ __device__ __forceinline__ uint64_t sw_splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+__device__ __forceinline__ float dropout_uniform(uint64_t base, uint64_t i) {
+  return (float)(sw_splitmix64(base + i) >> 40) * (1.0f / 16777216.0f);
+}
+
+// SGD with momentum as torch.optim.SGD rounds it (the library is built without FMA contraction): the one spelling of the update
+// (`first` alone decides whether m is used: callers pass what the buffer holds, written before or not; only the GEMM epilogue,
+// which requests the buffer ahead of its accumulators, passes 0 on a first step instead of loading)
+struct SgdWM { float w, m; };
+__device__ __forceinline__ SgdWM sgd_update(float w, float g, float m, int first, float mom, float gscale, float lr, float wd) {
+  const float d = g * gscale + wd * w;
+  const float mn = first ? d : mom * m + d;
+  return {w - lr * mn, mn};
+}
+// learning rate / weight decay: kernel arguments, or (hyper_dev) two floats in device memory — a captured hipGraph of the step then
+// stays valid when the schedule changes them
+struct SgdHyper { float lr, wd; };
+__device__ __forceinline__ SgdHyper sgd_hyper(const float* hyper_dev, float lr, float wd) {
+  return {hyper_dev ? hyper_dev[0] : lr, hyper_dev ? hyper_dev[1] : wd};
+}
+
+// Several problems in one launch.  `first[0..n]` are the prefix sums of the problems' block counts; a block finds its problem and
+// its index inside it.  The host fills the table with BatchTable: first[n] always holds the total, add() refuses past 2^31 - 1.
+template <typename T>
+__device__ __forceinline__ int batch_find(const T* first, int n, T blk, T* local) {
+  int i = 0;
+  while (i + 1 < n && blk >= first[i + 1]) ++i;
+  *local = blk - first[i];
+  return i;
+}
+struct BatchTable {
+  int* first; int n; long blocks;
+  explicit BatchTable(int* f) : first(f), n(0), blocks(0) { first[0] = 0; }
+  bool add(long nb) {
+    if (nb < 0 || blocks + nb > 2147483647L) return false;
+    blocks += nb; first[++n] = (int)blocks;
+    return true;
+  }
+};
+
 template <typename T> struct Elem;
 template <> struct Elem<float> {
   static constexpr int kDtype = SW_F32;

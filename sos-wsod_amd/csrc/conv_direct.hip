@@ -425,7 +425,7 @@ struct DirectMulti {
   DirectArgs p[DIRECT_MULTI_MAX];
 };
 __global__ __launch_bounds__(256, 2) void conv3x3_direct_multi_kernel(DirectMulti m) {
-  int i = 0;
+  int i = 0;                                                      // batch_find (common.h), spelled out: the call reschedules this kernel
   while (i + 1 < m.n && blockIdx.x >= m.first[i + 1]) ++i;
   conv3x3_direct_body<1, 64, 1>(m.p[i], blockIdx.x - m.first[i]);
 }

@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_direct_kernel(WdArgs wa) {
     const int per = in_round >> 3, extra = in_round & 7;
     if (j >= per + (x < extra ? 1 : 0)) continue;
     const int t = round * G + x * per + min(x, extra) + j;
-    int pi = 0;
+    int pi = 0;                                                   // batch_find (common.h), spelled out: the call reschedules this kernel
     while (pi + 1 < wa.n_problems && t >= wa.first_item[pi + 1]) ++pi;
     const WdProblem& P = wa.p[pi];
     const int local = t - wa.first_item[pi];

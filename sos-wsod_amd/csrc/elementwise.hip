@@ -118,7 +118,7 @@ __device__ __forceinline__ void vstore(T* p, const float* v) {
   u32x4 w;
   if (sizeof(T) == 2) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (unsigned)f32_to_bf16_bits(v[2 * i]) | ((unsigned)f32_to_bf16_bits(v[2 * i + 1]) << 16);
+    for (int i = 0; i < 4; ++i) w[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
   } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i) w[i] = __float_as_uint(v[i]);
@@ -292,9 +292,7 @@ __global__ void convert_2d_vec4_kernel(int rows, int cols4, const float* __restr
     const float4 v = *(const float4*)(src + r * ld_src + c);
     T* d = dst + r * ld_dst + c;
     if (sizeof(T) == 2) {
-      const unsigned lo = (unsigned)f32_to_bf16_bits(v.x) | ((unsigned)f32_to_bf16_bits(v.y) << 16);
-      const unsigned hi = (unsigned)f32_to_bf16_bits(v.z) | ((unsigned)f32_to_bf16_bits(v.w) << 16);
-      *(uint2*)d = make_uint2(lo, hi);
+      *(uint2*)d = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
     } else {
       *(float4*)d = v;
     }
@@ -383,9 +381,8 @@ struct ColsumPartMulti {
 };
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_ws_multi_kernel(ColsumPartMulti f) {
-  int i = 0;
-  while (i + 1 < f.n && (int)blockIdx.x >= f.first_wg[i + 1]) ++i;
-  const int w = (int)blockIdx.x - f.first_wg[i];
+  int w;
+  const int i = batch_find(f.first_wg, f.n, (int)blockIdx.x, &w);
   colsum_ws_body<T>(f.M[i], f.N[i], f.rpc[i], (const T*)f.X[i], f.ld[i], f.ws[i], w % f.slabs[i], w / f.slabs[i]);
 }
 
@@ -422,23 +419,15 @@ struct ColsumFoldMulti {
   float* out[CFOLD_MAX];
 };
 __global__ __launch_bounds__(256) void colsum_fold_multi_kernel(ColsumFoldMulti f) {
-  int i = 0;
-  while (i + 1 < f.n && (int)blockIdx.x >= f.first_wg[i + 1]) ++i;
-  colsum_fold_body(f.N[i], f.rows[i], f.ws[i], f.out[i], blockIdx.x - f.first_wg[i]);
+  int wg;
+  const int i = batch_find(f.first_wg, f.n, (int)blockIdx.x, &wg);
+  colsum_fold_body(f.N[i], f.rows[i], f.ws[i], f.out[i], wg);
 }
 
 // ---------------------------------------------------------------- dropout keep mask
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 __global__ void dropout_mask_kernel(uint8_t* __restrict__ keep, long n, uint64_t seed, uint64_t offset, float p) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const uint64_t z = splitmix64(splitmix64(seed) + offset + (uint64_t)i);
-    const float u = (float)(z >> 40) * (1.0f / 16777216.0f);
-    keep[i] = u >= p ? 1 : 0;
+    keep[i] = dropout_uniform(sw_splitmix64(seed) + offset, (uint64_t)i) >= p ? 1 : 0;
   }
 }
 
@@ -446,11 +435,9 @@ __global__ void dropout_mask_kernel(uint8_t* __restrict__ keep, long n, uint64_t
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long n, float lr,
                            float mom, float wd, int first, float gscale) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float w = p[i];
-    float d = g[i] * gscale + wd * w;
-    const float b = first ? d : mom * buf[i] + d;
-    buf[i] = b;
-    p[i] = w - lr * b;
+    const SgdWM u = sgd_update(p[i], g[i], buf[i], first, mom, gscale, lr, wd);
+    buf[i] = u.m;
+    p[i] = u.w;
   }
 }
 
@@ -476,11 +463,34 @@ __device__ __forceinline__ void sgd_stage(const sw_sgd_tensor& d, long i, float 
   }
 }
 
+// element j of tensor d: sgd_elem updates parameter and momentum buffer and returns the new weight, sgd_one also writes its compute copies
+__device__ __forceinline__ float sgd_elem(const sw_sgd_tensor& d, long j, SgdHyper h, float mom, float gscale) {
+  const SgdWM u = sgd_update(d.param[j], d.grad[j], d.momentum_buf[j], d.first_step, mom, gscale, h.lr, h.wd);
+  d.momentum_buf[j] = u.m; d.param[j] = u.w;
+  return u.w;
+}
+__device__ __forceinline__ void sgd_one(const sw_sgd_tensor& d, long j, SgdHyper h, float mom, float gscale) {
+  const float w1 = sgd_elem(d, j, h, mom, gscale);
+  if (d.stage_kind) { if (d.stage_dtype == SW_BF16) sgd_stage<unsigned short>(d, j, w1); else sgd_stage<float>(d, j, w1); }
+}
+// the vector form: four elements, the momentum buffer read and written in place
+__device__ __forceinline__ void sgd_update4(float* w, const float4 g4, float* buf, int first, float mom, float gscale, SgdHyper h) {
+  const float4 m4 = *(const float4*)buf;
+  const float g[4] = {g4.x, g4.y, g4.z, g4.w};
+  float m[4] = {m4.x, m4.y, m4.z, m4.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const SgdWM u = sgd_update(w[e], g[e], m[e], first, mom, gscale, h.lr, h.wd);
+    m[e] = u.m; w[e] = u.w;
+  }
+  *(float4*)buf = make_float4(m[0], m[1], m[2], m[3]);
+}
+
 // conv weights whose Cout and Cin are multiples of 32: one block = a 32 (co) x 32 (ci) x 9 (tap) tile.  The OIHW master is
 // read / written in 1152-byte runs, the updated values pass through an LDS tile, and both compute layouts leave as 64-byte
 // runs ([co][tap][ci]: 32 ci, [ci][8-tap][co]: 32 co).  The element-wise form scattered 2-byte stores 2 x Cin / Cout apart
 // and spent 0.2 ms per step on 14.7 M conv weights.
-__device__ __forceinline__ bool sgd_conv_tileable(const sw_sgd_tensor& d) {
+__host__ __device__ __forceinline__ bool sgd_conv_tileable(const sw_sgd_tensor& d) {
   return d.stage_kind == 2 && (d.d0 % 32) == 0 && (d.d1 % 32) == 0;
 }
 
@@ -489,16 +499,10 @@ __device__ __forceinline__ void sgd_conv_tile(const sw_sgd_tensor& d, int blk, f
   const int cib = d.d1 / 32;
   const int co0 = (blk / cib) * 32, ci0 = (blk % cib) * 32;
   const int Cin = d.d1, Cout = d.d0;
-  const float lr = d.hyper_dev ? d.hyper_dev[0] : d.lr, wd = d.hyper_dev ? d.hyper_dev[1] : d.weight_decay;
+  const SgdHyper h = sgd_hyper(d.hyper_dev, d.lr, d.weight_decay);
   for (int idx = threadIdx.x; idx < 32 * 288; idx += 256) {
     const int co_l = idx / 288, rem = idx - co_l * 288;                 // rem = ci_l * 9 + tap
-    const long o = ((long)(co0 + co_l) * Cin + ci0) * 9 + rem;
-    const float w0 = d.param[o];
-    const float dd = d.grad[o] * gscale + wd * w0;
-    const float m = d.first_step ? dd : mom * d.momentum_buf[o] + dd;
-    const float w1 = w0 - lr * m;
-    d.momentum_buf[o] = m; d.param[o] = w1;
-    tile[co_l][rem] = w1;
+    tile[co_l][rem] = sgd_elem(d, ((long)(co0 + co_l) * Cin + ci0) * 9 + rem, h, mom, gscale);
   }
   __syncthreads();
   if (d.stage0) {
@@ -521,40 +525,27 @@ __device__ __forceinline__ void sgd_conv_tile(const sw_sgd_tensor& d, int blk, f
 
 __global__ __launch_bounds__(256) void sgd_multi_kernel(SgdBatch b, float mom, float gscale) {
   __shared__ float conv_tile[32][289];
-  int ti = 0;
-  while (ti + 1 < b.n && (int)blockIdx.x >= b.block_start[ti + 1]) ++ti;
-  const sw_sgd_tensor& d = b.t[ti];
+  int blk;
+  const sw_sgd_tensor& d = b.t[batch_find(b.block_start, b.n, (int)blockIdx.x, &blk)];
   if (sgd_conv_tileable(d)) {
-    if (d.stage_dtype == SW_BF16) sgd_conv_tile<unsigned short>(d, (int)blockIdx.x - b.block_start[ti], mom, gscale, conv_tile);
-    else sgd_conv_tile<float>(d, (int)blockIdx.x - b.block_start[ti], mom, gscale, conv_tile);
+    if (d.stage_dtype == SW_BF16) sgd_conv_tile<unsigned short>(d, blk, mom, gscale, conv_tile);
+    else sgd_conv_tile<float>(d, blk, mom, gscale, conv_tile);
     return;
   }
-  // learning rate / weight decay: kernel arguments, or (hyper_dev) two floats in device memory — a captured hipGraph of the
-  // step then stays valid when the schedule changes them
-  const float lr = d.hyper_dev ? d.hyper_dev[0] : d.lr, wd = d.hyper_dev ? d.hyper_dev[1] : d.weight_decay;
-  const long base = (long)((int)blockIdx.x - b.block_start[ti]) * SGD_CHUNK;
+  const SgdHyper h = sgd_hyper(d.hyper_dev, d.lr, d.weight_decay);
+  const long base = (long)blk * SGD_CHUNK;
   const long end = min(d.n, base + SGD_CHUNK);
   const bool vec = ((((uintptr_t)d.param) | ((uintptr_t)d.grad) | ((uintptr_t)d.momentum_buf)) & 15) == 0;
   if (vec) {
     for (long i = base + threadIdx.x * 4; i < end; i += 256 * 4) {
       if (i + 4 <= end) {
         const float4 w4 = *(const float4*)(d.param + i);
-        const float4 g4 = *(const float4*)(d.grad + i);
-        float4 m4 = d.first_step ? make_float4(0.f, 0.f, 0.f, 0.f) : *(const float4*)(d.momentum_buf + i);
-        float w[4] = {w4.x, w4.y, w4.z, w4.w}; const float g[4] = {g4.x, g4.y, g4.z, g4.w};
-        float m[4] = {m4.x, m4.y, m4.z, m4.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float dd = g[e] * gscale + wd * w[e];
-          m[e] = d.first_step ? dd : mom * m[e] + dd;
-          w[e] = w[e] - lr * m[e];
-        }
-        *(float4*)(d.momentum_buf + i) = make_float4(m[0], m[1], m[2], m[3]);
+        float w[4] = {w4.x, w4.y, w4.z, w4.w};
+        sgd_update4(w, *(const float4*)(d.grad + i), d.momentum_buf + i, d.first_step, mom, gscale, h);
         *(float4*)(d.param + i) = make_float4(w[0], w[1], w[2], w[3]);
         if (d.stage_kind == 1 && (d.d0 & 3) == 0 && d.stage_dtype == SW_BF16) {      // 4 columns of one row: one 8-byte store
           const long r = i / d.d0; const int c = (int)(i - r * d.d0);
-          const unsigned lo = (unsigned)f32_to_bf16_bits(w[0]) | ((unsigned)f32_to_bf16_bits(w[1]) << 16);
-          const unsigned hi = (unsigned)f32_to_bf16_bits(w[2]) | ((unsigned)f32_to_bf16_bits(w[3]) << 16);
+          const unsigned lo = pack_bf16x2(w[0], w[1]), hi = pack_bf16x2(w[2], w[3]);
           unsigned short* o = (unsigned short*)d.stage0 + r * d.ld0 + c;
           if ((((uintptr_t)o) & 7) == 0) *(uint2*)o = make_uint2(lo, hi);
           else { o[0] = (unsigned short)lo; o[1] = (unsigned short)(lo >> 16); o[2] = (unsigned short)hi; o[3] = (unsigned short)(hi >> 16); }
@@ -565,25 +556,11 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(SgdBatch b, float mom, f
           }
         }
       } else {
-        for (long j = i; j < end; ++j) {
-          const float w0 = d.param[j];
-          const float dd = d.grad[j] * gscale + wd * w0;
-          const float m = d.first_step ? dd : mom * d.momentum_buf[j] + dd;
-          const float w1 = w0 - lr * m;
-          d.momentum_buf[j] = m; d.param[j] = w1;
-          if (d.stage_kind) { if (d.stage_dtype == SW_BF16) sgd_stage<unsigned short>(d, j, w1); else sgd_stage<float>(d, j, w1); }
-        }
+        for (long j = i; j < end; ++j) sgd_one(d, j, h, mom, gscale);
       }
     }
   } else {
-    for (long j = base + threadIdx.x; j < end; j += 256) {
-      const float w0 = d.param[j];
-      const float dd = d.grad[j] * gscale + wd * w0;
-      const float m = d.first_step ? dd : mom * d.momentum_buf[j] + dd;
-      const float w1 = w0 - lr * m;
-      d.momentum_buf[j] = m; d.param[j] = w1;
-      if (d.stage_kind) { if (d.stage_dtype == SW_BF16) sgd_stage<unsigned short>(d, j, w1); else sgd_stage<float>(d, j, w1); }
-    }
+    for (long j = base + threadIdx.x; j < end; j += 256) sgd_one(d, j, h, mom, gscale);
   }
 }
 
@@ -596,7 +573,7 @@ __global__ __launch_bounds__(256) void sgd_tile_t_kernel(int rows, int cols, flo
                                                          T* __restrict__ st0, long ld0, T* __restrict__ st1, long ld1,
                                                          const float* __restrict__ hyper) {
   __shared__ float tile[64][65];
-  if (hyper) { lr = hyper[0]; wd = hyper[1]; }
+  const SgdHyper h = sgd_hyper(hyper, lr, wd);
   const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
   const int tr = threadIdx.x >> 4, tc = (threadIdx.x & 15) * 4;
 #pragma unroll
@@ -606,24 +583,13 @@ __global__ __launch_bounds__(256) void sgd_tile_t_kernel(int rows, int cols, flo
     float4 w4 = *(const float4*)(param + o);
     float w[4] = {w4.x, w4.y, w4.z, w4.w};
     if (grad) {
-      const float4 g4 = *(const float4*)(grad + o);
-      const float4 m4 = first ? make_float4(0.f, 0.f, 0.f, 0.f) : *(const float4*)(buf + o);
-      const float g[4] = {g4.x, g4.y, g4.z, g4.w};
-      float m[4] = {m4.x, m4.y, m4.z, m4.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float dd = g[e] * gscale + wd * w[e];
-        m[e] = first ? dd : mom * m[e] + dd;
-        w[e] = w[e] - lr * m[e];
-      }
-      *(float4*)(buf + o) = make_float4(m[0], m[1], m[2], m[3]);
+      sgd_update4(w, *(const float4*)(grad + o), buf + o, first, mom, gscale, h);
       *(float4*)(param + o) = make_float4(w[0], w[1], w[2], w[3]);
     }
     if (st0) {
       T* d = st0 + (long)(r0 + r) * ld0 + c0 + tc;
       if (sizeof(T) == 2 && (((uintptr_t)d) & 7) == 0) {
-        *(uint2*)d = make_uint2((unsigned)f32_to_bf16_bits(w[0]) | ((unsigned)f32_to_bf16_bits(w[1]) << 16),
-                                (unsigned)f32_to_bf16_bits(w[2]) | ((unsigned)f32_to_bf16_bits(w[3]) << 16));
+        *(uint2*)d = make_uint2(pack_bf16x2(w[0], w[1]), pack_bf16x2(w[2], w[3]));
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) Elem<T>::store(d + e, w[e]);
@@ -640,7 +606,7 @@ __global__ __launch_bounds__(256) void sgd_tile_t_kernel(int rows, int cols, flo
     u32x4 o[2];
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-      o[e >> 2][e & 3] = (unsigned)f32_to_bf16_bits(tile[q + 2 * e][oc]) | ((unsigned)f32_to_bf16_bits(tile[q + 2 * e + 1][oc]) << 16);
+      o[e >> 2][e & 3] = pack_bf16x2(tile[q + 2 * e][oc], tile[q + 2 * e + 1][oc]);
     *(u32x4*)d = o[0];
     *(u32x4*)(d + 8) = o[1];
   } else {
@@ -1082,6 +1048,11 @@ void colsum_ws_geometry(int dtype, int M, int N, int* slabs, int* chunks, int* r
   *rpc = r;
   *chunks = (M + r - 1) / r;
 }
+// what the workspace form asks of a matrix: whole 16-byte pieces in every row
+bool colsum_ws_ok(int dtype, int M, int N, const void* X, long ld, const float* workspace) {
+  const int vec = dtype == SW_BF16 ? 8 : 4;
+  return workspace && M > 0 && N > 0 && (N % vec) == 0 && (ld % vec) == 0 && (((uintptr_t)X) & 15) == 0;
+}
 }  // namespace
 
 extern "C" long sw_colsum_workspace_floats(int dtype, int M, int N) {
@@ -1096,8 +1067,7 @@ extern "C" long sw_colsum_workspace_floats(int dtype, int M, int N) {
 static int colsum_partial(int dtype, int M, int N, const void* X, long ld, float* workspace, hipStream_t stream) {
   SW_ENTER();
   if (dtype != SW_BF16 && dtype != SW_F32) return -1;
-  const int vec = dtype == SW_BF16 ? 8 : 4;
-  if (!workspace || M <= 0 || N <= 0 || (N % vec) || (ld % vec) || (((uintptr_t)X) & 15)) return -5;
+  if (!colsum_ws_ok(dtype, M, N, X, ld, workspace)) return -5;
   int slabs, chunks, rpc;
   colsum_ws_geometry(dtype, M, N, &slabs, &chunks, &rpc);
   dim3 grid(slabs, chunks);
@@ -1112,25 +1082,22 @@ static int colsum_partial(int dtype, int M, int N, const void* X, long ld, float
 extern "C" int sw_colsum_partial_multi(int dtype, int n, const sw_colsum_part_desc* parts, hipStream_t stream) {
   SW_ENTER();
   if (dtype != SW_BF16 && dtype != SW_F32) return -1;
-  const int vec = dtype == SW_BF16 ? 8 : 4;
   for (int base = 0; base < n; base += CPART_MAX) {
     ColsumPartMulti f = {};
-    f.n = n - base < CPART_MAX ? n - base : CPART_MAX;
-    long wgs = 0;
-    for (int i = 0; i < f.n; ++i) {
-      const sw_colsum_part_desc& q = parts[base + i];
-      if (!q.workspace || q.M <= 0 || q.N <= 0 || (q.N % vec) || (q.ld % vec) || (((uintptr_t)q.X) & 15)) return -5;
+    BatchTable t(f.first_wg);
+    for (int i = base; i < n && i < base + CPART_MAX; ++i) {
+      const sw_colsum_part_desc& q = parts[i];
+      if (!colsum_ws_ok(dtype, q.M, q.N, q.X, q.ld, q.workspace)) return -5;
       int slabs, chunks, rpc;
       colsum_ws_geometry(dtype, q.M, q.N, &slabs, &chunks, &rpc);
-      f.M[i] = q.M; f.N[i] = q.N; f.rpc[i] = rpc; f.slabs[i] = slabs; f.ld[i] = q.ld; f.X[i] = q.X; f.ws[i] = q.workspace;
-      f.first_wg[i] = (int)wgs;
-      wgs += (long)slabs * chunks;
-      if (wgs > 2147483647L) return -6;
+      const int k = t.n;
+      f.M[k] = q.M; f.N[k] = q.N; f.rpc[k] = rpc; f.slabs[k] = slabs; f.ld[k] = q.ld; f.X[k] = q.X; f.ws[k] = q.workspace;
+      if (!t.add((long)slabs * chunks)) return -6;
     }
-    f.first_wg[f.n] = (int)wgs;
+    f.n = t.n;
     DISPATCH_T(dtype,
-      hipLaunchKernelGGL(colsum_ws_multi_kernel<unsigned short>, dim3((unsigned)wgs), dim3(256), 0, stream, f),
-      hipLaunchKernelGGL(colsum_ws_multi_kernel<float>, dim3((unsigned)wgs), dim3(256), 0, stream, f));
+      hipLaunchKernelGGL(colsum_ws_multi_kernel<unsigned short>, dim3((unsigned)t.blocks), dim3(256), 0, stream, f),
+      hipLaunchKernelGGL(colsum_ws_multi_kernel<float>, dim3((unsigned)t.blocks), dim3(256), 0, stream, f));
     SW_CHECK_LAUNCH();
   }
   return 0;
@@ -1140,17 +1107,16 @@ extern "C" int sw_colsum_fold_multi(int n, const sw_colsum_fold_desc* folds, hip
   SW_ENTER();
   for (int base = 0; base < n; base += CFOLD_MAX) {
     ColsumFoldMulti f = {};
-    f.n = n - base < CFOLD_MAX ? n - base : CFOLD_MAX;
-    int wgs = 0;
-    for (int i = 0; i < f.n; ++i) {
-      const sw_colsum_fold_desc& q = folds[base + i];
+    BatchTable t(f.first_wg);
+    for (int i = base; i < n && i < base + CFOLD_MAX; ++i) {
+      const sw_colsum_fold_desc& q = folds[i];
       if (q.N <= 0 || q.n_partial_rows < 1) return -5;
-      f.N[i] = q.N; f.rows[i] = q.n_partial_rows; f.ws[i] = q.workspace; f.out[i] = q.out;
-      f.first_wg[i] = wgs;
-      wgs += (q.N + 15) / 16;
+      const int k = t.n;
+      f.N[k] = q.N; f.rows[k] = q.n_partial_rows; f.ws[k] = q.workspace; f.out[k] = q.out;
+      if (!t.add((q.N + 15) / 16)) return -6;
     }
-    f.first_wg[f.n] = wgs;
-    hipLaunchKernelGGL(colsum_fold_multi_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, f);
+    f.n = t.n;
+    hipLaunchKernelGGL(colsum_fold_multi_kernel, dim3((unsigned)t.blocks), dim3(256), 0, stream, f);
     SW_CHECK_LAUNCH();
   }
   return 0;
@@ -1161,9 +1127,7 @@ extern "C" int sw_colsum(int dtype, int M, int N, const void* X, long ld, float*
   SW_ENTER();
   if (N <= 0) return 0;
   if (dtype != SW_BF16 && dtype != SW_F32) return -1;
-  const int vec = dtype == SW_BF16 ? 8 : 4;
-  const bool ws_form = workspace && M > 0 && (N % vec) == 0 && (ld % vec) == 0 && (((uintptr_t)X) & 15) == 0;
-  if (ws_form) {
+  if (colsum_ws_ok(dtype, M, N, X, ld, workspace)) {
     const int rc = colsum_partial(dtype, M, N, X, ld, workspace, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(colsum_fold_kernel, dim3((N + 15) / 16), dim3(256), 0, stream, N, (int)(sw_colsum_workspace_floats(dtype, M, N) / N),
@@ -1245,8 +1209,7 @@ extern "C" int sw_sgd_multi(int n_tensors, const sw_sgd_tensor* tensors, float m
   SW_ENTER();
   for (int t0 = 0; t0 < n_tensors; t0 += SW_SGD_MAX_TENSORS) {
     SgdBatch b;
-    b.n = 0;
-    int blocks = 0;
+    BatchTable t(b.block_start);
     for (int i = t0; i < n_tensors && i < t0 + SW_SGD_MAX_TENSORS; ++i) {
       const sw_sgd_tensor& d = tensors[i];
       if (d.n <= 0) continue;
@@ -1270,17 +1233,14 @@ extern "C" int sw_sgd_multi(int n_tensors, const sw_sgd_tensor* tensors, float m
       if (d.stage_kind && d.stage_dtype != SW_BF16 && d.stage_dtype != SW_F32) return -1;
       if (d.stage_kind == 1 && (d.d0 <= 0 || d.stage0 == nullptr)) return -5;
       if (d.stage_kind == 2 && (long)d.d0 * d.d1 * 9 != d.n) return -5;
-      const bool conv_tiles = d.stage_kind == 2 && (d.d0 % 32) == 0 && (d.d1 % 32) == 0;
-      const long nb = conv_tiles ? (long)(d.d0 / 32) * (d.d1 / 32) : (d.n + SGD_CHUNK - 1) / SGD_CHUNK;
+      const long nb = sgd_conv_tileable(d) ? (long)(d.d0 / 32) * (d.d1 / 32) : (d.n + SGD_CHUNK - 1) / SGD_CHUNK;
       if (nb > (1L << 30)) return -6;
-      b.t[b.n] = d;
-      b.block_start[b.n] = blocks;
-      blocks += (int)nb;
-      ++b.n;
+      b.t[t.n] = d;
+      if (!t.add(nb)) return -6;
     }
-    b.block_start[b.n] = blocks;
+    b.n = t.n;
     if (b.n == 0) continue;
-    hipLaunchKernelGGL(sgd_multi_kernel, dim3(blocks), dim3(256), 0, stream, b, momentum, grad_scale);
+    hipLaunchKernelGGL(sgd_multi_kernel, dim3((unsigned)t.blocks), dim3(256), 0, stream, b, momentum, grad_scale);
     SW_CHECK_LAUNCH();
   }
   return 0;
@@ -1399,9 +1359,9 @@ struct EmaBatch {
 // teacher = student * (1 - keep) + teacher * keep  (ubteacher/engine/trainer.py:588-604 _update_teacher_model), the products and
 // the sum rounded as torch rounds them (two multiplies, one add: no fused multiply-add)
 __global__ __launch_bounds__(256) void ema_multi_kernel(EmaBatch b, float keep, float one_minus_keep) {
-  int t = 0;
-  while (t + 1 < b.count && (int)blockIdx.x >= b.block_start[t + 1]) ++t;
-  const long base = (long)(blockIdx.x - b.block_start[t]) * 4096;
+  int blk;
+  const int t = batch_find(b.block_start, b.count, (int)blockIdx.x, &blk);
+  const long base = (long)blk * 4096;
   float* te = b.teacher[t];
   const float* st = b.student[t];
   const long n = b.n[t];
@@ -1458,18 +1418,16 @@ extern "C" int sw_ema_multi(int n_tensors, float* const* teacher, const float* c
   SW_ENTER();
   for (int t0 = 0; t0 < n_tensors; t0 += EMA_MAX) {
     EmaBatch b = {};
-    int blocks = 0;
+    BatchTable t(b.block_start);
     for (int i = t0; i < n_tensors && i < t0 + EMA_MAX; ++i) {
       if (numel[i] <= 0) continue;
-      b.teacher[b.count] = teacher[i]; b.student[b.count] = student[i]; b.n[b.count] = numel[i];
-      b.block_start[b.count] = blocks;
-      blocks += (int)((numel[i] + 4095) / 4096);
-      ++b.count;
+      b.teacher[t.n] = teacher[i]; b.student[t.n] = student[i]; b.n[t.n] = numel[i];
+      if (!t.add((numel[i] + 4095) / 4096)) return -6;
     }
-    b.block_start[b.count] = blocks;
-    if (blocks == 0) continue;
+    b.count = t.n;
+    if (t.blocks == 0) continue;
     // the two python-float scalars of `student * (1 - keep) + teacher * keep`, each rounded to f32 as torch rounds a scalar operand
-    hipLaunchKernelGGL(ema_multi_kernel, dim3(blocks), dim3(256), 0, stream, b, (float)keep_rate, (float)(1.0 - keep_rate));
+    hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)t.blocks), dim3(256), 0, stream, b, (float)keep_rate, (float)(1.0 - keep_rate));
     SW_CHECK_LAUNCH();
   }
   return 0;

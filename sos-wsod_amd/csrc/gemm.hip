@@ -520,8 +520,8 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
     constexpr int TP = 40;                                         // halfwords per column (32 rows + pad; 80 B: 16-byte column starts)
     unsigned short* tT = (unsigned short*)((float*)smem + NW * (32 * LDW)) + wave * (WTN * TP);
     static_assert((long)NW * (32 * LDW) * 4 + (long)NW * WTN * TP * 2 <= (long)STAGES * STAGE_BYTES, "epilogue staging fits the ring");
-    float sgd_lr = g.sgd_lr, sgd_wd = g.sgd_wd;
-    if (g.sgd_param && g.sgd_hyper) { sgd_lr = g.sgd_hyper[0]; sgd_wd = g.sgd_hyper[1]; }
+    SgdHyper sgd_h = {g.sgd_lr, g.sgd_wd};                         // sgd_hyper (common.h), spelled out: its selects reschedule this kernel
+    if (g.sgd_param && g.sgd_hyper) { sgd_h.lr = g.sgd_hyper[0]; sgd_h.wd = g.sgd_hyper[1]; }
     __syncthreads();                                               // every wave is done reading the last K-tile
     const bool vec_ok = g.staged_out;                              // host: 16-byte row pieces are aligned and inside the row pitch
     auto quarter = [&](auto qc) {
@@ -589,15 +589,8 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
                                                : ((const float*)g.res)[(long)m * g.ldres + n];
               if (g.relu) x = relu_keep_nan(x);
               if (g.drop && ok) x = g.drop[(long)m * g.ldd + n] ? x * g.drop_scale : 0.f;
-              if (g.drop_p > 0.f && ok) {                          // identical Bernoulli stream to dropout_mask_kernel (elementwise.hip)
-                unsigned long long z = drop_base + (unsigned long long)((long)m * g.N + n);
-                z += 0x9E3779B97F4A7C15ull;
-                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-                z ^= z >> 31;
-                const float u = (float)(z >> 40) * (1.0f / 16777216.0f);
-                x = u >= g.drop_p ? x * g.drop_scale : 0.f;
-              }
+              if (g.drop_p > 0.f && ok)                            // dropout_mask_kernel's Bernoulli stream (elementwise.hip)
+                x = dropout_uniform(drop_base, (unsigned long long)((long)m * g.N + n)) >= g.drop_p ? x * g.drop_scale : 0.f;
               if (g.ref && ok) {
                 float rv;
                 if (ref_piece) rv = __uint_as_float((t & 1) ? (refw[(t >> 1) & 3] & 0xFFFF0000u) : (refw[(t >> 1) & 3] << 16));
@@ -611,21 +604,19 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
           }
           const long o = (long)m * g.ldc + nb;
           if (CP == 4 && PLAIN && g.sgd_param) {
-            // ---- fused SGD (sgd_tile_t_kernel's arithmetic, elementwise.hip: identical bits): host guarantees full 16-byte pieces
+            // ---- fused SGD (sgd_update, as sgd_tile_t_kernel in elementwise.hip calls it): host guarantees full 16-byte pieces
             const long po = (long)m * g.sgd_ld + nb;
             const f32x4 w4 = pw[it * CP / 4 < NPC ? it * CP / 4 : 0];     // (CP == 4 here: piece `it` of the quarter)
             f32x4 m4 = pm[it * CP / 4 < NPC ? it * CP / 4 : 0];
             f32x4 wn;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-              const float dd = v[t] * g.sgd_gscale + sgd_wd * w4[t];
-              m4[t] = g.sgd_first ? dd : g.sgd_momentum * m4[t] + dd;
-              wn[t] = w4[t] - sgd_lr * m4[t];
+              const SgdWM u = sgd_update(w4[t], v[t], m4[t], g.sgd_first, g.sgd_momentum, g.sgd_gscale, sgd_h.lr, sgd_h.wd);
+              m4[t] = u.m; wn[t] = u.w;
             }
             *(f32x4*)(g.sgd_mom + po) = m4;
             *(f32x4*)(g.sgd_param + po) = wn;
-            const unsigned b01 = (unsigned)f32_to_bf16_bits(wn[0]) | ((unsigned)f32_to_bf16_bits(wn[1]) << 16);
-            const unsigned b23 = (unsigned)f32_to_bf16_bits(wn[2]) | ((unsigned)f32_to_bf16_bits(wn[3]) << 16);
+            const unsigned b01 = pack_bf16x2(wn[0], wn[1]), b23 = pack_bf16x2(wn[2], wn[3]);
             if (g.sgd_st0) *(u32x2*)(g.sgd_st0 + (long)m * g.sgd_ld0 + nb) = u32x2{b01, b23};
             if (g.sgd_st1) {
               tT[(c0 + 0) * TP + row] = (unsigned short)(b01 & 0xFFFFu); tT[(c0 + 1) * TP + row] = (unsigned short)(b01 >> 16);
@@ -654,7 +645,7 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
             if (full && vec_ok) {
               u32x4 w;
 #pragma unroll
-              for (int t = 0; t < 4; ++t) w[t] = (unsigned)f32_to_bf16_bits(v[2 * t]) | ((unsigned)f32_to_bf16_bits(v[2 * t + 1]) << 16);
+              for (int t = 0; t < 4; ++t) w[t] = pack_bf16x2(v[2 * t], v[2 * t + 1]);
               __builtin_nontemporal_store(w, (u32x4*)dst);
             } else {
 #pragma unroll
@@ -737,15 +728,8 @@ __device__ __forceinline__ void gemm2_tile(const GemmArgs& g, const int bm, cons
                                               : ((const float*)g.res)[(long)m * g.ldres + n];
         if (g.relu) v = relu_keep_nan(v);
         if (g.drop && ok) v = g.drop[(long)m * g.ldd + n] ? v * g.drop_scale : 0.f;
-        if (g.drop_p > 0.f && ok) {                        // identical Bernoulli stream to dropout_mask_kernel (elementwise.hip)
-          unsigned long long z = drop_base + (unsigned long long)((long)m * g.N + n);
-          z += 0x9E3779B97F4A7C15ull;
-          z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-          z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-          z ^= z >> 31;
-          const float u = (float)(z >> 40) * (1.0f / 16777216.0f);
-          v = u >= g.drop_p ? v * g.drop_scale : 0.f;
-        }
+        if (g.drop_p > 0.f && ok)                          // dropout_mask_kernel's Bernoulli stream (elementwise.hip)
+          v = dropout_uniform(drop_base, (unsigned long long)((long)m * g.N + n)) >= g.drop_p ? v * g.drop_scale : 0.f;
         if (ref_staged) {
           v = bf16_bits_to_f32(stile[lrow * WTN + j * TS + r]) > 0.f ? v * g.ref_scale : 0.f;
         } else if (ref_staged2) {
@@ -853,7 +837,7 @@ __global__ __launch_bounds__(1024, 1) void gemm2_grouped_kernel(GroupedArgs ga) 
     const int per = in_round >> 3, extra = in_round & 7;
     if (j >= per + (x < extra ? 1 : 0)) continue;
     const int t = round * G + x * per + min(x, extra) + j;
-    int pi = 0;
+    int pi = 0;                                                   // batch_find (common.h), spelled out: the call reschedules this kernel
     while (pi + 1 < ga.n_problems && t >= ga.first_item[pi + 1]) ++pi;
     const GroupedProblem& P = ga.p[pi];
     const int local = t - ga.first_item[pi];
@@ -869,6 +853,20 @@ __global__ __launch_bounds__(1024, 1) void gemm2_grouped_kernel(GroupedArgs ga) 
   }
 }
 
+// K-split geometry: a split takes ceil(K / splitk) rounded up to whole K-tiles, so fewer splits than asked for may remain
+long k_per_split(long K, int splitk, int bk) {
+  const long kps = (K + (splitk < 1 ? 1 : splitk) - 1) / (splitk < 1 ? 1 : splitk);
+  return ((kps + bk - 1) / bk) * bk;
+}
+long effective_splits(int dtype, long K, int splitk) {
+  const long kps = k_per_split(K, splitk, dtype == SW_BF16 ? 64 : 32);
+  return K <= 0 ? 0 : (K + kps - 1) / kps;
+}
+// blocks of 256 threads for `pieces` items of a grid-stride fold, at least one and at most cap
+unsigned fold_blocks(long pieces, long cap) {
+  const long b = (pieces + 255) / 256;
+  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 
 template <typename T, int AMODE, int BMODE, int BM, int BN, int STAGES, int WTM = 64, int WTN = 64>
 int launch2(GemmArgs& g, int splitk, hipStream_t stream) {
@@ -888,11 +886,8 @@ int launch2(GemmArgs& g, int splitk, hipStream_t stream) {
   g.patch_m_log2 = pml;
   g.patches_m = (g.tiles_m + (1 << pml) - 1) >> pml;
   const int patches_n = (g.tiles_n + (64 >> pml) - 1) / (64 >> pml);
-  if (splitk < 1) splitk = 1;
-  int kps = (g.K + splitk - 1) / splitk;
-  kps = ((kps + BK - 1) / BK) * BK;
-  g.k_per_split = kps;
-  splitk = (g.K + kps - 1) / kps;
+  g.k_per_split = (int)k_per_split(g.K, splitk, BK);
+  splitk = (g.K + g.k_per_split - 1) / g.k_per_split;
   if (splitk > 1 && !g.atomic && g.slab_stride <= 0) return -2;
   g.staged_out = (g.out_bf16 && !g.atomic && g.slab_stride <= 0 && (g.N % 8) == 0 && (g.ldc % 8) == 0 &&
                   (((uintptr_t)g.C) & 15) == 0 && (long)NT / 64 * WTM * WTN * 2 <= (long)LDS) ? 1 : 0;
@@ -974,26 +969,39 @@ __global__ void scale_rows_kernel(int M, int N, float* __restrict__ C, long ldc,
 
 // deterministic split-K: C[m][n] = sum_z ws[z][m][n], slabs added in a fixed order (pairs of four partial sums)
 // row_scale (may be NULL): C[m][n] = row_scale[m] * sum — the FrozenBN fold of a weight gradient (dW = scale * dW_eff) without a pass of its own
+// the ordered sum of one 16-byte piece over nslab slabs of nv pieces: four running sums, then (a0 + a1) + (a2 + a3)
+__device__ __forceinline__ f32x4 fold_slabs4(const f32x4* src, long nv, int nslab) {
+  f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
+  int z = 0;
+  for (; z + 4 <= nslab; z += 4) {
+    const f32x4 v0 = src[(long)z * nv], v1 = src[(long)(z + 1) * nv], v2 = src[(long)(z + 2) * nv], v3 = src[(long)(z + 3) * nv];
+    a0 += v0; a1 += v1; a2 += v2; a3 += v3;
+  }
+  for (; z < nslab; ++z) a0 += src[(long)z * nv];
+  return (a0 + a1) + (a2 + a3);
+}
+__device__ __forceinline__ f32x4 scale4(f32x4 r, float sc) {
+  return f32x4{__fmul_rn(r[0], sc), __fmul_rn(r[1], sc), __fmul_rn(r[2], sc), __fmul_rn(r[3], sc)};
+}
+// C = [C +] row_scale * fold over the pieces first, first + stride, ...: the body of the single fold and of the batched one
+__device__ __forceinline__ void splitk_fold_pieces(int M, int N, int nslab, const float* __restrict__ ws, float* __restrict__ C, long ldc,
+                                                   const float* __restrict__ row_scale, long first, long stride, int accumulate) {
+  const long nv = ((long)M * N) >> 2;
+  const int nq = N >> 2;
+  for (long q = first; q < nv; q += stride) {
+    f32x4 r = fold_slabs4((const f32x4*)ws + q, nv, nslab);
+    const long m = q / nq; const int n4 = (int)(q - m * nq);
+    if (row_scale) r = scale4(r, row_scale[m]);
+    f32x4* dst = (f32x4*)(C + m * ldc + n4 * 4);
+    if (accumulate) r += *dst;
+    *dst = r;
+  }
+}
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(int M, int N, int nslab, const float* __restrict__ ws,
                                                             float* __restrict__ C, long ldc, int vec, const float* __restrict__ row_scale) {
   const long slab = (long)M * N;
   if (vec) {
-    const long nv = slab >> 2;
-    const int nq = N >> 2;
-    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < nv; q += (long)gridDim.x * blockDim.x) {
-      const f32x4* src = (const f32x4*)ws + q;
-      f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
-      int z = 0;
-      for (; z + 4 <= nslab; z += 4) {
-        const f32x4 v0 = src[(long)z * nv], v1 = src[(long)(z + 1) * nv], v2 = src[(long)(z + 2) * nv], v3 = src[(long)(z + 3) * nv];
-        a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-      }
-      for (; z < nslab; ++z) a0 += src[(long)z * nv];
-      const long m = q / nq; const int n4 = (int)(q - m * nq);
-      f32x4 r = (a0 + a1) + (a2 + a3);
-      if (row_scale) { const float sc = row_scale[m]; r[0] = __fmul_rn(r[0], sc); r[1] = __fmul_rn(r[1], sc); r[2] = __fmul_rn(r[2], sc); r[3] = __fmul_rn(r[3], sc); }
-      *(f32x4*)(C + m * ldc + n4 * 4) = r;
-    }
+    splitk_fold_pieces(M, N, nslab, ws, C, ldc, row_scale, blockIdx.x * (long)blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x, 0);
   } else {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < slab; i += (long)gridDim.x * blockDim.x) {
       float a = 0.f;
@@ -1017,20 +1025,10 @@ __global__ __launch_bounds__(256) void splitk_fold_ep_kernel(FoldEp f) {
   const long nv = ((long)f.M * f.N) >> 2;
   const int nq = f.N >> 2;
   for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < nv; q += (long)gridDim.x * blockDim.x) {
-    const f32x4* src = (const f32x4*)f.ws + q;
-    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
-    int z = 0;
-    for (; z + 4 <= f.nslab; z += 4) {
-      const f32x4 v0 = src[(long)z * nv], v1 = src[(long)(z + 1) * nv], v2 = src[(long)(z + 2) * nv], v3 = src[(long)(z + 3) * nv];
-      a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-    }
-    for (; z < f.nslab; ++z) a0 += src[(long)z * nv];
     const long m = q / nq; const int n = (int)(q - m * nq) * 4;
-    const f32x4 r = (a0 + a1) + (a2 + a3);
+    f32x4 r = fold_slabs4((const f32x4*)f.ws + q, nv, f.nslab);
+    if (f.row_scale) r = scale4(r, f.row_scale[m]);
     float x[4] = {r[0], r[1], r[2], r[3]};
-    if (f.row_scale) { const float sc = f.row_scale[m];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) x[t] = __fmul_rn(x[t], sc); }
     if (f.bias) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) x[t] += f.bias[n + t]; }
@@ -1053,10 +1051,8 @@ __global__ __launch_bounds__(256) void splitk_fold_ep_kernel(FoldEp f) {
       }
     }
     if (f.out_bf16) {
-      unsigned int w0 = (unsigned)f32_to_bf16_bits(x[0]) | ((unsigned)f32_to_bf16_bits(x[1]) << 16);
-      unsigned int w1 = (unsigned)f32_to_bf16_bits(x[2]) | ((unsigned)f32_to_bf16_bits(x[3]) << 16);
       unsigned int* d = (unsigned int*)((unsigned short*)f.C + m * f.ldc + n);
-      d[0] = w0; d[1] = w1;
+      d[0] = pack_bf16x2(x[0], x[1]); d[1] = pack_bf16x2(x[2], x[3]);
     } else {
       f32x4 o = {x[0], x[1], x[2], x[3]};
       *(f32x4*)((float*)f.C + m * f.ldc + n) = o;
@@ -1081,14 +1077,6 @@ bool peel_geometry(int M, int N, int* r_out, long* sk_out) {
   while (sk > 1 && tm * r * sk >= 200) --sk;              // stay below launch_auto's switch to the 256x256 tile
   *r_out = r; *sk_out = sk;
   return true;
-}
-
-int effective_splits(int dtype, int K, int splitk) {
-  const int bk = dtype == SW_BF16 ? 64 : 32;
-  if (splitk < 1) splitk = 1;
-  int kps = (K + splitk - 1) / splitk;
-  kps = ((kps + bk - 1) / bk) * bk;
-  return (K + kps - 1) / kps;
 }
 
 int check_align(const void* p) { return (((uintptr_t)p) & 15) ? -4 : 0; }
@@ -1186,7 +1174,7 @@ extern "C" int sw_gemm(int dtype, int a_kstrided, int b_kstrided, int M, int N, 
     if ((ldc % 4) || (fz->ld0 % 4) || (fz->ld1 % 8) || ((((uintptr_t)fz->param) | ((uintptr_t)fz->momentum_buf)) & 15) ||
         (((uintptr_t)fz->stage0) & 7) || (((uintptr_t)fz->stage1) & 15)) return -4;
   }
-  const int eff = effective_splits(dtype, K, splitk);
+  const int eff = (int)effective_splits(dtype, K, splitk);
   // split-K with an epilogue (a few-tile, long-K GEMM whose result is not a plain f32 matrix: the 1x1 convolutions of res4 / res5, a
   // gradient accumulated into an existing one): plain slabs, the epilogue runs in the fold
   // (also with ONE slab when a row scale meets a residual: C = residual + row_scale * A B has no single-launch epilogue)
@@ -1213,9 +1201,7 @@ extern "C" int sw_gemm(int dtype, int a_kstrided, int b_kstrided, int M, int N, 
     f.bias = ep->bias; f.row_scale = ep->fold_row_scale;
     f.res = ep->residual; f.ldres = ep->ld_res; f.res_bf16 = ep->res_dtype == SW_BF16;
     f.relu = ep->relu; f.ref = ep->relu_ref; f.ldr = ep->ld_ref; f.ref_bf16 = ep->ref_dtype == SW_BF16; f.ref_scale = ep->ref_scale;
-    long blocks = (((long)M * N >> 2) + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-    hipLaunchKernelGGL(splitk_fold_ep_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, f);
+    hipLaunchKernelGGL(splitk_fold_ep_kernel, dim3(fold_blocks((long)M * N >> 2, 4096)), dim3(256), 0, stream, f);
     SW_CHECK_LAUNCH();
     return 0;
   }
@@ -1236,12 +1222,7 @@ extern "C" int sw_gemm(int dtype, int a_kstrided, int b_kstrided, int M, int N, 
       g.sgd_momentum = ep->sgd_momentum; g.sgd_gscale = ep->sgd_grad_scale;
     }
     if (!ep->drop_mask && ep->drop_hash_p > 0.f) {
-      unsigned long long x = ep->drop_seed;                  // splitmix64(seed), as the mask kernel mixes it
-      x += 0x9E3779B97F4A7C15ull;
-      x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-      x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-      x ^= x >> 31;
-      g.drop_seed_mixed = x; g.drop_offset = ep->drop_offset; g.drop_p = ep->drop_hash_p;
+      g.drop_seed_mixed = sw_splitmix64(ep->drop_seed); g.drop_offset = ep->drop_offset; g.drop_p = ep->drop_hash_p;
       g.drop_offset_dev = (const unsigned long long*)ep->drop_offset_dev;
     }
   }
@@ -1261,17 +1242,14 @@ extern "C" int sw_gemm(int dtype, int a_kstrided, int b_kstrided, int M, int N, 
   if (!det) {
     if (ep && ep->fold_row_scale) {            // no slab fold in this launch: the row scale as a pass of its own (plain f32 C only)
       if (!plain || ep->out_dtype != SW_F32) return -5;
-      long blocks = ((long)M * N + 255) / 256;
-      blocks = blocks > 4096 ? 4096 : blocks;
-      hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, M, N, (float*)C, ldc, ep->fold_row_scale);
+      hipLaunchKernelGGL(scale_rows_kernel, dim3(fold_blocks((long)M * N, 4096)), dim3(256), 0, stream, M, N, (float*)C, ldc, ep->fold_row_scale);
       SW_CHECK_LAUNCH();
     }
     return 0;
   }
   const int vec = ((N % 4) == 0 && (ldc % 4) == 0 && (((uintptr_t)C) & 15) == 0) ? 1 : 0;
-  long blocks = (((long)M * N >> (vec ? 2 : 0)) + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, M, N, eff, det_ws, (float*)C, ldc, vec,
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(fold_blocks((long)M * N >> (vec ? 2 : 0), 4096)), dim3(256), 0, stream, M, N, eff,
+                     det_ws, (float*)C, ldc, vec,
                      ep ? ep->fold_row_scale : nullptr);
   SW_CHECK_LAUNCH();
   return 0;
@@ -1356,7 +1334,7 @@ __device__ __forceinline__ void wgrad_reduce_body(int Cout, int Cin, int nslab, 
     }
     for (; z < nslab; ++z) a0 += *(const f32x4*)(p + (long)z * slab_f);
     f32x4 r = (a0 + a1) + (a2 + a3);
-    if (cout_scale) { const float sc = cout_scale[co]; r[0] = __fmul_rn(r[0], sc); r[1] = __fmul_rn(r[1], sc); r[2] = __fmul_rn(r[2], sc); r[3] = __fmul_rn(r[3], sc); }
+    if (cout_scale) r = scale4(r, cout_scale[co]);
     *(f32x4*)(s_t + tap * CI + c4 * 4) = r;
   }
   __syncthreads();
@@ -1390,22 +1368,23 @@ struct FoldMulti {
 };
 __global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(FoldMulti f) {
   extern __shared__ __attribute__((aligned(16))) float s_t[];
-  int i = 0;
-  while (i + 1 < f.n && (int)blockIdx.x >= f.first_wg[i + 1]) ++i;
-  const int local = blockIdx.x - f.first_wg[i];
+  int local;
+  const int i = batch_find(f.first_wg, f.n, (int)blockIdx.x, &local);
   wgrad_reduce_body(f.Cout[i], f.Cin[i], f.nslab[i], f.ws[i], f.out[i], local / f.parts[i], f.parts[i], local % f.parts[i], s_t);
+}
+
+// input-channel ranges per output channel of a weight-gradient fold (>= 1024 workgroups where Cin allows); 0: arguments refused
+int wgrad_fold_parts(int Cin, int Cout, int nslab, const float* workspace, const float* dw_oihw) {
+  if (nslab < 1 || (Cin % 4) || (size_t)36 * Cin > 65536 || (((uintptr_t)dw_oihw) & 15) || (((uintptr_t)workspace) & 15)) return 0;
+  int parts = 1;
+  while (Cout * parts < 1024 && (Cin % (parts * 2 * 4)) == 0 && Cin / (parts * 2) >= 32) parts *= 2;
+  return parts;
 }
 
 }  // namespace
 
 extern "C" long sw_conv3x3_wgrad_workspace_floats(int dtype, int nimg, int H, int W, int Cin, int Cout, int splitk) {
-  const int bk = dtype == SW_BF16 ? 64 : 32;
-  const long K = (long)nimg * H * W;
-  if (splitk < 1) splitk = 1;
-  long kps = (K + splitk - 1) / splitk;
-  kps = ((kps + bk - 1) / bk) * bk;
-  const long eff = (K + kps - 1) / kps;
-  return eff * Cout * 9L * Cin;
+  return effective_splits(dtype, (long)nimg * H * W, splitk) * Cout * 9L * Cin;
 }
 
 // conv3x3 weight gradient:  dW[co][ci][ty][tx] (OIHW, f32, overwritten)
@@ -1440,10 +1419,8 @@ static int conv3x3_wgrad_slabs(int dtype, int nimg, int H, int W, int Cin, int C
 extern "C" int sw_conv3x3_wgrad_fold(int Cin, int Cout, int nslab, const float* workspace, float* dw_oihw, const float* cout_scale,
                                      int accumulate, hipStream_t stream) {
   SW_ENTER();
-  if (nslab < 1 || (Cin % 4)) return -5;
-  if ((size_t)36 * Cin > 65536 || (((uintptr_t)dw_oihw) & 15) || (((uintptr_t)workspace) & 15)) return -5;
-  int parts = 1;                                              // input-channel ranges per output channel: >= 1024 workgroups
-  while (Cout * parts < 1024 && (Cin % (parts * 2 * 4)) == 0 && Cin / (parts * 2) >= 32) parts *= 2;
+  const int parts = wgrad_fold_parts(Cin, Cout, nslab, workspace, dw_oihw);
+  if (!parts) return -5;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)Cout, (unsigned)parts), dim3(256), (size_t)36 * Cin / parts, stream, Cout, Cin,
                      nslab, workspace, dw_oihw, cout_scale, accumulate);
   SW_CHECK_LAUNCH();
@@ -1485,11 +1462,8 @@ extern "C" int sw_conv3x3_wgrad_grouped(int dtype, int n_problems, const sw_wgra
       GroupedProblem& P = ga.p[i];
       P.A = q.dy; P.B = q.x; P.C = q.slabs; P.lda = q.Cout; P.ldb = 0;
       P.M = q.Cout; P.N = 9 * q.Cin; P.K = q.nimg * q.H * q.W; P.cH = q.H; P.cW = q.W; P.cC = q.Cin; P.cDil = q.dilation;
-      int ns = q.nsplit < 1 ? 1 : q.nsplit;
-      long kps = (P.K + ns - 1) / ns;
-      kps = ((kps + bk - 1) / bk) * bk;
-      P.k_per_split = (int)kps;
-      P.nsplit = (int)((P.K + kps - 1) / kps);
+      P.k_per_split = (int)k_per_split(P.K, q.nsplit, bk);
+      P.nsplit = (int)effective_splits(dtype, P.K, q.nsplit);
       P.tiles_m = (P.M + 255) / 256; P.tiles_n = (P.N + 255) / 256;
       const long ab = (long)P.K * q.Cout * es, bb = (long)P.K * q.Cin * es;
       if (ab >= 0xFFFFFF00L || bb >= 0xFFFFFF00L) return -6;
@@ -1539,11 +1513,8 @@ extern "C" int sw_gemm_kk_grouped(int dtype, int n_problems, const sw_gemm_kk_pr
       GroupedProblem& P = ga.p[i];
       P.A = q.A; P.B = q.B; P.C = q.slabs; P.lda = (int)q.lda; P.ldb = (int)q.ldb;
       P.M = q.M; P.N = q.N; P.K = q.K;
-      int ns = q.nsplit < 1 ? 1 : q.nsplit;
-      long kps = (P.K + ns - 1) / ns;
-      kps = ((kps + bk - 1) / bk) * bk;
-      P.k_per_split = (int)kps;
-      P.nsplit = (int)((P.K + kps - 1) / kps);
+      P.k_per_split = (int)k_per_split(P.K, q.nsplit, bk);
+      P.nsplit = (int)effective_splits(dtype, P.K, q.nsplit);
       P.tiles_m = (P.M + 255) / 256; P.tiles_n = (P.N + 255) / 256;
       const long ab = (long)P.K * q.lda * es, bb = (long)P.K * q.ldb * es;
       if (ab >= 0xFFFFFF00L || bb >= 0xFFFFFF00L) return -6;
@@ -1571,11 +1542,7 @@ extern "C" int sw_gemm_kk_grouped(int dtype, int n_problems, const sw_gemm_kk_pr
 }
 
 extern "C" long sw_gemm_kk_grouped_slabs(int dtype, int K, int nsplit) {        // slabs problem (K, nsplit) really writes
-  const int bk = dtype == SW_BF16 ? 64 : 32;
-  int ns = nsplit < 1 ? 1 : nsplit;
-  long kps = ((long)K + ns - 1) / ns;
-  kps = ((kps + bk - 1) / bk) * bk;
-  return K <= 0 ? 0 : ((long)K + kps - 1) / kps;
+  return effective_splits(dtype, K, nsplit);
 }
 
 // n ordered folds (splitk_reduce_kernel: C = [C +] row_scale * sum of slabs) in ONE launch; 16-byte pieces only
@@ -1589,29 +1556,10 @@ struct SplitkFoldMulti {
   long ldc[SFOLD_MAX];
 };
 __global__ __launch_bounds__(256) void splitk_fold_multi_kernel(SplitkFoldMulti f) {
-  int i = 0;
-  while (i + 1 < f.n && (int)blockIdx.x >= f.first_wg[i + 1]) ++i;
-  const int blk = blockIdx.x - f.first_wg[i], nblk = f.first_wg[i + 1] - f.first_wg[i];
-  const int M = f.M[i], N = f.N[i], nslab = f.nslab[i];
-  const long nv = ((long)M * N) >> 2;
-  const int nq = N >> 2;
-  const float* rs = f.row_scale[i];
-  for (long q = blk * 256L + threadIdx.x; q < nv; q += (long)nblk * 256) {
-    const f32x4* src = (const f32x4*)f.ws[i] + q;
-    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
-    int z = 0;
-    for (; z + 4 <= nslab; z += 4) {
-      const f32x4 v0 = src[(long)z * nv], v1 = src[(long)(z + 1) * nv], v2 = src[(long)(z + 2) * nv], v3 = src[(long)(z + 3) * nv];
-      a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-    }
-    for (; z < nslab; ++z) a0 += src[(long)z * nv];
-    const long m = q / nq; const int n4 = (int)(q - m * nq);
-    f32x4 r = (a0 + a1) + (a2 + a3);
-    if (rs) { const float sc = rs[m]; r[0] = __fmul_rn(r[0], sc); r[1] = __fmul_rn(r[1], sc); r[2] = __fmul_rn(r[2], sc); r[3] = __fmul_rn(r[3], sc); }
-    f32x4* dst = (f32x4*)(f.C[i] + m * f.ldc[i] + n4 * 4);
-    if (f.acc[i]) r += *dst;
-    *dst = r;
-  }
+  int blk;
+  const int i = batch_find(f.first_wg, f.n, (int)blockIdx.x, &blk);
+  const int nblk = f.first_wg[i + 1] - f.first_wg[i];
+  splitk_fold_pieces(f.M[i], f.N[i], f.nslab[i], f.ws[i], f.C[i], f.ldc[i], f.row_scale[i], blk * 256L + threadIdx.x, (long)nblk * 256, f.acc[i]);
 }
 }  // namespace
 
@@ -1619,20 +1567,17 @@ extern "C" int sw_splitk_fold_multi(int n, const sw_splitk_fold* folds, hipStrea
   SW_ENTER();
   for (int base = 0; base < n; base += SFOLD_MAX) {
     SplitkFoldMulti f = {};
-    f.n = n - base < SFOLD_MAX ? n - base : SFOLD_MAX;
-    int wgs = 0;
-    for (int i = 0; i < f.n; ++i) {
-      const sw_splitk_fold& q = folds[base + i];
+    BatchTable t(f.first_wg);
+    for (int i = base; i < n && i < base + SFOLD_MAX; ++i) {
+      const sw_splitk_fold& q = folds[i];
       if (q.M <= 0 || q.N <= 0 || q.nslab < 1 || (q.N % 4) || (q.ldc % 4) || (((uintptr_t)q.C) & 15) || (((uintptr_t)q.workspace) & 15)) return -5;
-      f.M[i] = q.M; f.N[i] = q.N; f.nslab[i] = q.nslab; f.acc[i] = q.accumulate; f.ws[i] = q.workspace; f.C[i] = q.C;
-      f.row_scale[i] = q.row_scale; f.ldc[i] = q.ldc;
-      long b = (((long)q.M * q.N >> 2) + 255) / 256;
-      b = b < 1 ? 1 : (b > 1024 ? 1024 : b);
-      f.first_wg[i] = wgs;
-      wgs += (int)b;
+      const int k = t.n;
+      f.M[k] = q.M; f.N[k] = q.N; f.nslab[k] = q.nslab; f.acc[k] = q.accumulate; f.ws[k] = q.workspace; f.C[k] = q.C;
+      f.row_scale[k] = q.row_scale; f.ldc[k] = q.ldc;
+      if (!t.add(fold_blocks((long)q.M * q.N >> 2, 1024))) return -6;
     }
-    f.first_wg[f.n] = wgs;
-    hipLaunchKernelGGL(splitk_fold_multi_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, f);
+    f.n = t.n;
+    hipLaunchKernelGGL(splitk_fold_multi_kernel, dim3((unsigned)t.blocks), dim3(256), 0, stream, f);
     SW_CHECK_LAUNCH();
   }
   return 0;
@@ -1642,22 +1587,20 @@ extern "C" int sw_conv3x3_wgrad_fold_multi(int n, const sw_wgrad_fold* folds, hi
   SW_ENTER();
   for (int base = 0; base < n; base += FOLD_MAX) {
     FoldMulti f = {};
-    f.n = n - base < FOLD_MAX ? n - base : FOLD_MAX;
-    int wgs = 0;
+    BatchTable t(f.first_wg);
     size_t lds = 0;
-    for (int i = 0; i < f.n; ++i) {
-      const sw_wgrad_fold& q = folds[base + i];
-      if (q.nslab < 1 || (q.Cin % 4) || (size_t)36 * q.Cin > 65536 || (((uintptr_t)q.dw_oihw) & 15) || (((uintptr_t)q.workspace) & 15)) return -5;
-      int parts = 1;
-      while (q.Cout * parts < 1024 && (q.Cin % (parts * 2 * 4)) == 0 && q.Cin / (parts * 2) >= 32) parts *= 2;
-      f.Cin[i] = q.Cin; f.Cout[i] = q.Cout; f.nslab[i] = q.nslab; f.parts[i] = parts; f.ws[i] = q.workspace; f.out[i] = q.dw_oihw;
-      f.first_wg[i] = wgs;
-      wgs += q.Cout * parts;
+    for (int i = base; i < n && i < base + FOLD_MAX; ++i) {
+      const sw_wgrad_fold& q = folds[i];
+      const int parts = wgrad_fold_parts(q.Cin, q.Cout, q.nslab, q.workspace, q.dw_oihw);
+      if (!parts) return -5;
+      const int k = t.n;
+      f.Cin[k] = q.Cin; f.Cout[k] = q.Cout; f.nslab[k] = q.nslab; f.parts[k] = parts; f.ws[k] = q.workspace; f.out[k] = q.dw_oihw;
+      if (!t.add((long)q.Cout * parts)) return -6;
       const size_t need = (size_t)36 * q.Cin / parts;
       lds = need > lds ? need : lds;
     }
-    f.first_wg[f.n] = wgs;
-    hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3((unsigned)wgs), dim3(256), lds, stream, f);
+    f.n = t.n;
+    hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3((unsigned)t.blocks), dim3(256), lds, stream, f);
     SW_CHECK_LAUNCH();
   }
   return 0;

@@ -23,14 +23,8 @@ constexpr int CHUNK = 1024;                  // elements per workgroup of the st
 constexpr int NBIN = 2048;                   // 11-bit radix digits
 constexpr unsigned KEY_NONE = 0xFFFFFFFFu;   // "not a candidate"
 
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-  unsigned long long z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 __device__ __forceinline__ unsigned hash_key24(unsigned long long seed, unsigned long long pos) {
-  return (unsigned)(splitmix64(seed + pos) >> 40);
+  return (unsigned)(sw_splitmix64(seed + pos) >> 40);
 }
 // ascending unsigned order == DESCENDING float order (larger logits first)
 __device__ __forceinline__ unsigned desc_key(float v) {

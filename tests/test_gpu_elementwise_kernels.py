@@ -380,6 +380,69 @@ def test_sgd_multi_against_float64_and_staged_copies(ops, sdt, first, hyper):
     assert set(ratios) == {"tile64", "conv_tile", "vector", "scalar"}
 
 
+def _sgd_seam_entries(all_live):
+    """25 entries (SW_SGD_MAX_TENSORS + 1): the empty one and the kind-3 one (its own launch) sit inside the first launch's range, the
+    conv tile form, an unaligned parameter and 4097 elements (a second chunk of one element) on both sides of the seam.  sw_sgd_multi
+    cuts its launches by input index, so those two leave the first launch 22 tensors; all_live puts element tensors in their places:
+    24 tensors, every slot of the table and block_start[24] in use"""
+    k1 = dict(name="k1-72/76", shape=(11, 72), mis=0, kind=1, d0=72, ld0=76)
+    k2t = dict(name="k2-32x32", shape=(32, 32, 3, 3), mis=0, kind=2, d0=32, d1=32, d2=32, s0=True, s1=True)
+    k2 = dict(name="k2-40x24", shape=(40, 24, 3, 3), mis=0, kind=2, d0=40, d1=24, d2=24, s0=True, s1=True)
+    k3 = dict(name="k3-64x128", shape=(64, 128), mis=0, kind=3, d0=128, ld0=128 + 8, ld1=64 + 8)
+    el = [dict(name=f"el{n}+{4 * m}B", shape=(n,), mis=m, kind=0) for n in (1, 4095, 4096, 4097) for m in (0, 3)]
+    es = el[:5] + [dict(name="zero", shape=(0,), mis=0, kind=0)] + el[5:] + [k2t, k3, k1, k2] + el + [k2t, k1, el[6], el[7]]
+    if all_live:
+        es[5], es[10] = el[2], el[3]
+    assert len(es) == E.SGD_MAX_TENSORS + 1 and es[24]["shape"] == (4097,) and es[24]["mis"] == 3
+    assert sum(e["kind"] != 3 and e["shape"] != (0,) for e in es[:24]) == (24 if all_live else 22)
+    return es
+
+
+def _sgd_entry(i, e, sdt, first):
+    """entry i on fresh device copies -> (ops.sgd_multi entry, its tensors and staged outputs)"""
+    w, g, buf = E.sgd_state(i, e, 0 if first else 1)
+    pd, gd, bd = _dev(w, "f32", e["mis"]), _dev(g, "f32", e["mis"]), _dev(buf, "f32", e["mis"])
+    (lr, wd), _ = E.sgd_hyper(i)
+    s0 = s1 = st = None
+    if e["kind"] == 1:
+        s0 = _Out((e["shape"][0], e["d0"]), sdt, 0, ld=e["ld0"])
+    elif e["kind"] == 2:
+        s0 = _Out((e["d0"] * 9, e["d1"]), sdt, 0, ld=e["d2"])
+        s1 = _Out((e["d1"] * 9, e["d0"]), sdt, 0, ld=e["d0"])
+    elif e["kind"] == 3:
+        s0 = _Out((e["shape"][0], e["d0"]), sdt, 0, ld=e["ld0"])
+        s1 = _Out((e["d0"], e["shape"][0]), sdt, 0, ld=e["ld1"])
+    if e["kind"]:
+        st = dict(kind=e["kind"], dtype=_tdt(sdt), stage0=s0.t, stage1=None if s1 is None else s1.t,
+                  d0=e["d0"], d1=e.get("d1", 0), d2=e.get("d2", 0), ld0=e.get("ld0", 0), ld1=e.get("ld1", 0))
+    return dict(param=pd, grad=gd, buf=bd, lr=lr, weight_decay=wd, first=first, staging=st), (pd, bd, s0, s1)
+
+
+@pytest.mark.parametrize("all_live", [False, True], ids=["skips", "full_table"])
+@pytest.mark.parametrize("first", [True, False], ids=["first", "later"])
+@pytest.mark.parametrize("sdt", E.DTYPES)
+def test_sgd_multi_across_the_launch_seam_equals_each_entry_alone(ops, sdt, first, all_live):
+    """25 entries in one call: parameter, momentum buffer and every staged copy bit for bit what the same entry gives as a call of
+    its own, and parameter and buffer within sgd_bounds of float64"""
+    es = _sgd_seam_entries(all_live)
+    made = [_sgd_entry(i, e, sdt, first) for i, e in enumerate(es)]
+    ops.sgd_multi([m[0] for m in made], _MOM, _GSCALE)
+    torch.cuda.synchronize()
+    ratios = {}
+    for i, e in enumerate(es):
+        entry, alone = _sgd_entry(i, e, sdt, first)
+        ops.sgd_multi([entry], _MOM, _GSCALE)
+        torch.cuda.synchronize()
+        for k, (a, b) in enumerate(zip(made[i][1], alone)):
+            if a is not None:
+                a, b = (a.cpu().numpy(), b.cpu().numpy()) if k < 2 else (a.host(), b.host())
+                assert E.same_bits(a, b), (e["name"], i, ("param", "buf", "stage0", "stage1")[k])
+        w, g, buf = E.sgd_state(i, e, 0 if first else 1)
+        _sgd_check(e["name"], made[i][1][0].cpu().numpy(), made[i][1][1].cpu().numpy(), w, g, buf, entry["lr"], entry["weight_decay"],
+                   first, ratios, E.sgd_form(e))
+    assert set(ratios) == {"conv_tile", "vector", "scalar"} | (set() if all_live else {"tile64"})
+
+
 @pytest.mark.parametrize("first", [True, False], ids=["first", "later"])
 def test_sgd_momentum_step_against_float64(ops, first):
     ratios = {}

@@ -1348,6 +1348,37 @@ def test_colsum_workspace_form(ops, dtype, M, N, pad):
     np.testing.assert_allclose(cs_b.cpu().numpy(), want, **tol)
 
 
+@pytest.mark.parametrize("dtype", DT)
+def test_colsum_multi_more_parts_and_folds_than_one_launch_holds(ops, dtype):
+    """sw_colsum_partial_multi with 41 parts (CPART_MAX + 1) and sw_colsum_fold_multi with 33 folds (CFOLD_MAX + 1): M = 1, 33, 70 (one
+    chunk, the 32-row floor, more chunks), N = one 16-byte piece and one column slab plus a piece (a second, ragged slab).  Every
+    workspace and every sum bit for bit what the same item gives as a batch of one, and the sums within test_colsum_workspace_form's
+    tolerance of float64"""
+    vec = 8 if dtype == torch.bfloat16 else 4
+    shapes = [(M, N) for M in (1, 33, 70) for N in (vec, 32 * vec + vec)]
+    nan = float("nan")
+    items = []
+    for i in range(41):
+        M, N = shapes[i % len(shapes)]
+        X = _rand((M, N), 900 + i, dtype, 2.0).cuda()
+        rows = ops.colsum_nrows(dtype, M, N)
+        items.append((X, rows, torch.full((rows, N), nan, device="cuda"), torch.full((N,), nan, device="cuda")))
+    ops.colsum_partial_multi([(X, ws) for X, _, ws, _ in items])
+    ops.colsum_fold_multi([(ws, rows, out) for _, rows, ws, out in items[:33]])
+    torch.cuda.synchronize()
+    for i, (X, rows, ws, out) in enumerate(items):
+        M, N = X.shape
+        ws1 = torch.full((rows, N), nan, device="cuda"); out1 = torch.full((N,), nan, device="cuda")
+        ops.colsum_partial_multi([(X, ws1)])
+        ops.colsum_fold_multi([(ws1, rows, out1)])
+        assert not bool(torch.isnan(ws1).any()) and torch.equal(ws, ws1), (i, M, N, "partial rows")
+        if i < 33:
+            assert torch.equal(out, out1), (i, M, N, "fold")
+            np.testing.assert_allclose(out.cpu().numpy(), X.double().sum(0).cpu().numpy(), rtol=2e-5, atol=2e-5 * float(np.sqrt(M)) * 4)
+        else:
+            assert bool(torch.isnan(out).all())
+
+
 def test_copy_multi_and_relu_bwd_out(ops):
     """sw_copy_multi: aligned / unaligned / odd-sized / empty tensors in one launch; sw_relu_bwd with a separate output leaves its gradient input alone"""
     g = torch.Generator().manual_seed(3)
@@ -1456,6 +1487,53 @@ def test_grouped_plain_weight_gradient_gemms_and_multi_fold(ops, dtype):
     for (M, N, K, ns, opt), C, ref in zip(spec, outs, refs):
         err = float((C.double() - ref).abs().max() / ref.abs().max())
         assert err <= 2e-5, (M, N, K, ns, opt, err)
+
+
+def _splitk_fold_f32(ws, C_old, rs, acc):
+    """sw_splitk_fold_multi's summation order in float32: four running sums over the slabs (slab z into sum z % 4 while four are left,
+    the rest into sum 0), (a0 + a1) + (a2 + a3), times the row scale, plus the C that exists"""
+    f = np.float32
+    nslab = ws.shape[0]
+    a = [np.zeros(ws.shape[1:], f) for _ in range(4)]
+    z = 0
+    while z + 4 <= nslab:
+        for k in range(4):
+            a[k] = a[k] + ws[z + k]
+        z += 4
+    for zz in range(z, nslab):
+        a[0] = a[0] + ws[zz]
+    r = (a[0] + a[1]) + (a[2] + a[3])
+    if rs is not None:
+        r = r * rs[:, None]
+    return (r + C_old if acc else r).astype(f)
+
+
+def test_splitk_fold_multi_more_folds_than_one_launch_holds(ops):
+    """25 folds (SFOLD_MAX + 1) of 1, 255 and 257 16-byte pieces (one thread, one block short of full, a second block of one piece) over
+    1, 3, 4 and 5 slabs (tail only, four at a time, four plus a tail), with and without a row scale and an existing C: bit for bit the
+    same fold as a batch of one, and the float32 restatement of the summation order"""
+    g = torch.Generator().manual_seed(11)
+    shapes, slabs = ((1, 1028), (1, 4), (3, 340)), (5, 1, 3, 4)
+    cases, folds, alone = [], [], []
+    for i in range(25):
+        (M, N), nslab = shapes[i % 3], slabs[i % 4]
+        use_rs, acc = (i // 2) % 2 == 0, (i // 3) % 2 == 0
+        ws = torch.randn(nslab, M, N, generator=g).cuda()
+        rs = (torch.rand(M, generator=g) + 0.5).cuda() if use_rs else None
+        C0 = torch.randn(M, N, generator=g) if acc else torch.full((M, N), float("nan"))
+        C, C1 = C0.cuda(), C0.cuda()
+        cases.append((ws, rs, acc, C0, C, C1))
+        folds.append((ws, nslab, C, rs, acc))
+        alone.append((ws, nslab, C1, rs, acc))
+    assert {(c[0].shape, c[1] is None, c[2]) for c in cases[23:]} == {((5, 1, 1028), False, True), ((4, 3, 340), True, False)}   # both sides of the seam
+    ops.splitk_fold_multi(folds)
+    for f in alone:
+        ops.splitk_fold_multi([f])
+    torch.cuda.synchronize()
+    for i, (ws, rs, acc, C0, C, C1) in enumerate(cases):
+        want = _splitk_fold_f32(ws.cpu().numpy(), C0.numpy(), None if rs is None else rs.cpu().numpy(), acc)
+        assert torch.equal(C, C1), (i, "batch of one")
+        assert np.array_equal(C.cpu().numpy(), want), (i, tuple(ws.shape), rs is not None, acc)
 
 
 @pytest.mark.gpu
