@@ -30,6 +30,16 @@ __device__ __forceinline__ unsigned int pack_bf16x2(float a, float b) {
   return (unsigned)f32_to_bf16_bits(a) | ((unsigned)f32_to_bf16_bits(b) << 16);
 }
 
+// flat index of an NHWC element -> (b, y, x, c)
+struct Nhwc { int b, y, x, c; };
+__device__ __forceinline__ Nhwc nhwc_split(long i, int H, int W, int C) {
+  Nhwc p;
+  p.c = (int)(i % C); long r = i / C;
+  p.x = (int)(r % W); r /= W;
+  p.y = (int)(r % H); p.b = (int)(r / H);
+  return p;
+}
+
 // Hash dropout: element i of a tensor is kept when dropout_uniform(splitmix64(seed) + offset, i) >= p.  The keep-mask kernel and the
 // GEMM epilogues draw from this one definition, the host pre-mixes the seed with the same splitmix64.
 __host__ __device__ __forceinline__ uint64_t sw_splitmix64(uint64_t x) {
@@ -97,6 +107,33 @@ template <> struct Elem<unsigned short> {   // bf16 carried as raw 16-bit words
 __device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
 __device__ __forceinline__ float max_keep_nan(float m, float v) { return (v > m || v != v) ? v : m; }
 
+// 16 bytes of T (float: 4 elements, bf16 bits: 8, low half of a word first) <-> float[16 / sizeof(T)]
+template <typename T>
+__device__ __forceinline__ void piece16_load(const T* p, float* v) {
+  const u32x4 q = *(const u32x4*)p;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (sizeof(T) == 2) { v[2 * k] = bf16_bits_to_f32((unsigned short)q[k]); v[2 * k + 1] = bf16_bits_to_f32((unsigned short)(q[k] >> 16)); }
+    else v[k] = __uint_as_float(q[k]);
+  }
+}
+template <typename T>
+__device__ __forceinline__ void piece16_store(T* p, const float* v) {
+  u32x4 o;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) o[k] = sizeof(T) == 2 ? pack_bf16x2(v[2 * k], v[2 * k + 1]) : __float_as_uint(v[k]);
+  *(u32x4*)p = o;
+}
+// V elements of a thread: one scalar access (any alignment) or one 16-byte piece
+template <typename T, int V>
+__device__ __forceinline__ void elems_load(const T* p, float* v) {
+  if (V == 1) v[0] = Elem<T>::load(p); else piece16_load(p, v);
+}
+template <typename T, int V>
+__device__ __forceinline__ void elems_store(T* p, const float* v) {
+  if (V == 1) Elem<T>::store(p, v[0]); else piece16_store(p, v);
+}
+
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -139,6 +176,38 @@ __device__ __forceinline__ float block_reduce_max(float v, float* red) {
   return r;
 }
 
+// ---- loss arithmetic shared by the RPN / detector losses (detector.hip) and the refinement / focal losses (heads.hip)
+// get_deltas(src, tgt) with weights (wx, wy, ww, wh) (box_regression.py:59-62), boxes as x0 y0 x1 y1
+__device__ __forceinline__ void box_deltas(const float* s, const float* g, float wx, float wy, float ww, float wh, float* t) {
+  const float sw = s[2] - s[0], sh = s[3] - s[1], sx = s[0] + 0.5f * sw, sy = s[1] + 0.5f * sh;
+  const float tw = g[2] - g[0], th = g[3] - g[1], tx = g[0] + 0.5f * tw, ty = g[1] + 0.5f * th;
+  t[0] = __fdiv_rn(wx * (tx - sx), sw);
+  t[1] = __fdiv_rn(wy * (ty - sy), sh);
+  t[2] = ww * logf(__fdiv_rn(tw, sw));
+  t[3] = wh * logf(__fdiv_rn(th, sh));
+}
+// max(x, 0) - x y + log(1 + exp(-|x|))   (torch's binary_cross_entropy_with_logits)
+__device__ __forceinline__ float bce_with_logits(float x, float y) { return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))); }
+// One wave over a row of C logits: maximum m, se = sum exp(x - m), and the logsumexp relative to c, the multiple of 64 nearest m:
+// x - c is exact in float32, so a common offset of the row costs no digits (m + log(se) at logits of 3e4 keeps 2e-3 of absolute
+// precision, 1e-3 of the softmax), and a row with |m| < 32 has c = 0 and is computed without offset, bit for bit.
+struct RowCe {
+  float m, se, c, lse;
+  __device__ __forceinline__ float ce(float xt) const { return lse - (xt - c); }     // cross-entropy against the target logit xt
+};
+__device__ __forceinline__ RowCe row_cross_entropy(const float* x, int C, int lane) {
+  RowCe r;
+  r.m = -3.402823466e38f;
+  for (int j = lane; j < C; j += 64) r.m = fmaxf(r.m, x[j]);
+  r.m = wave_reduce_max(r.m);
+  r.se = 0.f;
+  for (int j = lane; j < C; j += 64) r.se += expf(x[j] - r.m);
+  r.se = wave_reduce_sum(r.se);
+  r.c = 64.f * rintf(r.m * 0.015625f);
+  r.lse = (r.m - r.c) + logf(r.se);
+  return r;
+}
+
 // LDS-DMA (buffer_load_dwordx4 ... lds: 16 bytes per lane from a buffer resource straight into LDS at m0 + 16 * lane) issued through
 // inline assembly.  Through the builtin (__builtin_amdgcn_raw_ptr_buffer_load_lds) hipcc's waitcnt pass knows an LDS write is in flight, and
 // in front of the next ds_read_b64_tr_b16 — the transposed-read intrinsic carries no alias information — it puts s_waitcnt vmcnt(0): a
@@ -172,6 +241,26 @@ inline int sw_cu_count() {
 // hipGetLastError() is a per-thread sticky value: a recoverable error of an unrelated earlier HIP call (e.g. torch probing a
 // device) would otherwise be reported by the first SW_CHECK_LAUNCH of this library.  Every entry point starts clean.
 #define SW_ENTER() (void)hipGetLastError()
+
+// ---- host side of the elementwise launches
+// workgroups of `block` threads for a grid-stride loop over n elements, at most `cap`
+inline int grid_for(long n, long cap = 2048, int block = 256) {
+  const long g = (n + block - 1) / block;
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+// f(T()) with T the element type of dtype, then the launch status; -1 for an unknown dtype
+template <typename F>
+inline int dispatch_elem(int dtype, F&& f) {
+  if (dtype == SW_BF16) f((unsigned short)0);
+  else if (dtype == SW_F32) f(0.f);
+  else return -1;
+  return (int)hipGetLastError();
+}
+// do the 16-byte forms apply: a run of C elements of T is whole 16-byte pieces and every pointer is 16-byte aligned
+template <typename T, typename... P>
+inline bool vec16_ok(long C, const P*... ptrs) {
+  return (C * (long)sizeof(T)) % 16 == 0 && (((uintptr_t)ptrs | ...) & 15) == 0;
+}
 #define SW_CHECK_LAUNCH()                         \
   do {                                            \
     hipError_t e__ = hipGetLastError();           \

@@ -12,10 +12,7 @@
 
 namespace {
 
-inline int grid_for_n(long n, int block = 256) {
-  long g = (n + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > 1048576 ? 1048576 : g));
-}
+constexpr long GRID_CAP = 1048576;                             // these kernels' grid-stride loops start up to 2^20 workgroups
 
 // ------------------------------------------------------------------------------------------- input: normalise + pad
 // img u8 [3][h][w] -> out [H][W][4] = (img - mean) / std inside the image, 0 in the padding and in channel 3
@@ -85,82 +82,43 @@ __global__ __launch_bounds__(256) void stem_conv7_kernel(int N, int H, int W, in
   }
 }
 
+// The pooling / FPN kernels below are templates over <T, V>: a thread carries V channels of a pixel, V = 1 with scalar accesses (any
+// C, any alignment) or V = 16 / sizeof(T) with 16-byte pieces (C a multiple of V, 16-byte aligned tensors: vec16_ok).
 // 3x3 max pooling, stride 2, padding 1 (resnet.py:358): out [N][OH][OW][C], OH = (H + 2 - 3) / 2 + 1
-template <typename T>
+template <typename T, int V>
 __global__ void maxpool3x3s2_kernel(int N, int H, int W, int C, int OH, int OW, const T* __restrict__ in, T* __restrict__ out) {
-  const long n = (long)N * OH * OW * C;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); long r = i / C;
-    const int ox = (int)(r % OW); r /= OW;
-    const int oy = (int)(r % OH); const int b = (int)(r / OH);
-    float m = -INFINITY;
-    for (int ky = 0; ky < 3; ++ky) {
-      const int y = oy * 2 - 1 + ky;
-      if (y < 0 || y >= H) continue;
-      for (int kx = 0; kx < 3; ++kx) {
-        const int x = ox * 2 - 1 + kx;
-        if (x < 0 || x >= W) continue;
-        m = max_keep_nan(m, Elem<T>::load(in + (((long)b * H + y) * W + x) * C + c));
-      }
-    }
-    Elem<T>::store(out + i, m);
-  }
-}
-
-// 16-byte pieces (C a multiple of 8 bf16 / 4 f32 elements)
-template <typename T>
-__global__ void maxpool3x3s2_vec_kernel(int N, int H, int W, int C, int OH, int OW, const T* __restrict__ in, T* __restrict__ out) {
-  constexpr int V = 16 / (int)sizeof(T);
   const int cp = C / V;
   const long n = (long)N * OH * OW * cp;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % cp) * V; long r = i / cp;
-    const int ox = (int)(r % OW); r /= OW;
-    const int oy = (int)(r % OH); const int b = (int)(r / OH);
+    const Nhwc o = nhwc_split(i, OH, OW, cp);
     float m[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) m[k] = -INFINITY;
     for (int ky = 0; ky < 3; ++ky) {
-      const int y = oy * 2 - 1 + ky;
+      const int y = o.y * 2 - 1 + ky;
       if (y < 0 || y >= H) continue;
       for (int kx = 0; kx < 3; ++kx) {
-        const int x = ox * 2 - 1 + kx;
+        const int x = o.x * 2 - 1 + kx;
         if (x < 0 || x >= W) continue;
-        const u32x4 q = *(const u32x4*)(in + (((long)b * H + y) * W + x) * C + c);
-        if (sizeof(T) == 2) {
+        float v[V];
+        elems_load<T, V>(in + (((long)o.b * H + y) * W + x) * C + o.c * V, v);
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            m[2 * k] = max_keep_nan(m[2 * k], __uint_as_float(q[k] << 16));
-            m[2 * k + 1] = max_keep_nan(m[2 * k + 1], __uint_as_float(q[k] & 0xFFFF0000u));
-          }
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) m[k] = max_keep_nan(m[k], __uint_as_float(q[k]));
-        }
+        for (int k = 0; k < V; ++k) m[k] = max_keep_nan(m[k], v[k]);
       }
     }
-    u32x4 o;
-    if (sizeof(T) == 2) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = (unsigned)f32_to_bf16_bits(m[2 * k]) | ((unsigned)f32_to_bf16_bits(m[2 * k + 1]) << 16);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = __float_as_uint(m[k]);
-    }
-    *(u32x4*)(out + ((((long)b * OH + oy) * OW + ox) * C + c)) = o;
+    elems_store<T, V>(out + i * V, m);                   // (i * V: the flat index of channel o.c * V of this pixel, C = cp * V)
   }
 }
 
 // ------------------------------------------------------------------------------------------- stride-2 subsample / scatter
+// (T = u32x4 with C counted in pieces: the 16-byte form of these two copies)
 // out[n][y][x][:] = in[n][2y][2x][:]  (the pixels a 1x1 stride-2 convolution reads; also FPN's p6 = max_pool(k 1, s 2) of p5)
 template <typename T>
 __global__ void subsample2_kernel(int N, int H, int W, int C, int OH, int OW, const T* __restrict__ in, T* __restrict__ out) {
   const long n = (long)N * OH * OW * C;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); long r = i / C;
-    const int ox = (int)(r % OW); r /= OW;
-    const int oy = (int)(r % OH); const int b = (int)(r / OH);
-    out[i] = in[(((long)b * H + oy * 2) * W + ox * 2) * C + c];
+    const Nhwc o = nhwc_split(i, OH, OW, C);
+    out[i] = in[(((long)o.b * H + o.y * 2) * W + o.x * 2) * C + o.c];
   }
 }
 // backward: out [N][H][W][C] = g at the even pixels, 0 elsewhere (fully written)
@@ -168,11 +126,9 @@ template <typename T>
 __global__ void scatter2_kernel(int N, int H, int W, int C, int OH, int OW, const T* __restrict__ g, T* __restrict__ out) {
   const long n = (long)N * H * W * C;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); long r = i / C;
-    const int x = (int)(r % W); r /= W;
-    const int y = (int)(r % H); const int b = (int)(r / H);
+    const Nhwc p = nhwc_split(i, H, W, C);
     T v = {};
-    if (!(y & 1) && !(x & 1)) v = g[(((long)b * OH + (y >> 1)) * OW + (x >> 1)) * C + c];
+    if (!(p.y & 1) && !(p.x & 1)) v = g[(((long)p.b * OH + (p.y >> 1)) * OW + (p.x >> 1)) * C + p.c];
     out[i] = v;
   }
 }
@@ -187,86 +143,35 @@ __global__ void add_relu_kernel(long n, const T* __restrict__ a, const T* __rest
   }
 }
 // out [N][2h][2w][C] = lateral + nearest-neighbour 2x upsampling of top [N][h][w][C]  (fpn.py:142-144)
-template <typename T>
+template <typename T, int V>
 __global__ void upsample2_add_kernel(int N, int h, int w, int C, const T* __restrict__ lateral, const T* __restrict__ top,
                                      T* __restrict__ out) {
-  const long n = (long)N * 2 * h * 2 * w * C;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); long r = i / C;
-    const int x = (int)(r % (2 * w)); r /= (2 * w);
-    const int y = (int)(r % (2 * h)); const int b = (int)(r / (2 * h));
-    Elem<T>::store(out + i, Elem<T>::load(lateral + i) + Elem<T>::load(top + (((long)b * h + (y >> 1)) * w + (x >> 1)) * C + c));
-  }
-}
-// the same with 16-byte pieces (C a multiple of 8 bf16 / 4 f32 elements, 16-byte aligned tensors): one thread = one piece of a pixel
-template <typename T>
-__global__ void upsample2_add_vec_kernel(int N, int h, int w, int C, const T* __restrict__ lateral, const T* __restrict__ top,
-                                         T* __restrict__ out) {
-  constexpr int V = 16 / (int)sizeof(T);
   const int cp = C / V;
   const long n = (long)N * 2 * h * 2 * w * cp;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % cp) * V; long r = i / cp;
-    const int x = (int)(r % (2 * w)); r /= (2 * w);
-    const int y = (int)(r % (2 * h)); const int b = (int)(r / (2 * h));
-    const u32x4 a = *(const u32x4*)(lateral + i * V);
-    const u32x4 t = *(const u32x4*)(top + (((long)b * h + (y >> 1)) * w + (x >> 1)) * C + c);
-    u32x4 o;
-    if (sizeof(T) == 2) {
+    const Nhwc p = nhwc_split(i, 2 * h, 2 * w, cp);
+    float a[V], t[V];
+    elems_load<T, V>(lateral + i * V, a);
+    elems_load<T, V>(top + (((long)p.b * h + (p.y >> 1)) * w + (p.x >> 1)) * C + p.c * V, t);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float lo = __uint_as_float(a[k] << 16) + __uint_as_float(t[k] << 16);
-        const float hi = __uint_as_float(a[k] & 0xFFFF0000u) + __uint_as_float(t[k] & 0xFFFF0000u);
-        o[k] = (unsigned)f32_to_bf16_bits(lo) | ((unsigned)f32_to_bf16_bits(hi) << 16);
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = __float_as_uint(__uint_as_float(a[k]) + __uint_as_float(t[k]));
-    }
-    *(u32x4*)(out + i * V) = o;
+    for (int k = 0; k < V; ++k) a[k] += t[k];
+    elems_store<T, V>(out + i * V, a);
   }
 }
-// backward of the upsampling: out [N][h][w][C] = sum of the 2x2 block of g [N][2h][2w][C] (fixed order)
-template <typename T>
+// backward of the upsampling: out [N][h][w][C] = sum of the 2x2 block of g [N][2h][2w][C], (a + b) + (c + d) per element in f32
+template <typename T, int V>
 __global__ void downsample2_sum_kernel(int N, int h, int w, int C, const T* __restrict__ g, T* __restrict__ out) {
-  const long n = (long)N * h * w * C;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); long r = i / C;
-    const int x = (int)(r % w); r /= w;
-    const int y = (int)(r % h); const int b = (int)(r / h);
-    const T* p = g + (((long)b * 2 * h + 2 * y) * 2 * w + 2 * x) * C + c;
-    const float v = (Elem<T>::load(p) + Elem<T>::load(p + C)) + (Elem<T>::load(p + (long)2 * w * C) + Elem<T>::load(p + (long)2 * w * C + C));
-    Elem<T>::store(out + i, v);
-  }
-}
-
-// the same with 16-byte pieces: (a + b) + (c + d) per element in f32, as above
-template <typename T>
-__global__ void downsample2_sum_vec_kernel(int N, int h, int w, int C, const T* __restrict__ g, T* __restrict__ out) {
-  constexpr int V = 16 / (int)sizeof(T);
   const int cp = C / V;
   const long n = (long)N * h * w * cp;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % cp) * V; long r = i / cp;
-    const int x = (int)(r % w); r /= w;
-    const int y = (int)(r % h); const int b = (int)(r / h);
-    const T* p = g + (((long)b * 2 * h + 2 * y) * 2 * w + 2 * x) * C + c;
-    const u32x4 q0 = *(const u32x4*)p, q1 = *(const u32x4*)(p + C), q2 = *(const u32x4*)(p + (long)2 * w * C), q3 = *(const u32x4*)(p + (long)2 * w * C + C);
-    u32x4 o;
-    if (sizeof(T) == 2) {
+    const Nhwc o = nhwc_split(i, h, w, cp);
+    const T* p = g + (((long)o.b * 2 * h + 2 * o.y) * 2 * w + 2 * o.x) * C + o.c * V;
+    float q0[V], q1[V], q2[V], q3[V];
+    elems_load<T, V>(p, q0); elems_load<T, V>(p + C, q1);
+    elems_load<T, V>(p + (long)2 * w * C, q2); elems_load<T, V>(p + (long)2 * w * C + C, q3);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float lo = (__uint_as_float(q0[k] << 16) + __uint_as_float(q1[k] << 16)) + (__uint_as_float(q2[k] << 16) + __uint_as_float(q3[k] << 16));
-        const float hi = (__uint_as_float(q0[k] & 0xFFFF0000u) + __uint_as_float(q1[k] & 0xFFFF0000u)) +
-                         (__uint_as_float(q2[k] & 0xFFFF0000u) + __uint_as_float(q3[k] & 0xFFFF0000u));
-        o[k] = (unsigned)f32_to_bf16_bits(lo) | ((unsigned)f32_to_bf16_bits(hi) << 16);
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        o[k] = __float_as_uint((__uint_as_float(q0[k]) + __uint_as_float(q1[k])) + (__uint_as_float(q2[k]) + __uint_as_float(q3[k])));
-    }
-    *(u32x4*)(out + ((((long)b * h + y) * w + x) * C + c)) = o;
+    for (int k = 0; k < V; ++k) q0[k] = (q0[k] + q1[k]) + (q2[k] + q3[k]);
+    elems_store<T, V>(out + i * V, q0);
   }
 }
 
@@ -310,24 +215,32 @@ __device__ __forceinline__ float align_coord(float start, int p, float bin, int 
 
 // thread = (listed ROI, bin, channel): consecutive threads = consecutive channels -> coalesced NHWC reads.  Only the ROIs listed in
 // `sel` (n_sel row indices into rois / out) are computed: the FPN pooler calls once per level with that level's ROIs.
-// out [R][C][PH][PW] (the reference's flatten order: fc1.weight needs no permutation), row pitch ld.
+// `o` = where the bin's element sits in out / gout [R][C][PH][PW] (the reference's flatten order: fc1.weight needs no permutation),
+// row pitch ld.
+struct AlignBin { int ph, pw, c; long o; AlignGeom g; };
+__device__ __forceinline__ long align_bins(int n_sel, const int* n_sel_dev, int PH, int PW, int C) {
+  return (long)(n_sel_dev ? min(n_sel_dev[0], n_sel) : n_sel) * PH * PW * C;     // device count: no host round trip for the level lists
+}
+__device__ __forceinline__ AlignBin align_bin(long i, int C, int PH, int PW, float scale, int sampling_ratio, const float* rois,
+                                              const int* sel, long ld) {
+  const Nhwc p = nhwc_split(i, PH, PW, C);                   // (listed ROI, ph, pw, c)
+  const int row = sel[p.b];
+  return {p.y, p.x, p.c, (long)row * ld + ((long)p.c * PH + p.y) * PW + p.x, align_geom(rois + (long)row * 5, scale, PH, PW, sampling_ratio)};
+}
 template <typename T>
 __global__ void roi_align_fwd_kernel(int H, int W, int C, int PH, int PW, float scale, int sampling_ratio,
                                      const T* __restrict__ feat, const float* __restrict__ rois, const int* __restrict__ sel,
                                      int n_sel, const int* __restrict__ n_sel_dev, T* __restrict__ out, long ld) {
-  const long n = (long)(n_sel_dev ? min(n_sel_dev[0], n_sel) : n_sel) * PH * PW * C;     // device count: no host round trip for the level lists
+  const long n = align_bins(n_sel, n_sel_dev, PH, PW, C);
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); long r = i / C;
-    const int pw = (int)(r % PW); r /= PW;
-    const int ph = (int)(r % PH); const int s = (int)(r / PH);
-    const int row = sel[s];
-    const AlignGeom g = align_geom(rois + (long)row * 5, scale, PH, PW, sampling_ratio);
-    const T* f = feat + (long)g.batch * H * W * C + c;
+    const AlignBin b = align_bin(i, C, PH, PW, scale, sampling_ratio, rois, sel, ld);
+    const AlignGeom& g = b.g;
+    const T* f = feat + (long)g.batch * H * W * C + b.c;
     float v = 0.f;
     for (int iy = 0; iy < g.grid_h; ++iy) {
-      const float y = align_coord(g.start_h, ph, g.bin_h, iy, g.grid_h);
+      const float y = align_coord(g.start_h, b.ph, g.bin_h, iy, g.grid_h);
       for (int ix = 0; ix < g.grid_w; ++ix) {
-        const float x = align_coord(g.start_w, pw, g.bin_w, ix, g.grid_w);
+        const float x = align_coord(g.start_w, b.pw, g.bin_w, ix, g.grid_w);
         int yl, xl, yh, xh; float wg[4];
         if (!align_corners(H, W, y, x, &yl, &xl, &yh, &xh, wg)) continue;
         // ((w1 v1 + w2 v2) + w3 v3) + w4 v4 added to the running sum, as ROIAlign_cpu.cpp:204-206 evaluates it
@@ -338,7 +251,7 @@ __global__ void roi_align_fwd_kernel(int H, int W, int C, int PH, int PW, float 
         v = __fadd_rn(v, t);
       }
     }
-    Elem<T>::store(out + (long)row * ld + ((long)c * PH + ph) * PW + pw, __fdiv_rn(v, g.count));
+    Elem<T>::store(out + b.o, __fdiv_rn(v, g.count));
   }
 }
 // backward: dfeat f32 [N][H][W][C] (caller zero-fills) += w * g / count by f32 atomics (ROIAlign_cpu.cpp:286-400).
@@ -371,50 +284,13 @@ __device__ __forceinline__ AxisW align_axis_weights(float start, int p, float bi
   }
   return a;
 }
-template <typename T>
-__global__ void roi_align_bwd_kernel(int H, int W, int C, int PH, int PW, float scale, int sampling_ratio,
-                                     const T* __restrict__ gout, long ld, const float* __restrict__ rois,
-                                     const int* __restrict__ sel, int n_sel, const int* __restrict__ n_sel_dev, float* __restrict__ dfeat) {
-  const long n = (long)(n_sel_dev ? min(n_sel_dev[0], n_sel) : n_sel) * PH * PW * C;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); long r = i / C;
-    const int pw = (int)(r % PW); r /= PW;
-    const int ph = (int)(r % PH); const int s = (int)(r / PH);
-    const int row = sel[s];
-    const AlignGeom g = align_geom(rois + (long)row * 5, scale, PH, PW, sampling_ratio);
-    const float go = Elem<T>::load(gout + (long)row * ld + ((long)c * PH + ph) * PW + pw);
-    float* d = dfeat + (long)g.batch * H * W * C + c;
-    if (g.grid_h < AXIS_MAX && g.grid_w < AXIS_MAX && g.bin_h <= (float)g.grid_h && g.bin_w <= (float)g.grid_w) {     // (sample spacing <= 1)
-      const AxisW ay = align_axis_weights(g.start_h, ph, g.bin_h, g.grid_h, H);
-      const AxisW ax = align_axis_weights(g.start_w, pw, g.bin_w, g.grid_w, W);
-      if (ay.base < 0 || ax.base < 0) continue;
-      const float gs = __fdiv_rn(go, g.count);
-#pragma unroll
-      for (int ry = 0; ry < AXIS_MAX; ++ry) {
-        if (ay.w[ry] == 0.f) continue;
-        const float gy = __fmul_rn(gs, ay.w[ry]);
-        float* drow = d + (long)(ay.base + ry) * W * C;
-#pragma unroll
-        for (int rx = 0; rx < AXIS_MAX; ++rx)
-          if (ax.w[rx] != 0.f) atomicAdd(drow + (long)(ax.base + rx) * C, __fmul_rn(gy, ax.w[rx]));
-      }
-      continue;
-    }
-    for (int iy = 0; iy < g.grid_h; ++iy) {
-      const float y = align_coord(g.start_h, ph, g.bin_h, iy, g.grid_h);
-      for (int ix = 0; ix < g.grid_w; ++ix) {
-        const float x = align_coord(g.start_w, pw, g.bin_w, ix, g.grid_w);
-        int yl, xl, yh, xh; float wg[4];
-        if (!align_corners(H, W, y, x, &yl, &xl, &yh, &xh, wg)) continue;
-        atomicAdd(d + ((long)yl * W + xl) * C, __fdiv_rn(__fmul_rn(go, wg[0]), g.count));
-        atomicAdd(d + ((long)yl * W + xh) * C, __fdiv_rn(__fmul_rn(go, wg[1]), g.count));
-        atomicAdd(d + ((long)yh * W + xl) * C, __fdiv_rn(__fmul_rn(go, wg[2]), g.count));
-        atomicAdd(d + ((long)yh * W + xh) * C, __fdiv_rn(__fmul_rn(go, wg[3]), g.count));
-      }
-    }
-  }
-}
-
+// One kernel for both accumulators: Acc::init(arg) prepares the launch (false: nothing to add), Acc::add(p, v) adds contribution v into *p.
+struct AccF32 {                                              // f32 atomics, arrival order: the last bits differ between runs
+  typedef float type;
+  struct Arg {};
+  __device__ __forceinline__ bool init(Arg) { return true; }
+  __device__ __forceinline__ void add(float* p, float v) const { atomicAdd(p, v); }
+};
 // Deterministic backward (round 6).  The f32 atomics above add in arrival order: two runs of one iteration differ in the last bits of
 // the feature gradients, the student drifts, pseudo boxes jitter, position-keyed anchor sampling flips (tests had to allow 6e-2 on the
 // pseudo RPN losses).  Here the SAME contributions are accumulated as 64-bit fixed-point integers — integer addition commutes, so the sum
@@ -425,52 +301,59 @@ __global__ void roi_align_bwd_kernel(int H, int W, int C, int PH, int PW, float 
 // scaled by 2^k yields the same integers.  acc [N][H][W][C] int64, zero-filled by the caller; fx_to_float_kernel turns it into the map
 // (NaN / Inf in gout: absmax reports it, the whole map comes out NaN — the f32 form poisoned the pixels the ROI touched).
 constexpr int FX_BITS = 40;
-template <typename T>
-__global__ void roi_align_bwd_fx_kernel(int H, int W, int C, int PH, int PW, float scale, int sampling_ratio,
-                                        const T* __restrict__ gout, long ld, const float* __restrict__ rois,
-                                        const int* __restrict__ sel, int n_sel, const int* __restrict__ n_sel_dev,
-                                        const float* __restrict__ absmax, unsigned long long* __restrict__ acc) {
-  const float am = absmax[0];
-  if (!(am > 0.f) || !__builtin_isfinite(am)) return;               // zero gradient: nothing to add; NaN / Inf: the conversion reports it
-  int e;
-  (void)frexpf(am, &e);
-  const int sh = FX_BITS - e;                                        // v * 2^sh, |v| <= am < 2^e
-  const long n = (long)(n_sel_dev ? min(n_sel_dev[0], n_sel) : n_sel) * PH * PW * C;
+struct AccFx {
+  typedef unsigned long long type;
+  typedef const float* Arg;                                  // absmax: max |gout|, one float in device memory
+  int sh;                                                    // v * 2^sh, |v| <= am < 2^e
+  __device__ __forceinline__ bool init(Arg absmax) {
+    const float am = absmax[0];
+    if (!(am > 0.f) || !__builtin_isfinite(am)) return false;          // zero gradient: nothing to add; NaN / Inf: the conversion reports it
+    int e;
+    (void)frexpf(am, &e);
+    sh = FX_BITS - e;
+    return true;
+  }
+  __device__ __forceinline__ void add(unsigned long long* p, float v) const { atomicAdd(p, (unsigned long long)__float2ll_rn(ldexpf(v, sh))); }
+};
+template <typename T, typename Acc>
+__global__ void roi_align_bwd_kernel(int H, int W, int C, int PH, int PW, float scale, int sampling_ratio,
+                                     const T* __restrict__ gout, long ld, const float* __restrict__ rois,
+                                     const int* __restrict__ sel, int n_sel, const int* __restrict__ n_sel_dev,
+                                     typename Acc::Arg arg, typename Acc::type* __restrict__ dfeat) {
+  Acc acc;
+  if (!acc.init(arg)) return;
+  const long n = align_bins(n_sel, n_sel_dev, PH, PW, C);
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); long r = i / C;
-    const int pw = (int)(r % PW); r /= PW;
-    const int ph = (int)(r % PH); const int s = (int)(r / PH);
-    const int row = sel[s];
-    const AlignGeom g = align_geom(rois + (long)row * 5, scale, PH, PW, sampling_ratio);
-    const float go = Elem<T>::load(gout + (long)row * ld + ((long)c * PH + ph) * PW + pw);
-    unsigned long long* d = acc + (long)g.batch * H * W * C + c;
-    auto add = [&](unsigned long long* p, float v) { atomicAdd(p, (unsigned long long)__float2ll_rn(ldexpf(v, sh))); };
-    if (g.grid_h < AXIS_MAX && g.grid_w < AXIS_MAX && g.bin_h <= (float)g.grid_h && g.bin_w <= (float)g.grid_w) {
-      const AxisW ay = align_axis_weights(g.start_h, ph, g.bin_h, g.grid_h, H);
-      const AxisW ax = align_axis_weights(g.start_w, pw, g.bin_w, g.grid_w, W);
+    const AlignBin b = align_bin(i, C, PH, PW, scale, sampling_ratio, rois, sel, ld);
+    const AlignGeom& g = b.g;
+    const float go = Elem<T>::load(gout + b.o);
+    typename Acc::type* d = dfeat + (long)g.batch * H * W * C + b.c;
+    if (g.grid_h < AXIS_MAX && g.grid_w < AXIS_MAX && g.bin_h <= (float)g.grid_h && g.bin_w <= (float)g.grid_w) {     // (sample spacing <= 1)
+      const AxisW ay = align_axis_weights(g.start_h, b.ph, g.bin_h, g.grid_h, H);
+      const AxisW ax = align_axis_weights(g.start_w, b.pw, g.bin_w, g.grid_w, W);
       if (ay.base < 0 || ax.base < 0) continue;
       const float gs = __fdiv_rn(go, g.count);
 #pragma unroll
       for (int ry = 0; ry < AXIS_MAX; ++ry) {
         if (ay.w[ry] == 0.f) continue;
         const float gy = __fmul_rn(gs, ay.w[ry]);
-        unsigned long long* drow = d + (long)(ay.base + ry) * W * C;
+        typename Acc::type* drow = d + (long)(ay.base + ry) * W * C;
 #pragma unroll
         for (int rx = 0; rx < AXIS_MAX; ++rx)
-          if (ax.w[rx] != 0.f) add(drow + (long)(ax.base + rx) * C, __fmul_rn(gy, ax.w[rx]));
+          if (ax.w[rx] != 0.f) acc.add(drow + (long)(ax.base + rx) * C, __fmul_rn(gy, ax.w[rx]));
       }
       continue;
     }
     for (int iy = 0; iy < g.grid_h; ++iy) {
-      const float y = align_coord(g.start_h, ph, g.bin_h, iy, g.grid_h);
+      const float y = align_coord(g.start_h, b.ph, g.bin_h, iy, g.grid_h);
       for (int ix = 0; ix < g.grid_w; ++ix) {
-        const float x = align_coord(g.start_w, pw, g.bin_w, ix, g.grid_w);
+        const float x = align_coord(g.start_w, b.pw, g.bin_w, ix, g.grid_w);
         int yl, xl, yh, xh; float wg[4];
         if (!align_corners(H, W, y, x, &yl, &xl, &yh, &xh, wg)) continue;
-        add(d + ((long)yl * W + xl) * C, __fdiv_rn(__fmul_rn(go, wg[0]), g.count));
-        add(d + ((long)yl * W + xh) * C, __fdiv_rn(__fmul_rn(go, wg[1]), g.count));
-        add(d + ((long)yh * W + xl) * C, __fdiv_rn(__fmul_rn(go, wg[2]), g.count));
-        add(d + ((long)yh * W + xh) * C, __fdiv_rn(__fmul_rn(go, wg[3]), g.count));
+        acc.add(d + ((long)yl * W + xl) * C, __fdiv_rn(__fmul_rn(go, wg[0]), g.count));
+        acc.add(d + ((long)yl * W + xh) * C, __fdiv_rn(__fmul_rn(go, wg[1]), g.count));
+        acc.add(d + ((long)yh * W + xl) * C, __fdiv_rn(__fmul_rn(go, wg[2]), g.count));
+        acc.add(d + ((long)yh * W + xh) * C, __fdiv_rn(__fmul_rn(go, wg[3]), g.count));
       }
     }
   }
@@ -481,7 +364,7 @@ __global__ void fx_to_float_kernel(long n, const long long* __restrict__ acc, co
   const bool bad = !__builtin_isfinite(am);                           // NaN or Inf somewhere in the gradient
   int e = 0;
   if (!bad) (void)frexpf(am, &e);
-  const double inv = ldexp(1.0, e - FX_BITS);                         // the exact inverse of roi_align_bwd_fx_kernel's 2^(40 - e)
+  const double inv = ldexp(1.0, e - FX_BITS);                         // the exact inverse of AccFx's 2^(40 - e)            
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
     Elem<T>::store(out + i, bad ? __uint_as_float(0x7FC00000u) : (float)((double)acc[i] * inv));
 }
@@ -506,18 +389,14 @@ __global__ __launch_bounds__(256) void rpn_loss_kernel(long n, long n_anchors, c
     float dl = 0.f;
     if (lab >= 0) {
       const float y = (float)lab;
-      // max(x, 0) - x y + log(1 + exp(-|x|))   (torch's binary_cross_entropy_with_logits)
-      s_obj += fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
+      s_obj += bce_with_logits(x, y);
       dl = (1.f / (1.f + expf(-x)) - y) * inv_norm;
     }
     if (dlogits) dlogits[i] = dl;
     float dd[4] = {0.f, 0.f, 0.f, 0.f};
     if (lab == 1) {
-      const float* a = anchors + (i % n_anchors) * 4;
-      const float* g = gt_boxes + i * 4;
-      const float sw = a[2] - a[0], sh = a[3] - a[1], sx = a[0] + 0.5f * sw, sy = a[1] + 0.5f * sh;
-      const float tw = g[2] - g[0], th = g[3] - g[1], tx = g[0] + 0.5f * tw, ty = g[1] + 0.5f * th;
-      const float t[4] = {wx * (tx - sx) / sw, wy * (ty - sy) / sh, ww * logf(tw / sw), wh * logf(th / sh)};
+      float t[4];
+      box_deltas(anchors + (i % n_anchors) * 4, gt_boxes + i * 4, wx, wy, ww, wh, t);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float e = deltas[i * 4 + k] - t[k];
@@ -587,8 +466,8 @@ __global__ __launch_bounds__(256) void stage_weights_multi_kernel(int n, const s
         else if (sizeof(T) == 4) *(f32x4*)((float*)d.dst + i) = v;
         else {
           unsigned int* o = (unsigned int*)((unsigned short*)d.dst + i);
-          o[0] = (unsigned)f32_to_bf16_bits(v[0]) | ((unsigned)f32_to_bf16_bits(v[1]) << 16);
-          o[1] = (unsigned)f32_to_bf16_bits(v[2]) | ((unsigned)f32_to_bf16_bits(v[3]) << 16);
+          o[0] = pack_bf16x2(v[0], v[1]);
+          o[1] = pack_bf16x2(v[2], v[3]);
         }
       }
     } else {
@@ -660,16 +539,10 @@ __global__ __launch_bounds__(256) void det_loss_partial_kernel(
     for (long a = lo + threadIdx.x; a < hi; a += blockDim.x) {
       const long i = base + a;
       const int lab = labels[i];
-      if (lab >= 0) {
-        const float x = logits[i], y = (float)lab;
-        s_obj += fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));        // as rpn_loss_kernel
-      }
+      if (lab >= 0) s_obj += bce_with_logits(logits[i], (float)lab);
       if (lab == 1) {
-        const float* an = anchors + a * 4;
-        const float* g = matched + i * 4;
-        const float sw = an[2] - an[0], sh = an[3] - an[1], sx = an[0] + 0.5f * sw, sy = an[1] + 0.5f * sh;
-        const float tw = g[2] - g[0], th = g[3] - g[1], tx = g[0] + 0.5f * tw, ty = g[1] + 0.5f * th;
-        const float t[4] = {rx * (tx - sx) / sw, ry * (ty - sy) / sh, rw * logf(tw / sw), rh * logf(th / sh)};
+        float t[4];
+        box_deltas(anchors + a * 4, matched + i * 4, rx, ry, rw, rh, t);
 #pragma unroll
         for (int k = 0; k < 4; ++k) s_loc += fabsf(deltas[i * 4 + k] - t[k]);
         s_fg += 1.f;
@@ -701,22 +574,11 @@ __global__ __launch_bounds__(256) void det_loss_partial_kernel(
     const float* x = roi_logits + r * ld;
     const int t = roi_cls[r];
     if ((unsigned)t >= (unsigned)C) { s_ce = nan; continue; }            // (focal_loss_kernel's rule for a class outside [0, C))
-    float m = -FLT_MAX;
-    for (int j = lane; j < C; j += 64) m = fmaxf(m, x[j]);
-    m = wave_reduce_max(m);
-    float se = 0.f;
-    for (int j = lane; j < C; j += 64) se += expf(x[j] - m);
-    se = wave_reduce_sum(se);
-    const float c = 64.f * rintf(m * 0.015625f);                          // as focal_loss_kernel (heads.hip): exact offset, 0 for |m| < 32
-    const float ce = (m - c) + logf(se) - (x[t] - c);
+    const float ce = row_cross_entropy(x, C, lane).ce(x[t]);
     s_ce += powf(fmaxf(1.f - expf(-ce), 0.f), gamma) * ce;              // gamma 0: the plain cross-entropy term
     if (t < K) {
-      const float* s = roi_boxes + r * 4;
-      const float* g = roi_gt + r * 4;
-      const float sw = s[2] - s[0], sh = s[3] - s[1], sx = s[0] + 0.5f * sw, sy = s[1] + 0.5f * sh;
-      const float tw = g[2] - g[0], th = g[3] - g[1], tx = g[0] + 0.5f * tw, ty = g[1] + 0.5f * th;
-      const float tg[4] = {__fdiv_rn(bx * (tx - sx), sw), __fdiv_rn(by * (ty - sy), sh), bw * logf(__fdiv_rn(tw, sw)),
-                           bh * logf(__fdiv_rn(th, sh))};              // as oicr_refine_loss_kernel (box_regression.py:59-62)
+      float tg[4];
+      box_deltas(roi_boxes + r * 4, roi_gt + r * 4, bx, by, bw, bh, tg);
       const float* pd = x + C + 4 * t;
 #pragma unroll
       for (int k = 0; k < 4; ++k) s_box += fabsf(pd[k] - tg[k]);
@@ -758,21 +620,18 @@ __global__ void det_loss_fold_kernel(int n_img, int chunks, int rchunks, const f
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL_BF16, CALL_F32) \
-  if ((dtype) == SW_BF16) { CALL_BF16; } else if ((dtype) == SW_F32) { CALL_F32; } else return -1;
+// every launch below: 256 threads, a grid-stride loop over n items
+#define LAUNCH_N(kernel, n, ...) hipLaunchKernelGGL((kernel), dim3(grid_for((n), GRID_CAP)), dim3(256), 0, stream, __VA_ARGS__)
 
 extern "C" int sw_preprocess_pad(int dtype, int h, int w, int H, int W, const uint8_t* img_chw, const float* mean3,
                                  const float* std3, void* out_nhwc4, hipStream_t stream) {
   SW_ENTER();
   if (h > H || w > W || H <= 0 || W <= 0) return -5;
-  const long n = (long)H * W;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(preprocess_pad_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, h, w, H, W, img_chw,
-                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (unsigned short*)out_nhwc4),
-    hipLaunchKernelGGL(preprocess_pad_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, h, w, H, W, img_chw, mean3[0],
-                       mean3[1], mean3[2], std3[0], std3[1], std3[2], (float*)out_nhwc4));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    LAUNCH_N(preprocess_pad_kernel<T>, (long)H * W, h, w, H, W, img_chw, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2],
+             (T*)out_nhwc4);
+  });
 }
 
 extern "C" int sw_stem_conv7x7(int dtype, int N, int H, int W, const void* in_nhwc4, const float* w_oihw, const float* scale,
@@ -782,13 +641,11 @@ extern "C" int sw_stem_conv7x7(int dtype, int N, int H, int W, const void* in_nh
   if (N <= 0 || OH <= 0 || OW <= 0) return 0;
   const long tiles = (long)N * ((OH + 7) / 8) * ((OW + 7) / 8);
   if (tiles > 2147483647L) return -6;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(stem_conv7_kernel<unsigned short>, dim3((unsigned)tiles), dim3(256), 0, stream, N, H, W, OH, OW,
-                       (const unsigned short*)in_nhwc4, w_oihw, scale, bias, (unsigned short*)out_nhwc64),
-    hipLaunchKernelGGL(stem_conv7_kernel<float>, dim3((unsigned)tiles), dim3(256), 0, stream, N, H, W, OH, OW,
-                       (const float*)in_nhwc4, w_oihw, scale, bias, (float*)out_nhwc64));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(stem_conv7_kernel<T>, dim3((unsigned)tiles), dim3(256), 0, stream, N, H, W, OH, OW, (const T*)in_nhwc4, w_oihw,
+                       scale, bias, (T*)out_nhwc64);
+  });
 }
 
 extern "C" int sw_maxpool3x3s2(int dtype, int N, int H, int W, int C, const void* in, void* out, hipStream_t stream) {
@@ -796,25 +653,12 @@ extern "C" int sw_maxpool3x3s2(int dtype, int N, int H, int W, int C, const void
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
   const long n = (long)N * OH * OW * C;
   if (n <= 0) return 0;
-  {
-    const int V = dtype == SW_BF16 ? 8 : 4;
-    if ((C % V) == 0 && ((((uintptr_t)in | (uintptr_t)out) & 15) == 0)) {
-      DISPATCH_T(dtype,
-        hipLaunchKernelGGL(maxpool3x3s2_vec_kernel<unsigned short>, dim3(grid_for_n(n / V)), dim3(256), 0, stream, N, H, W, C, OH, OW,
-                           (const unsigned short*)in, (unsigned short*)out),
-        hipLaunchKernelGGL(maxpool3x3s2_vec_kernel<float>, dim3(grid_for_n(n / V)), dim3(256), 0, stream, N, H, W, C, OH, OW,
-                           (const float*)in, (float*)out));
-      SW_CHECK_LAUNCH();
-      return 0;
-    }
-  }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(maxpool3x3s2_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, N, H, W, C, OH, OW,
-                       (const unsigned short*)in, (unsigned short*)out),
-    hipLaunchKernelGGL(maxpool3x3s2_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, N, H, W, C, OH, OW, (const float*)in,
-                       (float*)out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    constexpr int V = 16 / (int)sizeof(T);
+    if (vec16_ok<T>(C, in, out)) LAUNCH_N((maxpool3x3s2_kernel<T, V>), n / V, N, H, W, C, OH, OW, (const T*)in, (T*)out);
+    else LAUNCH_N((maxpool3x3s2_kernel<T, 1>), n, N, H, W, C, OH, OW, (const T*)in, (T*)out);
+  });
 }
 
 extern "C" int sw_subsample2x(int dtype, int N, int H, int W, int C, const void* in, void* out, hipStream_t stream) {
@@ -822,23 +666,13 @@ extern "C" int sw_subsample2x(int dtype, int N, int H, int W, int C, const void*
   const int OH = (H + 1) / 2, OW = (W + 1) / 2;
   const long n = (long)N * OH * OW * C;
   if (n <= 0) return 0;
-  {                                                           // a copy: 16-byte pieces of a pixel's channel run when they exist
-    const long es = dtype == SW_BF16 ? 2 : 4;
-    if (((long)C * es) % 16 == 0 && ((((uintptr_t)in | (uintptr_t)out) & 15) == 0) && (dtype == SW_BF16 || dtype == SW_F32)) {
-      const int Cp = (int)((long)C * es / 16);
-      hipLaunchKernelGGL(subsample2_kernel<u32x4>, dim3(grid_for_n((long)N * OH * OW * Cp)), dim3(256), 0, stream, N, H, W, Cp, OH, OW,
-                         (const u32x4*)in, (u32x4*)out);
-      SW_CHECK_LAUNCH();
-      return 0;
-    }
-  }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(subsample2_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, N, H, W, C, OH, OW,
-                       (const unsigned short*)in, (unsigned short*)out),
-    hipLaunchKernelGGL(subsample2_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, N, H, W, C, OH, OW, (const float*)in,
-                       (float*)out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    constexpr int V = 16 / (int)sizeof(T);
+    if (vec16_ok<T>(C, in, out))                              // a copy: 16-byte pieces of a pixel's channel run when they exist
+      LAUNCH_N(subsample2_kernel<u32x4>, n / V, N, H, W, C / V, OH, OW, (const u32x4*)in, (u32x4*)out);
+    else LAUNCH_N(subsample2_kernel<T>, n, N, H, W, C, OH, OW, (const T*)in, (T*)out);
+  });
 }
 
 extern "C" int sw_scatter2x(int dtype, int N, int H, int W, int C, const void* g, void* out, hipStream_t stream) {
@@ -846,35 +680,21 @@ extern "C" int sw_scatter2x(int dtype, int N, int H, int W, int C, const void* g
   const int OH = (H + 1) / 2, OW = (W + 1) / 2;
   const long n = (long)N * H * W * C;
   if (n <= 0) return 0;
-  {
-    const long es = dtype == SW_BF16 ? 2 : 4;
-    if (((long)C * es) % 16 == 0 && ((((uintptr_t)g | (uintptr_t)out) & 15) == 0) && (dtype == SW_BF16 || dtype == SW_F32)) {
-      const int Cp = (int)((long)C * es / 16);
-      hipLaunchKernelGGL(scatter2_kernel<u32x4>, dim3(grid_for_n((long)N * H * W * Cp)), dim3(256), 0, stream, N, H, W, Cp, OH, OW,
-                         (const u32x4*)g, (u32x4*)out);
-      SW_CHECK_LAUNCH();
-      return 0;
-    }
-  }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(scatter2_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, N, H, W, C, OH, OW,
-                       (const unsigned short*)g, (unsigned short*)out),
-    hipLaunchKernelGGL(scatter2_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, N, H, W, C, OH, OW, (const float*)g,
-                       (float*)out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    constexpr int V = 16 / (int)sizeof(T);
+    if (vec16_ok<T>(C, g, out)) LAUNCH_N(scatter2_kernel<u32x4>, n / V, N, H, W, C / V, OH, OW, (const u32x4*)g, (u32x4*)out);
+    else LAUNCH_N(scatter2_kernel<T>, n, N, H, W, C, OH, OW, (const T*)g, (T*)out);
+  });
 }
 
 extern "C" int sw_add_relu(int dtype, long n, const void* a, const void* b, void* out, int relu, hipStream_t stream) {
   SW_ENTER();
   if (n <= 0) return 0;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(add_relu_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, n, (const unsigned short*)a,
-                       (const unsigned short*)b, (unsigned short*)out, relu),
-    hipLaunchKernelGGL(add_relu_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, n, (const float*)a, (const float*)b,
-                       (float*)out, relu));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    LAUNCH_N(add_relu_kernel<T>, n, n, (const T*)a, (const T*)b, (T*)out, relu);
+  });
 }
 
 extern "C" int sw_upsample2x_add(int dtype, int N, int h, int w, int C, const void* lateral, const void* top, void* out,
@@ -882,49 +702,25 @@ extern "C" int sw_upsample2x_add(int dtype, int N, int h, int w, int C, const vo
   SW_ENTER();
   const long n = (long)N * 4 * h * w * C;
   if (n <= 0) return 0;
-  const int V = dtype == SW_BF16 ? 8 : 4;
-  if ((C % V) == 0 && ((((uintptr_t)lateral | (uintptr_t)top | (uintptr_t)out) & 15) == 0)) {
-    const long nv = n / V;
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(upsample2_add_vec_kernel<unsigned short>, dim3(grid_for_n(nv)), dim3(256), 0, stream, N, h, w, C,
-                         (const unsigned short*)lateral, (const unsigned short*)top, (unsigned short*)out),
-      hipLaunchKernelGGL(upsample2_add_vec_kernel<float>, dim3(grid_for_n(nv)), dim3(256), 0, stream, N, h, w, C, (const float*)lateral,
-                         (const float*)top, (float*)out));
-    SW_CHECK_LAUNCH();
-    return 0;
-  }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(upsample2_add_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, N, h, w, C,
-                       (const unsigned short*)lateral, (const unsigned short*)top, (unsigned short*)out),
-    hipLaunchKernelGGL(upsample2_add_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, N, h, w, C, (const float*)lateral,
-                       (const float*)top, (float*)out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    constexpr int V = 16 / (int)sizeof(T);
+    if (vec16_ok<T>(C, lateral, top, out))
+      LAUNCH_N((upsample2_add_kernel<T, V>), n / V, N, h, w, C, (const T*)lateral, (const T*)top, (T*)out);
+    else LAUNCH_N((upsample2_add_kernel<T, 1>), n, N, h, w, C, (const T*)lateral, (const T*)top, (T*)out);
+  });
 }
 
 extern "C" int sw_downsample2x_sum(int dtype, int N, int h, int w, int C, const void* g, void* out, hipStream_t stream) {
   SW_ENTER();
   const long n = (long)N * h * w * C;
   if (n <= 0) return 0;
-  {
-    const int V = dtype == SW_BF16 ? 8 : 4;
-    if ((C % V) == 0 && ((((uintptr_t)g | (uintptr_t)out) & 15) == 0)) {
-      DISPATCH_T(dtype,
-        hipLaunchKernelGGL(downsample2_sum_vec_kernel<unsigned short>, dim3(grid_for_n(n / V)), dim3(256), 0, stream, N, h, w, C,
-                           (const unsigned short*)g, (unsigned short*)out),
-        hipLaunchKernelGGL(downsample2_sum_vec_kernel<float>, dim3(grid_for_n(n / V)), dim3(256), 0, stream, N, h, w, C, (const float*)g,
-                           (float*)out));
-      SW_CHECK_LAUNCH();
-      return 0;
-    }
-  }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(downsample2_sum_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, N, h, w, C,
-                       (const unsigned short*)g, (unsigned short*)out),
-    hipLaunchKernelGGL(downsample2_sum_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, N, h, w, C, (const float*)g,
-                       (float*)out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    constexpr int V = 16 / (int)sizeof(T);
+    if (vec16_ok<T>(C, g, out)) LAUNCH_N((downsample2_sum_kernel<T, V>), n / V, N, h, w, C, (const T*)g, (T*)out);
+    else LAUNCH_N((downsample2_sum_kernel<T, 1>), n, N, h, w, C, (const T*)g, (T*)out);
+  });
 }
 
 extern "C" int sw_roi_align_fwd(int dtype, int H, int W, int C, int PH, int PW, float spatial_scale, int sampling_ratio,
@@ -933,14 +729,11 @@ extern "C" int sw_roi_align_fwd(int dtype, int H, int W, int C, int PH, int PW, 
   SW_ENTER();
   if (n_sel <= 0) return 0;
   if (ld_out < (long)C * PH * PW) return -5;
-  const long n = (long)n_sel * PH * PW * C;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(roi_align_fwd_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, H, W, C, PH, PW,
-                       spatial_scale, sampling_ratio, (const unsigned short*)feat, rois, sel, n_sel, n_sel_dev, (unsigned short*)out, ld_out),
-    hipLaunchKernelGGL(roi_align_fwd_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, H, W, C, PH, PW, spatial_scale,
-                       sampling_ratio, (const float*)feat, rois, sel, n_sel, n_sel_dev, (float*)out, ld_out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    LAUNCH_N(roi_align_fwd_kernel<T>, (long)n_sel * PH * PW * C, H, W, C, PH, PW, spatial_scale, sampling_ratio, (const T*)feat, rois, sel,
+             n_sel, n_sel_dev, (T*)out, ld_out);
+  });
 }
 
 extern "C" int sw_roi_align_bwd(int dtype, int H, int W, int C, int PH, int PW, float spatial_scale, int sampling_ratio,
@@ -949,14 +742,11 @@ extern "C" int sw_roi_align_bwd(int dtype, int H, int W, int C, int PH, int PW, 
   SW_ENTER();
   if (n_sel <= 0) return 0;
   if (ld < (long)C * PH * PW) return -5;
-  const long n = (long)n_sel * PH * PW * C;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(roi_align_bwd_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, H, W, C, PH, PW,
-                       spatial_scale, sampling_ratio, (const unsigned short*)gout, ld, rois, sel, n_sel, n_sel_dev, dfeat_f32),
-    hipLaunchKernelGGL(roi_align_bwd_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, H, W, C, PH, PW, spatial_scale,
-                       sampling_ratio, (const float*)gout, ld, rois, sel, n_sel, n_sel_dev, dfeat_f32));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    LAUNCH_N((roi_align_bwd_kernel<T, AccF32>), (long)n_sel * PH * PW * C, H, W, C, PH, PW, spatial_scale, sampling_ratio, (const T*)gout,
+             ld, rois, sel, n_sel, n_sel_dev, AccF32::Arg{}, dfeat_f32);
+  });
 }
 
 extern "C" int sw_roi_align_bwd_fx(int dtype, int H, int W, int C, int PH, int PW, float spatial_scale, int sampling_ratio,
@@ -965,26 +755,21 @@ extern "C" int sw_roi_align_bwd_fx(int dtype, int H, int W, int C, int PH, int P
   SW_ENTER();
   if (n_sel <= 0) return 0;
   if (ld < (long)C * PH * PW || !gout_absmax || !acc_i64) return -5;
-  const long n = (long)n_sel * PH * PW * C;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(roi_align_bwd_fx_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, H, W, C, PH, PW,
-                       spatial_scale, sampling_ratio, (const unsigned short*)gout, ld, rois, sel, n_sel, n_sel_dev, gout_absmax,
-                       (unsigned long long*)acc_i64),
-    hipLaunchKernelGGL(roi_align_bwd_fx_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, H, W, C, PH, PW, spatial_scale,
-                       sampling_ratio, (const float*)gout, ld, rois, sel, n_sel, n_sel_dev, gout_absmax, (unsigned long long*)acc_i64));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    LAUNCH_N((roi_align_bwd_kernel<T, AccFx>), (long)n_sel * PH * PW * C, H, W, C, PH, PW, spatial_scale, sampling_ratio, (const T*)gout,
+             ld, rois, sel, n_sel, n_sel_dev, gout_absmax, (unsigned long long*)acc_i64);
+  });
 }
 
 extern "C" int sw_fx_to_float(int out_dtype, long n, const long long* acc_i64, const float* absmax, void* out, hipStream_t stream) {
   SW_ENTER();
   if (n <= 0) return 0;
   if (!acc_i64 || !absmax || !out) return -5;
-  DISPATCH_T(out_dtype,
-    hipLaunchKernelGGL(fx_to_float_kernel<unsigned short>, dim3(grid_for_n(n)), dim3(256), 0, stream, n, acc_i64, absmax, (unsigned short*)out),
-    hipLaunchKernelGGL(fx_to_float_kernel<float>, dim3(grid_for_n(n)), dim3(256), 0, stream, n, acc_i64, absmax, (float*)out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(out_dtype, [&](auto elem) {
+    using T = decltype(elem);
+    LAUNCH_N(fx_to_float_kernel<T>, n, n, acc_i64, absmax, (T*)out);
+  });
 }
 
 extern "C" long sw_rpn_loss_workspace_floats(void) { return 2L * RPN_LOSS_BLOCKS; }
@@ -994,7 +779,7 @@ extern "C" int sw_rpn_loss(long n, long n_anchors, const float* logits, const fl
                            float* losses2, float* dlogits, float* ddeltas, float* workspace, hipStream_t stream) {
   SW_ENTER();
   if (n <= 0 || n_anchors <= 0) return -5;
-  int blocks = grid_for_n(n);
+  int blocks = grid_for(n, GRID_CAP);
   if (blocks > RPN_LOSS_BLOCKS) blocks = RPN_LOSS_BLOCKS;
   hipLaunchKernelGGL(rpn_loss_kernel, dim3(blocks), dim3(256), 0, stream, n, n_anchors, logits, deltas, (const signed char*)labels,
                      anchors, matched_gt_boxes, weights4[0], weights4[1], weights4[2], weights4[3], inv_norm, workspace, dlogits,
@@ -1046,9 +831,7 @@ extern "C" int sw_stage_weights_multi(int dtype, int n, const sw_stage_desc* des
                                       hipStream_t stream) {
   SW_ENTER();
   if (n <= 0 || total_blocks <= 0) return 0;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(stage_weights_multi_kernel<unsigned short>, dim3(total_blocks), dim3(256), 0, stream, n, descs_dev, eps),
-             hipLaunchKernelGGL(stage_weights_multi_kernel<float>, dim3(total_blocks), dim3(256), 0, stream, n, descs_dev, eps));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    hipLaunchKernelGGL(stage_weights_multi_kernel<decltype(elem)>, dim3(total_blocks), dim3(256), 0, stream, n, descs_dev, eps);
+  });
 }

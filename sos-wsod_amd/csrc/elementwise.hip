@@ -6,11 +6,6 @@
 
 namespace {
 
-inline int grid_for(long n, int block = 256) {
-  long g = (n + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-
 // ---------------------------------------------------------------- preprocess (rcnn_multi.py:256-269)
 template <typename T>
 __global__ void preprocess_kernel(int H, int W, int cpad, const uint8_t* __restrict__ img, float m0, float m1, float m2,
@@ -51,10 +46,8 @@ __global__ void maxpool_fwd_kernel(int nimg, int H, int W, int C, int stride, in
                                    T* __restrict__ out) {
   const long total = (long)nimg * OH * OW * C;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); long t = i / C;
-    const int ox = (int)(t % OW); t /= OW;
-    const int oy = (int)(t % OH); const int n = (int)(t / OH);
-    const T* b = in + (((long)n * H + oy * stride) * W + ox * stride) * C + c;
+    const Nhwc o = nhwc_split(i, OH, OW, C);
+    const T* b = in + (((long)o.b * H + o.y * stride) * W + o.x * stride) * C + o.c;
     float m = Elem<T>::load(b);
     m = max_keep_nan(m, Elem<T>::load(b + C));
     m = max_keep_nan(m, Elem<T>::load(b + (long)W * C));
@@ -71,9 +64,8 @@ __global__ void maxpool_bwd_kernel(int nimg, int H, int W, int C, int stride, in
                                    const T* __restrict__ dout, T* __restrict__ din, int relu_mask) {
   const long total = (long)nimg * H * W * C;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C); long t = i / C;
-    const int x = (int)(t % W); t /= W;
-    const int y = (int)(t % H); const int n = (int)(t / H);
+    const Nhwc p = nhwc_split(i, H, W, C);
+    const int c = p.c, x = p.x, y = p.y, n = p.b;
     const float self = Elem<T>::load(in + i);
     float g = 0.f;
     if (!(relu_mask && !(self > 0.f))) {
@@ -803,9 +795,6 @@ __global__ void loss_finalize_kernel(int nl, int V, int B, const float* __restri
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL_BF16, CALL_F32) \
-  if ((dtype) == SW_BF16) { CALL_BF16; } else if ((dtype) == SW_F32) { CALL_F32; } else return -1;
-
 extern "C" int sw_preprocess(int dtype, int H, int W, int cpad, const uint8_t* img, const float* mean3,
                              const float* std3, void* out, hipStream_t stream) {
   SW_ENTER();
@@ -813,13 +802,11 @@ extern "C" int sw_preprocess(int dtype, int H, int W, int cpad, const uint8_t* i
   // configuration constants; they are passed by value through the launch instead of dereferenced on device.
   // => mean3/std3 are HOST pointers (documented exception).
   const long n = (long)H * W;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(preprocess_kernel<unsigned short>, dim3(grid_for(n)), dim3(256), 0, stream, H, W, cpad, img,
-                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (unsigned short*)out),
-    hipLaunchKernelGGL(preprocess_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, H, W, cpad, img,
-                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (float*)out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(preprocess_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, H, W, cpad, img,
+                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (T*)out);
+  });
 }
 
 extern "C" int sw_preprocess_multi(int dtype, int n, int H, int W, int cpad, const uint8_t* const* imgs_chw, const float* mean3,
@@ -835,12 +822,11 @@ extern "C" int sw_preprocess_multi(int dtype, int n, int H, int W, int cpad, con
     for (int i = 0; i < m; ++i) a.img[i] = imgs_chw[base + i];
     void* out = (char*)out_nhwc + (long)base * npix * cpad * es;
     long bx = grid_for(npix); if (bx > 512) bx = 512;
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(preprocess_multi_kernel<unsigned short>, dim3((unsigned)bx, (unsigned)m), dim3(256), 0, stream, H, W, cpad, a,
-                         mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (unsigned short*)out),
-      hipLaunchKernelGGL(preprocess_multi_kernel<float>, dim3((unsigned)bx, (unsigned)m), dim3(256), 0, stream, H, W, cpad, a,
-                         mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (float*)out));
-    SW_CHECK_LAUNCH();
+    if (const int rc = dispatch_elem(dtype, [&](auto elem) {
+      using T = decltype(elem);
+      hipLaunchKernelGGL(preprocess_multi_kernel<T>, dim3((unsigned)bx, (unsigned)m), dim3(256), 0, stream, H, W, cpad, a,
+                         mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (T*)out);
+    })) return rc;
   }
   return 0;
 }
@@ -852,21 +838,17 @@ extern "C" int sw_maxpool2x2_fwd(int dtype, int nimg, int H, int W, int C, int s
   const long n = (long)nimg * OH * OW * C;
   const int vn = dtype == SW_BF16 ? 8 : 4;
   if ((C % vn) == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0) {
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(maxpool_fwd_vec_kernel<unsigned short>, dim3(grid_for(n / vn)), dim3(256), 0, stream, nimg, H, W, C,
-                         stride, OH, OW, (const unsigned short*)in, (unsigned short*)out),
-      hipLaunchKernelGGL(maxpool_fwd_vec_kernel<float>, dim3(grid_for(n / vn)), dim3(256), 0, stream, nimg, H, W, C, stride,
-                         OH, OW, (const float*)in, (float*)out));
-    SW_CHECK_LAUNCH();
-    return 0;
+    return dispatch_elem(dtype, [&](auto elem) {
+      using T = decltype(elem);
+      hipLaunchKernelGGL(maxpool_fwd_vec_kernel<T>, dim3(grid_for(n / vn)), dim3(256), 0, stream, nimg, H, W, C,
+                         stride, OH, OW, (const T*)in, (T*)out);
+    });
   }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(maxpool_fwd_kernel<unsigned short>, dim3(grid_for(n)), dim3(256), 0, stream, nimg, H, W, C, stride,
-                       OH, OW, (const unsigned short*)in, (unsigned short*)out),
-    hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, nimg, H, W, C, stride, OH, OW,
-                       (const float*)in, (float*)out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, nimg, H, W, C, stride,
+                       OH, OW, (const T*)in, (T*)out);
+  });
 }
 
 extern "C" int sw_maxpool2x2_bwd(int dtype, int nimg, int H, int W, int C, int stride, const void* in,
@@ -877,31 +859,25 @@ extern "C" int sw_maxpool2x2_bwd(int dtype, int nimg, int H, int W, int C, int s
   const int vn = dtype == SW_BF16 ? 8 : 4;
   if (stride == 2 && (C % vn) == 0 && (((uintptr_t)in | (uintptr_t)dout | (uintptr_t)din) & 15) == 0) {
     const long nw = (long)nimg * ((H + 1) / 2) * ((W + 1) / 2) * (C / vn);
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(maxpool_bwd_s2_kernel<unsigned short>, dim3(grid_for(nw)), dim3(256), 0, stream, nimg, H, W, C, OH, OW,
-                         (const unsigned short*)in, (const unsigned short*)dout, (unsigned short*)din, relu_mask),
-      hipLaunchKernelGGL(maxpool_bwd_s2_kernel<float>, dim3(grid_for(nw)), dim3(256), 0, stream, nimg, H, W, C, OH, OW,
-                         (const float*)in, (const float*)dout, (float*)din, relu_mask));
-    SW_CHECK_LAUNCH();
-    return 0;
+    return dispatch_elem(dtype, [&](auto elem) {
+      using T = decltype(elem);
+      hipLaunchKernelGGL(maxpool_bwd_s2_kernel<T>, dim3(grid_for(nw)), dim3(256), 0, stream, nimg, H, W, C, OH, OW,
+                         (const T*)in, (const T*)dout, (T*)din, relu_mask);
+    });
   }
   if ((C % vn) == 0 && (((uintptr_t)in | (uintptr_t)dout | (uintptr_t)din) & 15) == 0) {
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(maxpool_bwd_vec_kernel<unsigned short>, dim3(grid_for(n / vn)), dim3(256), 0, stream, nimg, H, W, C,
-                         stride, OH, OW, (const unsigned short*)in, (const unsigned short*)dout, (unsigned short*)din,
-                         relu_mask),
-      hipLaunchKernelGGL(maxpool_bwd_vec_kernel<float>, dim3(grid_for(n / vn)), dim3(256), 0, stream, nimg, H, W, C, stride,
-                         OH, OW, (const float*)in, (const float*)dout, (float*)din, relu_mask));
-    SW_CHECK_LAUNCH();
-    return 0;
+    return dispatch_elem(dtype, [&](auto elem) {
+      using T = decltype(elem);
+      hipLaunchKernelGGL(maxpool_bwd_vec_kernel<T>, dim3(grid_for(n / vn)), dim3(256), 0, stream, nimg, H, W, C,
+                         stride, OH, OW, (const T*)in, (const T*)dout, (T*)din,
+                         relu_mask);
+    });
   }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(maxpool_bwd_kernel<unsigned short>, dim3(grid_for(n)), dim3(256), 0, stream, nimg, H, W, C, stride,
-                       OH, OW, (const unsigned short*)in, (const unsigned short*)dout, (unsigned short*)din, relu_mask),
-    hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, nimg, H, W, C, stride, OH, OW,
-                       (const float*)in, (const float*)dout, (float*)din, relu_mask));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, nimg, H, W, C, stride,
+                       OH, OW, (const T*)in, (const T*)dout, (T*)din, relu_mask);
+  });
 }
 
 extern "C" int sw_conv_weight_prep(int dtype, int mode, int Cout, int Cin, int cin_pad, const float* w, void* wk,
@@ -910,13 +886,11 @@ extern "C" int sw_conv_weight_prep(int dtype, int mode, int Cout, int Cin, int c
   if (mode != 0 && mode != 1) return -3;
   if (mode == 1 && cin_pad != Cin) return -3;
   const long n = mode == 0 ? (long)Cout * 9 * cin_pad : (long)Cin * 9 * Cout;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(conv_weight_prep_kernel<unsigned short>, dim3(grid_for(n)), dim3(256), 0, stream, mode, Cout, Cin,
-                       cin_pad, w, (unsigned short*)wk),
-    hipLaunchKernelGGL(conv_weight_prep_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, mode, Cout, Cin, cin_pad,
-                       w, (float*)wk));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(conv_weight_prep_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, mode, Cout, Cin,
+                       cin_pad, w, (T*)wk);
+  });
 }
 
 extern "C" int sw_convert_2d(int dtype, int rows, int cols, const float* src, long ld_src, void* dst, long ld_dst,
@@ -927,21 +901,17 @@ extern "C" int sw_convert_2d(int dtype, int rows, int cols, const float* src, lo
   const long esz = dtype == SW_BF16 ? 2 : 4;
   if ((cols % 4) == 0 && (ld_src % 4) == 0 && (ld_dst % 4) == 0 && (((uintptr_t)src) & 15) == 0 &&
       (((uintptr_t)dst) & (4 * esz - 1)) == 0) {
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(convert_2d_vec4_kernel<unsigned short>, dim3(grid_for(n / 4)), dim3(256), 0, stream, rows, cols / 4,
-                         src, ld_src, (unsigned short*)dst, ld_dst),
-      hipLaunchKernelGGL(convert_2d_vec4_kernel<float>, dim3(grid_for(n / 4)), dim3(256), 0, stream, rows, cols / 4, src,
-                         ld_src, (float*)dst, ld_dst));
-    SW_CHECK_LAUNCH();
-    return 0;
+    return dispatch_elem(dtype, [&](auto elem) {
+      using T = decltype(elem);
+      hipLaunchKernelGGL(convert_2d_vec4_kernel<T>, dim3(grid_for(n / 4)), dim3(256), 0, stream, rows, cols / 4,
+                         src, ld_src, (T*)dst, ld_dst);
+    });
   }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(convert_2d_kernel<unsigned short>, dim3(grid_for(n)), dim3(256), 0, stream, rows, cols, src, ld_src,
-                       (unsigned short*)dst, ld_dst),
-    hipLaunchKernelGGL(convert_2d_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, rows, cols, src, ld_src,
-                       (float*)dst, ld_dst));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(convert_2d_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, rows, cols, src, ld_src,
+                       (T*)dst, ld_dst);
+  });
 }
 
 // f32 -> three bf16 pieces a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2) (both differences exact in f32), written as
@@ -996,11 +966,10 @@ extern "C" int sw_nchw_to_nhwc(int dtype, int N, int C, int H, int W, int cpad, 
   SW_ENTER();
   const long n = (long)N * H * W * cpad;
   if (n <= 0) return 0;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<unsigned short>, dim3(grid_for(n)), dim3(256), 0, stream, N, C, H, W, cpad, in, (unsigned short*)out),
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, N, C, H, W, cpad, in, (float*)out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, N, C, H, W, cpad, in, (T*)out);
+  });
 }
 
 extern "C" int sw_relu_bwd(int dtype, long n, const void* ref, const void* grad, void* out, hipStream_t stream) {
@@ -1010,18 +979,16 @@ extern "C" int sw_relu_bwd(int dtype, long n, const void* ref, const void* grad,
     const long V = dtype == SW_BF16 ? 8 : 4;
     if ((n % V) == 0 && ((((uintptr_t)ref | (uintptr_t)grad | (uintptr_t)out) & 15) == 0)) {
       const long nv = n / V;
-      DISPATCH_T(dtype,
-        hipLaunchKernelGGL(relu_bwd_vec_kernel<unsigned short>, dim3(grid_for(nv)), dim3(256), 0, stream, nv, (const unsigned short*)ref, (const unsigned short*)grad, (unsigned short*)out),
-        hipLaunchKernelGGL(relu_bwd_vec_kernel<float>, dim3(grid_for(nv)), dim3(256), 0, stream, nv, (const float*)ref, (const float*)grad, (float*)out));
-      SW_CHECK_LAUNCH();
-      return 0;
+      return dispatch_elem(dtype, [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(relu_bwd_vec_kernel<T>, dim3(grid_for(nv)), dim3(256), 0, stream, nv, (const T*)ref, (const T*)grad, (T*)out);
+      });
     }
   }
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(relu_bwd_kernel<unsigned short>, dim3(grid_for(n)), dim3(256), 0, stream, n, (const unsigned short*)ref, (const unsigned short*)grad, (unsigned short*)out),
-    hipLaunchKernelGGL(relu_bwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, n, (const float*)ref, (const float*)grad, (float*)out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(relu_bwd_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, n, (const T*)ref, (const T*)grad, (T*)out);
+  });
 }
 
 extern "C" int sw_scale_cols(int dtype, int M, int N, const float* in, long ld_in, const float* colscale, void* out,
@@ -1029,11 +996,10 @@ extern "C" int sw_scale_cols(int dtype, int M, int N, const float* in, long ld_i
   SW_ENTER();
   const long n = (long)M * N;
   if (n <= 0) return 0;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(scale_cols_kernel<unsigned short>, dim3(grid_for(n)), dim3(256), 0, stream, M, N, in, ld_in, colscale, (unsigned short*)out, ld_out),
-    hipLaunchKernelGGL(scale_cols_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, M, N, in, ld_in, colscale, (float*)out, ld_out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(scale_cols_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, M, N, in, ld_in, colscale, (T*)out, ld_out);
+  });
 }
 
 namespace {
@@ -1071,12 +1037,11 @@ static int colsum_partial(int dtype, int M, int N, const void* X, long ld, float
   int slabs, chunks, rpc;
   colsum_ws_geometry(dtype, M, N, &slabs, &chunks, &rpc);
   dim3 grid(slabs, chunks);
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(colsum_ws_kernel<unsigned short>, grid, dim3(256), 0, stream, M, N, rpc, (const unsigned short*)X, ld,
-                       workspace),
-    hipLaunchKernelGGL(colsum_ws_kernel<float>, grid, dim3(256), 0, stream, M, N, rpc, (const float*)X, ld, workspace));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(colsum_ws_kernel<T>, grid, dim3(256), 0, stream, M, N, rpc, (const T*)X, ld,
+                       workspace);
+  });
 }
 
 extern "C" int sw_colsum_partial_multi(int dtype, int n, const sw_colsum_part_desc* parts, hipStream_t stream) {
@@ -1095,10 +1060,10 @@ extern "C" int sw_colsum_partial_multi(int dtype, int n, const sw_colsum_part_de
       if (!t.add((long)slabs * chunks)) return -6;
     }
     f.n = t.n;
-    DISPATCH_T(dtype,
-      hipLaunchKernelGGL(colsum_ws_multi_kernel<unsigned short>, dim3((unsigned)t.blocks), dim3(256), 0, stream, f),
-      hipLaunchKernelGGL(colsum_ws_multi_kernel<float>, dim3((unsigned)t.blocks), dim3(256), 0, stream, f));
-    SW_CHECK_LAUNCH();
+    if (const int rc = dispatch_elem(dtype, [&](auto elem) {
+      using T = decltype(elem);
+      hipLaunchKernelGGL(colsum_ws_multi_kernel<T>, dim3((unsigned)t.blocks), dim3(256), 0, stream, f);
+    })) return rc;
   }
   return 0;
 }
@@ -1146,11 +1111,10 @@ extern "C" int sw_colsum(int dtype, int M, int N, const void* X, long ld, float*
   if (rpc < 32) rpc = 32;
   chunks = (M + rpc - 1) / rpc;
   dim3 grid(slabs, chunks);
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(colsum_kernel<unsigned short>, grid, dim3(256), 0, stream, M, N, rpc, (const unsigned short*)X, ld, out),
-    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, stream, M, N, rpc, (const float*)X, ld, out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, stream, M, N, rpc, (const T*)X, ld, out);
+  });
 }
 
 extern "C" int sw_fill_zero(void* p, long bytes, hipStream_t stream) {
@@ -1183,13 +1147,11 @@ extern "C" int sw_convert_2d_t(int dtype, int rows, int cols, const float* src, 
   if (rows <= 0 || cols <= 0) return 0;
   if ((rows % 64) || (cols % 64) || (ld_src % 4) || (((uintptr_t)src) & 15)) return -5;
   dim3 grid(cols / 64, rows / 64);
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(sgd_tile_t_kernel<unsigned short>, grid, dim3(256), 0, stream, rows, cols, (float*)src, (const float*)nullptr,
-                       (float*)nullptr, ld_src, 0.f, 0.f, 0, 0.f, 0.f, (unsigned short*)nullptr, 0L, (unsigned short*)dst, ld_dst, (const float*)nullptr),
-    hipLaunchKernelGGL(sgd_tile_t_kernel<float>, grid, dim3(256), 0, stream, rows, cols, (float*)src, (const float*)nullptr,
-                       (float*)nullptr, ld_src, 0.f, 0.f, 0, 0.f, 0.f, (float*)nullptr, 0L, (float*)dst, ld_dst, (const float*)nullptr));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(sgd_tile_t_kernel<T>, grid, dim3(256), 0, stream, rows, cols, (float*)src, (const float*)nullptr,
+                       (float*)nullptr, ld_src, 0.f, 0.f, 0, 0.f, 0.f, (T*)nullptr, 0L, (T*)dst, ld_dst, (const float*)nullptr);
+  });
 }
 
 // the tiled update kernel on a column block of a 2D parameter (gemm.hip: the peeled tail columns of a GEMM with a fused SGD epilogue)
@@ -1270,13 +1232,11 @@ extern "C" int sw_scale_cols_loss(int dtype, int M, int N, int n_valid, const fl
   const long n = (long)M * N;
   if (n <= 0) return 0;
   if (!col_to_loss && g_losses) return -5;
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(scale_cols_loss_kernel<unsigned short>, dim3(grid_for(n)), dim3(256), 0, stream, M, N, n_valid, in, ld_in,
-                       g_losses, g_total, col_to_loss, mul, (unsigned short*)out, ld_out),
-    hipLaunchKernelGGL(scale_cols_loss_kernel<float>, dim3(grid_for(n)), dim3(256), 0, stream, M, N, n_valid, in, ld_in,
-                       g_losses, g_total, col_to_loss, mul, (float*)out, ld_out));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(scale_cols_loss_kernel<T>, dim3(grid_for(n)), dim3(256), 0, stream, M, N, n_valid, in, ld_in,
+                       g_losses, g_total, col_to_loss, mul, (T*)out, ld_out);
+  });
 }
 
 extern "C" int sw_resize_pass_u8(int C, int H, int W, long in_ld, long in_plane, int out_size, int horizontal, const uint8_t* in,
@@ -1338,12 +1298,11 @@ extern "C" int sw_transpose_2d(int dtype, int rows, int cols, const void* src, l
   const int vec = dtype == SW_BF16 ? 8 : 4;
   if ((ld_src % vec) || (ld_dst % vec) || (((uintptr_t)src) & 15) || (((uintptr_t)dst) & 15)) return -5;
   dim3 grid((cols + 63) / 64, (rows + 63) / 64);
-  DISPATCH_T(dtype,
-    hipLaunchKernelGGL(transpose_2d_kernel<unsigned short>, grid, dim3(256), 0, stream, rows, cols, (const unsigned short*)src, ld_src,
-                       (unsigned short*)dst, ld_dst),
-    hipLaunchKernelGGL(transpose_2d_kernel<float>, grid, dim3(256), 0, stream, rows, cols, (const float*)src, ld_src, (float*)dst, ld_dst));
-  SW_CHECK_LAUNCH();
-  return 0;
+  return dispatch_elem(dtype, [&](auto elem) {
+    using T = decltype(elem);
+    hipLaunchKernelGGL(transpose_2d_kernel<T>, grid, dim3(256), 0, stream, rows, cols, (const T*)src, ld_src,
+                       (T*)dst, ld_dst);
+  });
 }
 
 // ---------------------------------------------------------------- Stage-3 (Unbiased Teacher) step pieces

@@ -265,13 +265,8 @@ __global__ __launch_bounds__(256) void refine_loss_kernel(int V, int R, int K, c
   const float gs_cls = (dlogits && grad_scale) ? grad_scale[0] / (float)V / (float)R : 0.f;
   const float gs_box = (dlogits && grad_scale) ? grad_scale[1] / (float)V / (float)R : 0.f;
   // own softmax (predict_probs, fast_rcnn_oicr.py:702-716)
-  float m = -FLT_MAX;
-  for (int j = lane; j < K1; j += 64) m = fmaxf(m, x[j]);
-  m = wave_reduce_max(m);
-  float z = 0.f;
-  for (int j = lane; j < K1; j += 64) z += expf(x[j] - m);
-  z = wave_reduce_sum(z);
-  const float logz = logf(z);
+  const RowCe sm = row_cross_entropy(x, K1, lane);                      // (its m and sum only: this loss takes no offset)
+  const float m = sm.m, z = sm.se, logz = logf(z);
   const int gt = lab_class[r];
   const float w = gt == -1 ? 0.f : lab_weight[r];                       // fast_rcnn_oicr.py:217-218
   int ntgt = 0;
@@ -288,15 +283,8 @@ __global__ __launch_bounds__(256) void refine_loss_kernel(int V, int R, int K, c
       const float* s = B + (long)r * 4;
       const float* t = (TGT0 && v == 0) ? tgt_box0 + ((long)round * R + r) * 4
                                         : B + (long)lab_index[r] * 4;    // target = this view's proposal[gt_index]
-      const float sw_ = s[2] - s[0], sh_ = s[3] - s[1];
-      const float sx = s[0] + 0.5f * sw_, sy = s[1] + 0.5f * sh_;
-      const float tw_ = t[2] - t[0], th_ = t[3] - t[1];
-      const float tx = t[0] + 0.5f * tw_, ty = t[1] + 0.5f * th_;
       float tgt[4];
-      tgt[0] = __fdiv_rn(wx * (tx - sx), sw_);                           // box_regression.py:59-62
-      tgt[1] = __fdiv_rn(wy * (ty - sy), sh_);
-      tgt[2] = ww * logf(__fdiv_rn(tw_, sw_));
-      tgt[3] = wh * logf(__fdiv_rn(th_, sh_));
+      box_deltas(s, t, wx, wy, ww, wh, tgt);
       const float* pd = logits + ((long)pv * R + r) * ld + box_col + 4 * gt;
       float dl[4];
 #pragma unroll
@@ -357,18 +345,8 @@ __global__ __launch_bounds__(256) void focal_loss_kernel(int N, int C, const flo
     if (dlogits) for (int j = lane; j < C; j += 64) dlogits[(long)r * ld_d + j] = nan;
     return;
   }
-  float m = -FLT_MAX;
-  for (int j = lane; j < C; j += 64) m = fmaxf(m, x[j]);
-  m = wave_reduce_max(m);
-  float se = 0.f;
-  for (int j = lane; j < C; j += 64) se += expf(x[j] - m);
-  se = wave_reduce_sum(se);
-  // logsumexp and the target logit are formed relative to c, the multiple of 64 nearest the row maximum: x - c is exact in float32, so
-  // a common offset of the row costs no digits (m + log(se) at logits of 3e4 keeps 2e-3 of absolute precision, 1e-3 of the softmax),
-  // and a row with |m| < 32 has c = 0 and is computed as before, bit for bit
-  const float c = 64.f * rintf(m * 0.015625f);
-  const float lse = (m - c) + logf(se);
-  const float ce = lse - (x[t] - c);
+  const RowCe rc = row_cross_entropy(x, C, lane);
+  const float c = rc.c, lse = rc.lse, ce = rc.ce(x[t]);
   const float p = expf(-ce);
   const float om = fmaxf(1.f - p, 0.f);
   const float w = powf(om, gamma);

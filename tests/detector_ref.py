@@ -185,7 +185,7 @@ def maxpool_ref(x):
 
 # ============================================================================================ subsample2x / scatter2x
 SUB_HW = [(1, 1), (1, 6), (9, 13), (8, 8)]
-SUB_C = [3, 8, 16]
+SUB_C = [3, 8, 12, 16]                     # 12: whole 16-byte pieces in f32, a multiple of 4 but not of 8 elements in bf16
 SUB_CASES = [(H, W, C) for (H, W) in SUB_HW for C in SUB_C]
 
 
