@@ -158,6 +158,100 @@ def rect_mask(hw, rects):
     return m
 
 
+# ------------------------------------------------------------------------------------------------ erased bytes
+_U64 = np.uint64
+
+
+def splitmix64(x):
+    """one splitmix64 output of state x (uint64 scalar or array, arithmetic modulo 2^64)"""
+    with np.errstate(over="ignore"):
+        x = np.asarray(x, _U64) + _U64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> _U64(30))) * _U64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> _U64(27))) * _U64(0x94D049BB133111EB)
+        return x ^ (x >> _U64(31))
+
+
+def erase_uniforms(seed, key, e, c, h, w):
+    """-> (u1, arg) float32 (h, w): the kernel's hash chain over (seed, key, e * 4 + c, dy << 32 | dx), the first uniform in (0, 1]
+    and the cosine argument float32(2 pi) * u2.  The 24-bit integers, `+ 1` and the scaling by 2^-24 are exact in float32; the
+    product with 2 pi is one correctly rounded float32 operation: both are the same bits on every IEEE machine."""
+    dy, dx = np.meshgrid(np.arange(h, dtype=_U64), np.arange(w, dtype=_U64), indexing="ij")
+    s = splitmix64(_U64(int(seed) & 0xFFFFFFFFFFFFFFFF))
+    s = splitmix64(s ^ _U64(int(key) & 0xFFFFFFFFFFFFFFFF))
+    s = splitmix64(s ^ _U64(e * 4 + c))
+    s = splitmix64(s ^ ((dy << _U64(32)) | dx))
+    u1 = ((s >> _U64(40)).astype(f32) + f32(1)) * f32(1.0 / 16777216.0)
+    u2 = ((s >> _U64(16)) & _U64(0xFFFFFF)).astype(f32) * f32(1.0 / 16777216.0)
+    return u1, f32(6.283185307179586) * u2
+
+
+def erase_values(seed, key, e, c, h, w):
+    """-> (v, band) float64 (h, w): v = 255 n at every offset (dy, dx) of erasing e, channel c, where the kernel computes
+    `255.0f * (sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2))` in float32; band bounds |kernel's float - v|.
+
+    u1 and the cosine argument are taken in float32 exactly as the kernel has them (erase_uniforms); log, sqrt and cos are then
+    evaluated in float64, whose own error (2^-52) does not count.  The kernel's float32 chain adds, relative to its result:
+    logf <= 1 ulp, so sqrt(-2 log u1) <= 1/2 ulp from it (the factor -2 is exact) + 1/2 ulp of the correctly rounded sqrtf
+    = 1 ulp; cosf <= 2 ulp; the product of the two and the product with 255 correctly rounded, 1/2 ulp each: 4 ulp in all, and an
+    ulp is at most 2^-23 of the value it belongs to, so the relative error of 255 n is at most 2^-21.  The two library
+    figures (1 ulp, 2 ulp) are the vendor's documented bounds, not this project's measurements, so the band is doubled:
+    band = 2^-20 * max(1, |v|)  (below |v| = 1 the truncation is 0 either way and the floor of 2^-20 only keeps the band from
+    vanishing at v = 0)."""
+    u1, arg = erase_uniforms(seed, key, e, c, h, w)
+    v = 255.0 * (np.sqrt(-2.0 * np.log(u1.astype(f64))) * np.cos(arg.astype(f64)))
+    return v, 2.0 ** -20 * np.maximum(1.0, np.abs(v))
+
+
+def erase_bytes(seed, key, e, c, h, w):
+    """-> (lo, hi) uint8 (h, w): trunc(v - band) & 255 and trunc(v + band) & 255 (truncation toward zero, wrapped modulo 256: torch's
+    CPU float -> uint8).  A sample is decided where they agree; elsewhere the kernel may give either."""
+    v, band = erase_values(seed, key, e, c, h, w)
+    wrap = lambda t: (np.trunc(t).astype(np.int64) & 255).astype(np.uint8)
+    return wrap(v - band), wrap(v + band)
+
+
+def apply_erasings(img, rects, seed, key):
+    """the three erasings in turn on an HWC uint8 image (a later rectangle overwrites an earlier one)
+    -> (out, decided, alt): decided (H, W, 3) bool; where it is False the byte may also be alt"""
+    out, alt = img.copy(), img.copy()
+    decided = np.ones(img.shape, bool)
+    for e, rc in enumerate(rects or ()):
+        if rc is None or rc[2] <= 0:
+            continue
+        t, l, h, w = rc
+        for c in range(3):
+            lo, hi = erase_bytes(seed, key, e, c, h, w)
+            out[t:t + h, l:l + w, c], alt[t:t + h, l:l + w, c], decided[t:t + h, l:l + w, c] = lo, hi, lo == hi
+    return out, decided, alt
+
+
+# ------------------------------------------------------------------------------------------------ blend inputs
+BLEND_FACTORS = (0.0, 0.1, 1.0 / 3.0, 0.6, 0.72, 1.0, 1.31, 1.4, 2.0)
+CONTRAST_DEGENERATES = (0, 1, 127, 128, 254, 255)
+
+
+def contrast_ramp_image(d, rows=300):
+    """(rows, 256, 3) grey image: row 0 the ramp 0..255, every other row the constant d, which puts int(mean(L) + 0.5) at d
+    (the ramp moves the mean by less than 0.43): contrast then blends every x in 0..255 with the degenerate d"""
+    img = np.full((rows, 256, 3), d, np.uint8)
+    img[0] = np.arange(256, dtype=np.uint8)[:, None]
+    assert contrast_mean(img) == d
+    return img
+
+
+def saturation_pairs_image():
+    """a subsample of all 2^24 colours: 586 x 820 pixels whose (lum, channel value) pairs are what saturation blends"""
+    return np.ascontiguousarray(all_colours()[::7, ::5])
+
+
+def blend_fused(deg, img, f):
+    """`blend` as a build with floating-point contraction would compute it: d + f * (x - d) as ONE fused multiply-add, i.e. the exact
+    f * (x - d) + d rounded once to float32 (f a float32, x - d an integer below 2^8: product and sum are exact in float64)"""
+    d = np.asarray(deg).astype(f64)
+    t = (f64(f32(f)) * (img.astype(f64) - d) + d).astype(f32)
+    return np.clip(t, f32(0), f32(255)).astype(np.uint8)
+
+
 def digest(img):
     """(sha256 hex of the bytes, crc32 per row) of an HWC uint8 image: what the fixtures keep of images too large to commit"""
     img = np.ascontiguousarray(img)

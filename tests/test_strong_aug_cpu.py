@@ -57,8 +57,9 @@ def test_hue_shift_equals_pillow(f):
     assert np.array_equal(R.hue(src, f), np.array(M.pil_hue(Image.fromarray(src, "RGB"), f)))
 
 
-# sigma = 2.4495 and 2.45 sit on either side of the l = 1 -> 2 boundary (12 sigma^2 / 3 + 1 = 25)
-@pytest.mark.parametrize("sigma", [0.1, 0.3, 0.45, 0.9, 1.0, 1.37, 1.73, 2.0, 2.4495, 2.45])
+# sigma = 2.4495 and 2.45 sit on either side of the l = 1 -> 2 boundary (12 sigma^2 / 3 + 1 = 25); 2.45, 3.0 and 3.4 give r = 2, the
+# largest radius the kernels accept
+@pytest.mark.parametrize("sigma", [0.1, 0.3, 0.45, 0.9, 1.0, 1.37, 1.73, 2.0, 2.4495, 2.45, 3.0, 3.4])
 def test_gaussian_blur_equals_pillow(sigma):
     M = _pil()
     for h, w, tag in SIZES:
@@ -99,6 +100,68 @@ def test_fixture_generator_reproduces_the_fixture_with_this_pillow():
     for c in cases:
         if "out" in c:
             assert np.array_equal(M.pil_recipe(R.make_image(*c["hw"], c["tag"]), c["recipe"]), c["out"]), c["name"]
+
+
+# ------------------------------------------------------------------------------------------------ erased bytes
+def test_splitmix64_published_vector():
+    assert int(R.splitmix64(0)) == 0xE220A8397B1DCDAF                     # the first output of the published generator seeded 0
+    assert int(R.splitmix64(np.array([0, 0], np.uint64))[1]) == 0xE220A8397B1DCDAF
+
+
+def test_erase_band_holds_a_float32_evaluation_and_few_bytes_are_undecided():
+    """4e6 hashed counters: the formula evaluated in float32 by numpy (another libm than the device's, the same error class)
+    lands inside the band of the float64 value everywhere, so its byte is one of (lo, hi); at most 0.2 % of the counters are
+    undecided (a condition: the GPU tests allow the same share)"""
+    seed, key, e, c, h, w = 2 ** 63 + 5, 12345, 1, 2, 2000, 2000
+    v, band = R.erase_values(seed, key, e, c, h, w)
+    lo, hi = R.erase_bytes(seed, key, e, c, h, w)
+    u1, arg = R.erase_uniforms(seed, key, e, c, h, w)
+    assert u1.dtype == np.float32 and arg.dtype == np.float32 and float(u1.min()) > 0 and float(u1.max()) <= 1
+    v32 = np.float32(255) * (np.sqrt(np.float32(-2) * np.log(u1)) * np.cos(arg))
+    assert v32.dtype == np.float32
+    err = np.abs(v32.astype(np.float64) - v)
+    b32 = (np.trunc(v32).astype(np.int64) & 255).astype(np.uint8)
+    b64 = (np.trunc(v).astype(np.int64) & 255).astype(np.uint8)
+    undecided = float((lo != hi).mean())
+    print(f"erase band: {v.size} counters, {int((b32 != b64).sum())} float32/float64 byte disagreements, largest relative error "
+          f"{float((err / np.maximum(1.0, np.abs(v))).max()):.3g} of {2.0 ** -20:.3g} allowed, undecided share {undecided:.3g}")
+    assert v.size == 4 * 10 ** 6 and (err <= band).all()
+    assert ((b32 == lo) | (b32 == hi)).all()
+    assert ((b64 == lo) | (b64 == hi)).all()
+    assert undecided <= 0.002
+    assert abs(float(v.mean())) < 1.0 and abs(float(v.std()) - 255.0) < 1.0      # 255 n, n ~ N(0, 1): 4 sigma of the mean is 0.51
+
+
+def test_apply_erasings_order_and_mask():
+    img = np.full((20, 30, 3), 128, np.uint8)
+    rects = ((2, 3, 10, 12), (5, 6, 10, 12), None)
+    out, decided, alt = R.apply_erasings(img, rects, 7, 9)
+    lo0, _ = R.erase_bytes(7, 9, 0, 1, 10, 12)
+    lo1, _ = R.erase_bytes(7, 9, 1, 1, 10, 12)
+    assert np.array_equal(out[5:15, 6:18, 1], lo1)                             # the later erasing wins where they overlap
+    assert np.array_equal(out[2:5, 3:15, 1], lo0[:3]) and np.array_equal(out[5:12, 3:6, 1], lo0[3:, :3])
+    m = R.rect_mask((20, 30), rects)
+    assert (out[~m] == 128).all() and decided[~m].all() and np.array_equal(alt[decided], out[decided])
+    assert not np.array_equal(R.erase_bytes(7, 9, 0, 0, 10, 12)[0], R.erase_bytes(7, 9, 0, 0, 12, 10)[0].T)   # (dy, dx) is ordered
+
+
+@pytest.mark.parametrize("op", ["contrast", "saturation"])
+def test_blend_inputs_are_sensitive_to_a_fused_multiply_add(op):
+    """the (x, d, f) triples of tests/test_gpu_strong_aug_edges.py's blend cases: for each op at least one triple gives another byte
+    when d + f * (x - d) is evaluated as one fused multiply-add, so a build with contraction on cannot pass the GPU test"""
+    differing = {}
+    if op == "contrast":
+        for d in R.CONTRAST_DEGENERATES:
+            src = R.contrast_ramp_image(d)
+            for f in R.BLEND_FACTORS:
+                differing[(d, f)] = int((R.blend(np.uint8(d), src, f) != R.blend_fused(np.uint8(d), src, f)).sum())
+    else:
+        src = R.saturation_pairs_image()
+        L = R.lum(src)[..., None]
+        for f in R.BLEND_FACTORS:
+            differing[f] = int((R.blend(L, src, f) != R.blend_fused(L, src, f)).sum())
+    print(op, "bytes that a fused multiply-add changes:", differing)
+    assert sum(differing.values()) >= 1, differing
 
 
 # ------------------------------------------------------------------------------------------------ recipe draws
