@@ -123,11 +123,22 @@ def compute_iou(gt, dt):
     return [[bb_iou(d["bbox"], g["bbox"], bool(g["iscrowd"])) for g in gt] for d in dt]
 
 
-def evaluate_pair(gt, dt, ious, area_range):
+VARIANTS = ("gt_walk", "no_break", "closed_area", "crowd_once")   # deliberately wrong restatements, for sensitivity tests
+
+
+def evaluate_pair(gt, dt, ious, area_range, variant=None):
     """cocoeval.cpp: SortInstancesByDetectionScore, SortInstancesByIgnore, MatchDetectionsToGroundTruth for one area range
-    -> (detection_matches [T][D] ids, detection_ignores [T][D], detection_scores [D], ground_truth_ignores [G])"""
+    -> (detection_matches [T][D] ids, detection_ignores [T][D], detection_scores [D], ground_truth_ignores [G]).
+    variant: one of VARIANTS, a restatement that is wrong on purpose in that one rule."""
+    assert variant is None or variant in VARIANTS, variant
+    if variant == "closed_area":
+        def outside(area):
+            return area <= area_range[0] or area >= area_range[1]
+    else:
+        def outside(area):
+            return area < area_range[0] or area > area_range[1]
     dind = sorted(range(len(dt)), key=lambda j: -dt[j]["score"])[:MAX_DETS[-1]]          # sorted() is stable
-    ignores = [bool(g["ignore"]) or g["area"] < area_range[0] or g["area"] > area_range[1] for g in gt]
+    ignores = [bool(g["ignore"]) or outside(g["area"]) for g in gt]
     gind = sorted(range(len(gt)), key=lambda j: int(ignores[j]))
     gt_ign = [ignores[j] for j in gind]
     T, D, G = len(IOU_THRS), len(dind), len(gind)
@@ -139,24 +150,42 @@ def evaluate_pair(gt, dt, ious, area_range):
             best = min(float(IOU_THRS[t]), 1 - 1e-10)
             m = -1
             for g in range(G):
-                if gtm[t][g] > 0 and not gt[gind[g]]["iscrowd"]:
+                if gtm[t][g] > 0 and (variant == "crowd_once" or not gt[gind[g]]["iscrowd"]):
                     continue
-                if m >= 0 and not gt_ign[m] and gt_ign[g]:
+                if m >= 0 and not gt_ign[m] and gt_ign[g] and variant != "no_break":
                     break
-                if ious[d][gind[g]] >= best:
-                    best = ious[d][gind[g]]
+                o = ious[d][gind[g]]
+                if (o > best) if variant == "gt_walk" else (o >= best):
+                    best = o
                     m = g
             if m >= 0:
                 dtig[t][d] = gt_ign[m]
                 dtm[t][d] = gt[gind[m]]["id"]
                 gtm[t][m] = dt[dind[d]]["id"]
             det = dt[dind[d]]
-            dtig[t][d] = dtig[t][d] or (dtm[t][d] == 0 and (det["area"] < area_range[0] or det["area"] > area_range[1]))
+            dtig[t][d] = dtig[t][d] or (dtm[t][d] == 0 and outside(det["area"]))
     return dtm, dtig, [dt[j]["score"] for j in dind], gt_ign
 
 
-def restated(ds, res, img_ids=None):
-    """-> {"precision" [T, R, K, A, M], "recall" [T, K, A, M], "scores" [T, R, K, A, M], "counts"}"""
+def _pair_record(dt, ev):
+    dind = sorted(range(len(dt)), key=lambda j: -dt[j]["score"])[:MAX_DETS[-1]]
+    return {"ids": [dt[j]["id"] for j in dind], "matched": np.asarray([e[0] for e in ev], dtype=np.int64) > 0,
+            "ignored": np.asarray([e[1] for e in ev], dtype=bool), "gt_ignored": [e[3] for e in ev]}
+
+
+def pair_matches(ds, res, img_ids=None, variant=None):
+    """what evaluate_pair decides for every (image, category) that has detections: {(image id, category id): {"ids" [D] (the
+    detections' loadRes ids, 1-based positions in res, in the pair's score order cut at 100), "matched" / "ignored" bool
+    [A, T, D] (detection_matches > 0, detection_ignores), "gt_ignored" [A][G] in the partition's order}}; restated(pairs={})
+    fills the same dict on its way"""
+    pairs = {}
+    restated(ds, res, img_ids, variant, pairs, accumulate=False)
+    return pairs
+
+
+def restated(ds, res, img_ids=None, variant=None, pairs=None, accumulate=True):
+    """-> {"precision" [T, R, K, A, M], "recall" [T, K, A, M], "scores" [T, R, K, A, M], "counts"}; pairs: a dict that receives
+    pair_matches()'s records"""
     img_list, cat_list, gts, dts = prepare(ds, res, img_ids)
     T, R, K, A, M = len(IOU_THRS), len(REC_THRS), len(cat_list), len(AREA_RNG), len(MAX_DETS)
     precision = -np.ones((T, R, K, A, M))
@@ -168,7 +197,11 @@ def restated(ds, res, img_ids=None):
             gt, dt = gts[i, c], dts[i, c]
             ious = compute_iou(gt, dt)
             for a in range(A):
-                evals[a][n] = evaluate_pair(gt, dt, ious, AREA_RNG[a])
+                evals[a][n] = evaluate_pair(gt, dt, ious, AREA_RNG[a], variant)
+            if pairs is not None and dt:
+                pairs[i, c] = _pair_record(dt, [evals[a][n] for a in range(A)])
+        if not accumulate:
+            continue
         for a in range(A):
             npig = sum(1 for e in evals[a] for ig in e[3] if not ig)
             if npig == 0:

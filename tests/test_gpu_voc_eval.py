@@ -153,7 +153,8 @@ def _fuzz_split(rng, n_img, K, n_det, n_obj=(0, 5), tie_scores=True):
     return objs, dets
 
 
-def _check_fuzz(objs, dets, K):
+def _check_fuzz(objs, dets, K, detail=None):
+    """detail: a list that receives the restatement's per-class intermediates (voc_eval_fixture.restated_detail)"""
     from sos_wsod_amd import evaluation as E
     names = [f"{i:06d}" for i in range(len(objs))]
     recs = {n: [{"name": F.CLASS_NAMES[c], "pose": "Unspecified", "truncated": 0, "difficult": d, "bbox": b} for c, b, d in o]
@@ -161,7 +162,9 @@ def _check_fuzz(objs, dets, K):
     gt = E.GroundTruth(names, recs, F.CLASS_NAMES[:K])
     corloc = all(gt.npos_im[c] > 0 or len(dets[c][0]) == 0 for c in range(K))
     res = E.voc_eval_arrays(gt, E.Detections(dets), corloc=corloc)
-    a07, aar, cl = F.restated(objs, len(objs), dets, K, corloc=corloc)
+    a07, aar, cl, per_class = F.restated_detail(objs, len(objs), dets, K, corloc=corloc)
+    if detail is not None:
+        detail.extend(per_class)
     assert _same(res["ap_07"], a07), np.argwhere(res["ap_07"] != a07)
     assert _same(res["ap_area"], aar), np.argwhere((res["ap_area"] != aar) & ~(np.isnan(aar) & np.isnan(res["ap_area"])))
     if corloc:
@@ -194,8 +197,10 @@ def test_fuzz_large_class_against_restatement():
         if c == 1:
             box = np.where(hit[:, None], np.array([5.0, 5.0, 60.0, 60.0]), box)
         dets.append((img, score, box + rng.integers(-10, 11, (n, 4)) / 10))
-    res = _check_fuzz(objs, dets, K)
+    detail = []
+    res = _check_fuzz(objs, dets, K, detail)
     assert res["ap_area"][0, 0] > 0
+    assert len(detail[0]["terms"][0]) > 8192, len(detail[0]["terms"][0])       # the change points of class 0 at IoU 0.5
 
 
 def test_two_runs_identical_bits(golden_dir, tmp_path):

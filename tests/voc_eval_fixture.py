@@ -129,6 +129,61 @@ def _overlaps(BBGT, bb):
     return inters / uni
 
 
+def voc_ap_terms(rec, prec):
+    """the array voc_ap's area metric hands to np.sum: one term per recall change point of the sentinel-extended curve"""
+    mrec = np.concatenate(([0.0], rec, [1.0]))
+    mpre = np.concatenate(([0.0], prec, [0.0]))
+    for i in range(mpre.size - 1, 0, -1):
+        mpre[i - 1] = np.maximum(mpre[i - 1], mpre[i])
+    i = np.where(mrec[1:] != mrec[:-1])[0]
+    return (mrec[i + 1] - mrec[i]) * mpre[i + 1]
+
+
+def sequential_sum(terms):
+    """the same terms added left to right in f64, which is not the order np.sum takes"""
+    s = 0.0
+    for v in np.asarray(terms, dtype=np.float64).tolist():
+        s += v
+    return s
+
+
+def _pairwise(a, s, n):
+    """numpy's pairwise_sum of the Python floats a[s : s + n]: leaves of at most 128 with eight accumulators"""
+    if n < 8:
+        res = 0.0
+        for k in range(s, s + n):
+            res += a[k]
+        return res
+    if n <= 128:
+        r = a[s:s + 8]
+        i = 8
+        while i < n - n % 8:
+            for k in range(8):
+                r[k] += a[s + i + k]
+            i += 8
+        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+        for k in range(s + i, s + n):
+            res += a[k]
+        return res
+    n2 = n // 2
+    n2 -= n2 % 8
+    return _pairwise(a, s, n2) + _pairwise(a, s + n2, n - n2)
+
+
+def pairwise_sum(terms, chunk=8192):
+    """np.sum of a contiguous f64 array spelled out: the identity, then one pairwise sum per `chunk` elements (the ufunc buffer);
+    chunk=None is one pairwise block over the whole array, which np.sum does not do beyond 8192 elements"""
+    a = np.asarray(terms, dtype=np.float64).tolist()
+    res = 0.0
+    step = len(a) if chunk is None else chunk
+    for s in range(0, len(a), max(step, 1)):
+        res += _pairwise(a, s, min(step, len(a) - s))
+    return res
+
+
+VARIANTS = ("ge", "last_max", "reversed_ties", "sequential_sum")    # deliberately wrong restatements, for sensitivity tests
+
+
 def voc_ap(rec, prec, use_07_metric):
     if use_07_metric:
         ap = 0.0
@@ -136,17 +191,24 @@ def voc_ap(rec, prec, use_07_metric):
             p = 0 if np.sum(rec >= t) == 0 else np.max(prec[rec >= t])
             ap = ap + p / 11.0
         return ap
-    mrec = np.concatenate(([0.0], rec, [1.0]))
-    mpre = np.concatenate(([0.0], prec, [0.0]))
-    for i in range(mpre.size - 1, 0, -1):
-        mpre[i - 1] = np.maximum(mpre[i - 1], mpre[i])
-    i = np.where(mrec[1:] != mrec[:-1])[0]
-    return np.sum((mrec[i + 1] - mrec[i]) * mpre[i + 1])
+    return np.sum(voc_ap_terms(rec, prec))
 
 
-def restated(objs_by_img, n_img, dets_by_class, K, corloc=True):
+def restated(objs_by_img, n_img, dets_by_class, K, corloc=True, variant=None):
     """objs_by_img: [n_img] lists of (class, box [4] int, difficult); every image once in the split.  dets_by_class: [K] of
-    (img [n], score [n], box [n, 4]) in line order.  -> (ap_07, ap_area, corloc) [K, 10] in percent (corloc None if not asked)"""
+    (img [n], score [n], box [n, 4]) in line order.  -> (ap_07, ap_area, corloc) [K, 10] in percent (corloc None if not asked).
+    variant: one of VARIANTS, a restatement that is wrong on purpose in that one rule."""
+    return restated_detail(objs_by_img, n_img, dets_by_class, K, corloc, variant)[:3]
+
+
+def restated_detail(objs_by_img, n_img, dets_by_class, K, corloc=True, variant=None):
+    """restated() and what it went through, per class: -> (ap_07, ap_area, corloc, detail) with detail[c] = {"order" [nd] (line
+    index of each rank), "img" [nd], "ovmax" [nd], "jmax" [nd] (within the image's objects of the class), "tp" / "fp" [10, nd]
+    flags in rank order, "terms" [10] (the arrays voc_ap sums), "holder" {image: rank of the detection CorLoc reads}}"""
+    assert variant is None or variant in VARIANTS, variant
+    above = (lambda o, thr: o >= thr) if variant == "ge" else (lambda o, thr: o > thr)
+    total = sequential_sum if variant == "sequential_sum" else np.sum
+    detail = []
     with np.errstate(all="ignore"):
         out = np.full((3, K, 10), np.nan)
         for c in range(K):
@@ -155,20 +217,27 @@ def restated(objs_by_img, n_img, dets_by_class, K, corloc=True):
             npos = sum(int((~d).sum()) for d in dif)
             npos_im = sum(1 for d in dif if len(d) and (~d).any())
             img, score, box = dets_by_class[c]
-            order = np.argsort(-np.asarray(score, dtype=np.float64), kind="stable")
+            score = np.asarray(score, dtype=np.float64)
+            if variant == "reversed_ties":
+                order = np.lexsort((-np.arange(len(score)), -score))
+            else:
+                order = np.argsort(-score, kind="stable")
             img, box = np.asarray(img)[order], np.asarray(box, dtype=np.float64).reshape(-1, 4)[order]
             nd = len(img)
             ov, jm = np.full(nd, -np.inf), np.zeros(nd, dtype=np.int64)
             for d in range(nd):
                 if gtb[img[d]].size:
                     o = _overlaps(gtb[img[d]], box[d])
-                    ov[d], jm[d] = np.max(o), np.argmax(o)
+                    ov[d], jm[d] = np.max(o), (len(o) - 1 - np.argmax(o[::-1])) if variant == "last_max" else np.argmax(o)
+            det = {"order": order, "img": img, "ovmax": ov, "jmax": jm, "tp": np.zeros((10, nd)), "fp": np.zeros((10, nd)),
+                   "terms": [], "holder": {}}
+            detail.append(det)
             for t, th in enumerate(range(50, 100, 5)):
                 thr = th / 100.0
-                tp, fp = np.zeros(nd), np.zeros(nd)
+                tp, fp = det["tp"][t], det["fp"][t]
                 claimed = [np.zeros(len(d), dtype=bool) for d in dif]
                 for d in range(nd):
-                    if ov[d] > thr:
+                    if above(ov[d], thr):
                         if not dif[img[d]][jm[d]]:
                             if not claimed[img[d]][jm[d]]:
                                 tp[d] = 1.0
@@ -181,7 +250,8 @@ def restated(objs_by_img, n_img, dets_by_class, K, corloc=True):
                 rec = tp / float(npos)
                 prec = tp / np.maximum(tp + fp, np.finfo(np.float64).eps)
                 out[0, c, t] = voc_ap(rec, prec, True) * 100
-                out[1, c, t] = voc_ap(rec, prec, False) * 100
+                det["terms"].append(voc_ap_terms(rec, prec))
+                out[1, c, t] = total(det["terms"][-1]) * 100              # voc_ap(rec, prec, False)
                 if corloc:
                     if nd == 0:
                         out[2, c, t] = 0.0 * 100
@@ -191,6 +261,7 @@ def restated(objs_by_img, n_img, dets_by_class, K, corloc=True):
                         if img[d] in seen or not (~dif[img[d]]).any():
                             continue
                         seen.add(img[d])
-                        hits += ov[d] > thr
+                        det["holder"][int(img[d])] = d
+                        hits += above(ov[d], thr)
                     out[2, c, t] = 1.0 * hits / npos_im * 100
-    return out[0], out[1], (out[2] if corloc else None)
+    return out[0], out[1], (out[2] if corloc else None), detail
