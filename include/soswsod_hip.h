@@ -802,6 +802,43 @@ int sw_proposal_recall(int n_img, const int64_t* prop_off, const double* prop_bo
                        int n_cut, const int32_t* cuts, int n_thr, const double* thr, double* ovmax, int32_t* jmax,
                        long long* cnt_yes, sw_stream_t stream);
 
+/* Box-proposal AR of one split for every (limit, area range) at once (replaces the per-image loop of _evaluate_box_proposals,
+ * detectron2/detectron2/evaluation/coco_evaluation.py:482-514, with pairwise_iou of structures/boxes.py:322-368, and the eight
+ * passes of _eval_box_proposals :286-290).  CSR over images: image i owns rows [prop_off[i], prop_off[i + 1]) of prop_box
+ * [n_prop][4] f32 [x1, y1, x2, y2] (16-byte aligned), already ranked by descending objectness, and rows [gt_off[i],
+ * gt_off[i + 1]) of its non-crowd ground truth in file order: gt_box [n_gt][4] f32 (16-byte aligned) and gt_area [n_gt] f32
+ * (the annotation's own area).  area_rng [n_area][2] f32, limits [n_lim] i32 (0: no limit) and thr [n_thr] f32 are HOST arrays.
+ * Item (l, a, i) is limit l and area range a of image i: its valid boxes are those with area_rng[a][0] <= gt_area <=
+ * area_rng[a][1], G' of them, its proposals the first P' = min(limits[l] or all, n_i).  An image without proposals or without
+ * ground truth has no items (:479).  Item (l, a, i) owns elements [item_off[(l * n_area + a) * n_img + i], item_off[.. + 1]) of
+ * the three outputs (item_off [n_item_off = n_lim * n_area * n_img + 1] i64, device memory, G' elements per item and 0 for an
+ * image without items): element r holds what round r of the greedy matching took — the pair that is best under (largest IoU,
+ * smallest box index, smallest proposal index) among pairs whose proposal and box are both unused — as overlap [n_out] f32 (its
+ * IoU), match_gt [n_out] i32 (the box's index among the item's valid boxes) and match_box [n_out] i32 (the proposal's rank);
+ * min(P', G') rounds run, the elements behind them hold 0, -1, -1.  cnt_yes [n_lim][n_area][n_thr] i64 (8-byte aligned; zeroed
+ * here) counts the elements with overlap >= thr[t].  Every IoU is the reference's float32 arithmetic in its order, so every value
+ * is bit-identical to the reference's, and so are two launches.
+ * An item of P' <= SW_BOXAR_LDS_BOXES and G' <= SW_BOXAR_LDS_GT runs in LDS.  Any other needs the workspace (16-byte aligned,
+ * sw_box_proposal_ar_workspace_bytes(n_img, ws_boxes, ws_props) bytes for items of up to ws_boxes valid boxes and ws_props
+ * proposals; 0 bytes, and NULL is allowed, when every item fits LDS).
+ * Returns -1 NULL host array, -4 alignment, -5 negative count, -6 n_area / n_lim / n_thr outside 1..SW_BOXAR_MAX_*, a negative
+ * limit or n_item_off of another split, -7 ws_bytes too small; nothing is written then.  status [1] i32 (device; zeroed here) is
+ * 0 after a clean launch, else the last SW_BOXAR_* refusal: such an image or item is skipped, never written. */
+#define SW_BOXAR_MAX_AREAS 8
+#define SW_BOXAR_MAX_LIMITS 8
+#define SW_BOXAR_MAX_THRESHOLDS 16
+#define SW_BOXAR_LDS_BOXES 1024 /* ranked proposals staged per image */
+#define SW_BOXAR_LDS_GT 128     /* valid boxes whose state a wave keeps in LDS */
+#define SW_BOXAR_BAD_OFFSETS 1  /* prop_off / gt_off decrease or leave [0, n_prop] / [0, n_gt] */
+#define SW_BOXAR_BAD_LAYOUT 2   /* an item's region is not G' long or leaves [0, n_out] */
+#define SW_BOXAR_WORKSPACE 3    /* an item needs more than ws_boxes / ws_props (or there is no workspace) */
+long long sw_box_proposal_ar_workspace_bytes(int n_img, long long max_boxes, long long max_props);
+int sw_box_proposal_ar(int n_img, const int64_t* prop_off, const float* prop_box, long long n_prop, const int64_t* gt_off,
+                       const float* gt_box, const float* gt_area, long long n_gt, int n_area, const float* area_rng, int n_lim,
+                       const int32_t* limits, int n_thr, const float* thr, const int64_t* item_off, long long n_item_off,
+                       long long n_out, float* overlap, int32_t* match_gt, int32_t* match_box, long long* cnt_yes, void* workspace,
+                       long long ws_bytes, long long ws_boxes, long long ws_props, int32_t* status, sw_stream_t stream);
+
 /* Stage-3 strong augmentation of a planar u8 [3][H][W] image, every pixel operation bit-identical to Pillow's (replaces
  * build_strong_augmentation, unbias/ubteacher/data/detection_utils.py:9-46, applied by DatasetMapperTwoCropSeparate.__call__,
  * unbias/ubteacher/data/dataset_mapper.py:141-149; the blur is unbias/ubteacher/data/transforms/augmentation_impl.py GaussianBlur):

@@ -284,6 +284,11 @@ SIGNATURES = {
     # ---- proposal recall (csrc/proposal_recall.hip)
     "sw_proposal_recall": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
+    # ---- box-proposal AR (csrc/proposal_ar.hip)
+    "sw_box_proposal_ar_workspace_bytes": (c_longlong, [c_int, c_longlong, c_longlong]),
+    "sw_box_proposal_ar": (c_int, [c_int, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_int, _F4, c_int,
+                                   ctypes.POINTER(c_int32), c_int, _F4, c_void_p, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_longlong, c_longlong, c_longlong, c_void_p, c_void_p]),
     # ---- JPEG reader (csrc/jpeg.hip); the first five are host code
     "sw_jpeg_probe": (c_int, [c_void_p, c_long, ctypes.POINTER(JpegInfo)]),
     "sw_jpeg_entropy_decode": (c_int, [c_void_p, c_long, ctypes.POINTER(JpegInfo), c_void_p, c_void_p]),

@@ -553,13 +553,16 @@ class COCOEvaluator:
     AP-<name>...}} in percent, NaN where COCOeval has -1.  No predictions returns {}; predictions without any instance give the
     all-NaN dict.  `eval` holds the accumulated arrays, `stats` COCOeval's twelve numbers.  With save_detection_result the
     gathered predictions are written to save_path.format(name) first (Stage 2's `pgf_coco` reads that file); output_dir
-    receives coco_instances_results.json.  Outputs with "proposals", masks or keypoints are refused: box-proposal AR, segm and
-    keypoints are out of scope (so is LVIS, for which there is no evaluator here).  `set_predictions` takes the records of an
+    receives coco_instances_results.json.  Outputs with masks or keypoints are refused: segm and keypoints are out of scope (so
+    is LVIS, for which there is no evaluator here).  Outputs with "proposals" are refused too unless box_proposals=True: then
+    `process` keeps them (moved to the CPU, coco_evaluation.py:141-142) and `evaluate` writes the reference's box_proposals.pkl
+    into output_dir and adds {"box_proposals": {AR@100, ARs@100, ARm@100, ARl@100, AR@1000, ...}} (box_proposals.py; one launch),
+    beside "bbox" when instances were given too.  `set_predictions` takes the records of an
     earlier run (the save_detection_result file) in place of `process`.  Kept from the reference: an annotation whose id is 0 can never be a true positive
     (cocoeval.cpp tests the matched id > 0), though it does take its detection."""
 
     def __init__(self, json_file, thing_classes=None, output_dir=None, save_detection_result=False, save_path=None,
-                 name="coco"):
+                 name="coco", box_proposals=False):
         if save_detection_result and not save_path:
             raise ValueError("save_detection_result needs a save_path")
         self.json_file = json_file
@@ -568,6 +571,7 @@ class COCOEvaluator:
         self.save_detection_result = save_detection_result
         self.save_path = save_path
         self._thing_classes = thing_classes
+        self.box_proposals = bool(box_proposals)
         self._gt = None
         self._predictions = []
         self.eval = self.stats = None
@@ -586,11 +590,14 @@ class COCOEvaluator:
 
     def process(self, inputs, outputs):
         for inp, out in zip(inputs, outputs):
-            if "proposals" in out:
-                raise ValueError("box-proposal AR is out of scope: COCOEvaluator takes outputs with 'instances' only")
+            if "proposals" in out and not self.box_proposals:
+                raise ValueError("box-proposal AR is out of scope: COCOEvaluator takes outputs with 'instances' only "
+                                 "(COCOEvaluator(..., box_proposals=True) evaluates proposals)")
             prediction = {"image_id": inp["image_id"]}
             if "instances" in out:
                 prediction["instances"] = instances_to_coco_json(out["instances"], inp["image_id"])
+            if "proposals" in out:
+                prediction["proposals"] = out["proposals"].to("cpu")
             self._predictions.append(prediction)
 
     def evaluate(self, img_ids=None):
@@ -599,11 +606,26 @@ class COCOEvaluator:
             return {}
         if self.save_detection_result:
             with open(self.save_path.format(self.dataset_name), "w") as f:
-                json.dump(predictions, f)
+                json.dump([{k: v for k, v in x.items() if k != "proposals"} for x in predictions], f)
         if len(predictions) == 0:
             return {}
+        results = OrderedDict()
+        if "proposals" in predictions[0]:                          # coco_evaluation.py:175-176, before the instances
+            results["box_proposals"] = self._eval_box_proposals(predictions)
         if "instances" not in predictions[0]:
-            return OrderedDict()
+            return results
+        results["bbox"] = self._eval_instances(predictions, img_ids)
+        return results
+
+    def _eval_box_proposals(self, predictions):
+        """coco_evaluation.py:255-292: box_proposals.pkl into output_dir, then the eight ARs"""
+        from .box_proposals import box_proposal_metrics, write_box_proposals
+        if self.output_dir:
+            os.makedirs(self.output_dir, exist_ok=True)
+            write_box_proposals(predictions, os.path.join(self.output_dir, "box_proposals.pkl"))
+        return box_proposal_metrics(predictions, self.ground_truth())
+
+    def _eval_instances(self, predictions, img_ids):
         gt = self.ground_truth()
         reverse = {v: k for k, v in gt.thing_dataset_id_to_contiguous_id.items()}
         coco_results = []
@@ -622,7 +644,7 @@ class COCOEvaluator:
         else:
             self.eval = coco_eval_arrays(gt, COCODetections.from_results(coco_results, gt), img_ids=img_ids)
             self.stats = coco_summarize(self.eval)
-        return OrderedDict(bbox=derive_coco_results(self.eval, self.stats, names))
+        return derive_coco_results(self.eval, self.stats, names)
 
 
 def evaluate_coco_results(results, json_file, img_ids=None):
@@ -655,15 +677,30 @@ def inference_on_dataset(model, data_loader, evaluator):
 def parse_args(argv=None):
     p = argparse.ArgumentParser("python -m sos_wsod_amd.evaluation",
                                 description="VOC mAP and CorLoc of a detection file (VOCDetectionWriter.dump JSON), or with "
-                                            "--coco-json the COCO bbox AP of a coco_instances_results.json.")
+                                            "--coco-json the COCO bbox AP of a coco_instances_results.json; with --proposals "
+                                            "the box-proposal AR of a proposal pickle against either ground truth.")
     p.add_argument("--voc-root", default=None, help="dataset directory holding Annotations/ and ImageSets/Main/")
     p.add_argument("--split", default="test")
     p.add_argument("--year", type=int, default=2007, choices=(2007, 2012))
     p.add_argument("--coco-json", default=None, help="COCO annotation file: evaluate --detections as a COCO result list instead")
     p.add_argument("--detections", default=None, help="JSON list of {image_id, category_id (1-based), score, bbox}; with "
                                                       "--coco-json: {image_id, category_id (dataset id), bbox XYWH, score}")
+    p.add_argument("--proposals", default=None, help="a proposal pickle (box_proposals.pkl, or a converted MCG / Selective Search "
+                                                     "file): print AR@100 ... ARl@1000 instead; takes no --detections")
     p.add_argument("--out", default=None, help="also write the metrics and per-class arrays here as JSON")
     args = p.parse_args(argv)
+    if args.proposals is not None:
+        if args.detections is not None:
+            p.error("--proposals and --detections exclude each other")
+        if (args.voc_root is None) == (args.coco_json is None):
+            p.error("--proposals needs one of --coco-json and --voc-root")
+        paths = [(args.proposals, "--proposals")]
+        paths.append((args.coco_json, "--coco-json") if args.coco_json is not None else
+                     (os.path.join(args.voc_root, "ImageSets", "Main", args.split + ".txt"), "--voc-root/--split image set"))
+        for path, what in paths:
+            if not os.path.isfile(path):
+                p.error(f"{what}: no file {path}")
+        return args
     # --voc-root is required unless --coco-json is given, --detections always: argparse's own message for what is missing
     missing = [flag for flag, v in (("--voc-root", args.voc_root if args.coco_json is None else ""), ("--detections", args.detections))
                if v is None]
@@ -693,8 +730,23 @@ def evaluate_records(records, dirname, split, year, class_names=VOC_CLASS_NAMES)
     return summarize(ap, res["corloc"]), ap, res["corloc"]
 
 
+def evaluate_proposal_file(path, json_file=None, voc_root=None, split="test"):
+    """AR@100 ... ARl@1000 of a proposal pickle against a COCO annotation file, or against a VOC split as convert_to_coco_json
+    would describe it"""
+    from .box_proposals import box_proposal_metrics, predictions_from_file, voc_ground_truth
+    gt = COCOGroundTruth.load(json_file) if json_file is not None else voc_ground_truth(voc_root, split)
+    return box_proposal_metrics(predictions_from_file(path), gt)
+
+
 def main(argv=None):
     args = parse_args(argv)
+    if args.proposals is not None:
+        result = OrderedDict(box_proposals=evaluate_proposal_file(args.proposals, args.coco_json, args.voc_root, args.split))
+        print(json.dumps(result))
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(result, f)
+        return result
     with open(args.detections) as f:
         records = json.load(f)
     if args.coco_json is not None:

@@ -1887,3 +1887,70 @@ class GeneralizedRCNN(TwoStagePseudoLabGeneralizedRCNN):
         if not self.training:
             return self.inference(batched_inputs)
         return super().forward(batched_inputs, branch="supervised")[0]
+
+
+@META_ARCH_REGISTRY.register()
+class ProposalNetwork(TwoStagePseudoLabGeneralizedRCNN):
+    """detectron2/detectron2/modeling/meta_arch/rcnn.py:249-329 — the detector's backbone, preprocessing and proposal generator
+    without ROI heads (MODEL.META_ARCHITECTURE: ProposalNetwork): the state-dict names are the reference's `backbone.*` and
+    `proposal_generator.*` (with the `pixel_mean` / `pixel_std` buffers, not saved there either).  In training
+    `forward(batched_inputs)` returns the two RPN losses; in eval mode [{"proposals": Instances(proposal_boxes,
+    objectness_logits)}] after `detector_postprocess` to each input's "height" / "width".  The modules and the path are the
+    detector's own, so with the same weights the proposals are the ones its `inference` hands to the ROI heads.  The ROI-head keys
+    of a detector config are read and checked as the detector does, and otherwise unused."""
+
+    PROPOSAL_GENERATOR_NAMES = ("RPN", "PseudoLabRPN")
+
+    def __init__(self, cfg=None, *, compute_dtype=torch.float32, freeze_at=2, sampler=None, pixel_mean=(103.530, 116.280, 123.675),
+                 pixel_std=(1.0, 1.0, 1.0), stride_in_1x1=True, fpn_norm="", rpn=None):
+        """rpn: keyword arguments of PseudoLabRPN (pre_nms_topk, post_nms_topk, nms_thresh, ...) when there is no config"""
+        nn.Module.__init__(self)
+        rpn_kw = dict(rpn or {})
+        if cfg is not None:
+            M = cfg.MODEL
+            assert M.BACKBONE.get("NAME", "build_resnet_fpn_backbone") == "build_resnet_fpn_backbone"
+            assert M.get("PROPOSAL_GENERATOR", {}).get("NAME", "RPN") in self.PROPOSAL_GENERATOR_NAMES
+            assert M.get("RPN", {}).get("LOSS", "CrossEntropy") == "CrossEntropy"
+            freeze_at = M.BACKBONE.get("FREEZE_AT", 2)
+            pixel_mean, pixel_std = M.PIXEL_MEAN, M.PIXEL_STD
+            compute_dtype = torch.bfloat16 if M.get("AMD", {}).get("COMPUTE_DTYPE", "fp32") == "bf16" else torch.float32
+            sampler = Sampler(int(cfg.get("SEED", 0)) if int(cfg.get("SEED", 0)) >= 0 else 0)
+            rpn_kw = dict(self._cfg_kwargs(M, cfg.get("TEST", {}))[0], **_loss_kwargs(M)[0])
+            stride_in_1x1, fpn_norm, _ = self._arch_kwargs(M)
+        sampler = sampler if sampler is not None else Sampler()
+        self.backbone = FPN(ResNet(freeze_at, stride_in_1x1), fpn_norm)
+        self.proposal_generator = PseudoLabRPN(sampler, **rpn_kw)
+        self.register_buffer("pixel_mean", torch.tensor(pixel_mean).view(-1, 1, 1), False)
+        self.register_buffer("pixel_std", torch.tensor(pixel_std).view(-1, 1, 1), False)
+        self.compute_dtype = compute_dtype
+        self.sampler = sampler
+        self.graph_nograd_backbone = False
+
+    def load_detector_state_dict(self, state_dict):
+        """load a detector's checkpoint by name: its `backbone.*` and `proposal_generator.*` entries; `roi_heads.*` is ignored,
+        anything else that does not fit is an error"""
+        return self.load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("roi_heads.")}, strict=True)
+
+    def forward(self, batched_inputs):
+        if not self.training:
+            return self.inference(batched_inputs)
+        self.refresh_staged_weights()
+        x4, sizes = self.preprocess_image(batched_inputs)
+        gt = [x["instances"] for x in batched_inputs] if "instances" in batched_inputs[0] else None
+        _, losses = self.proposal_generator(sizes, self._features(x4), gt)
+        return losses
+
+    def image_losses(self, batched_inputs):
+        raise NotImplementedError("ProposalNetwork has no ROI heads: image_losses scores the four losses of a detector")
+
+    @torch.no_grad()
+    def inference(self, batched_inputs, do_postprocess=True):
+        """rcnn.py:301-329; do_postprocess=False returns the raw list[Instances] in network-input coordinates"""
+        from .inference import detector_postprocess
+        self.refresh_staged_weights()
+        x4, sizes = self.preprocess_image(batched_inputs)
+        proposals, _ = self.proposal_generator(sizes, self._features(x4), None, compute_loss=False)
+        if not do_postprocess:
+            return proposals
+        return [{"proposals": detector_postprocess(p, inp.get("height", s[0]), inp.get("width", s[1]))}
+                for p, inp, s in zip(proposals, batched_inputs, sizes)]

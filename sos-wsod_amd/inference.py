@@ -96,8 +96,8 @@ def oicr_view_scores(heads, feat_nhwc, proposals):
 
 
 def detector_postprocess(results, output_height, output_width):
-    """modeling/postprocessing.py:9-44 (boxes only): scale the detections from the network's input resolution to the
-    requested output resolution, clip, drop empty boxes."""
+    """modeling/postprocessing.py:9-44 (boxes only): scale the detections (`pred_boxes`) or, for a proposal network's output, the
+    proposals (`proposal_boxes`) from the network's input resolution to the requested output resolution, clip, drop empty boxes."""
     from .structures import Instances
     scale_x, scale_y = output_width / results.image_size[1], output_height / results.image_size[0]
     out = Instances((int(output_height), int(output_width)), **results.get_fields())
@@ -106,6 +106,12 @@ def detector_postprocess(results, output_height, output_width):
         boxes.scale(scale_x, scale_y)
         boxes.clip(out.image_size)
         out.pred_boxes = boxes
+        out = out[boxes.nonempty()]
+    elif out.has("proposal_boxes"):
+        boxes = out.proposal_boxes.clone()
+        boxes.scale(scale_x, scale_y)
+        boxes.clip(out.image_size)
+        out.proposal_boxes = boxes
         out = out[boxes.nonempty()]
     return out
 

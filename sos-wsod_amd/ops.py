@@ -1607,6 +1607,74 @@ def proposal_recall(prop_off, prop_box, gt_off, gt_box, cuts, thr, ovmax=None, j
     return ovmax, jmax, cnt_yes
 
 
+BOXAR_MAX_AREAS, BOXAR_MAX_LIMITS, BOXAR_MAX_THRESHOLDS = 8, 8, 16      # SW_BOXAR_MAX_AREAS / _MAX_LIMITS / _MAX_THRESHOLDS
+BOXAR_LDS_BOXES, BOXAR_LDS_GT = 1024, 128                               # SW_BOXAR_LDS_BOXES / SW_BOXAR_LDS_GT
+BOXAR_STATUS = {1: "the image offsets decrease or leave their arrays", 2: "item_off is not the layout of this split",
+                3: "an item needs more workspace than was given"}       # SW_BOXAR_BAD_OFFSETS / _BAD_LAYOUT / _WORKSPACE
+
+
+def box_proposal_ar(prop_off, prop_box, gt_off, gt_box, gt_area, area_rng, limits, thr, item_off, overlap=None, match_gt=None,
+                    match_box=None, max_boxes=None, max_props=None, check_offsets=True):
+    """One-to-one greedy coverage of every image's ground truth by its ranked proposals, for every (limit, area range) at once, and
+    the boxes covered at every threshold (sw_box_proposal_ar; the layout is in include/soswsod_hip.h).  On the GPU: prop_off /
+    gt_off [n_img + 1] i64 (CSR over images), prop_box [P, 4] f32 xyxy in rank order, gt_box [G, 4] f32, gt_area [G] f32,
+    item_off [L * A * n_img + 1] i64.  On the host (sequences): area_rng [A <= 8][2], limits [L <= 8] (0: no limit), thr [T <= 16].
+    overlap f32 / match_gt i32 / match_box i32 [>= item_off[-1]] may be passed in (tests fill them with sentinels; only the
+    elements of items are written).  max_boxes / max_props: the largest ground-truth count of an image and the largest number of
+    proposals an item reads, which size the workspace; read from the offsets when not given.  check_offsets: refuse offsets that
+    decrease or leave their arrays with ValueError before the launch (one device-to-host copy; the kernel skips such an image and
+    reports it in status either way).
+    -> (overlap, match_gt, match_box, cnt_yes [L, A, T] i64, status [1] i32) on the GPU; status is 0 after a clean launch, else a
+    key of BOXAR_STATUS."""
+    _need_gpu(prop_off, prop_box, gt_off, gt_box, gt_area, item_off, overlap, match_gt, match_box)
+    n_img, P, G = prop_off.numel() - 1, prop_box.shape[0], gt_box.shape[0]
+    area_rng = [[float(lo), float(hi)] for lo, hi in area_rng]
+    limits = [int(v) for v in limits]
+    thr = [float(t) for t in thr]
+    A, L, T = len(area_rng), len(limits), len(thr)
+    assert prop_off.dtype == torch.int64 and gt_off.dtype == torch.int64 and item_off.dtype == torch.int64
+    assert prop_box.dtype == torch.float32 and gt_box.dtype == torch.float32 and gt_area.dtype == torch.float32
+    assert n_img >= 0 and prop_off.shape == (n_img + 1,) and gt_off.shape == (n_img + 1,) and item_off.dim() == 1
+    assert prop_box.shape == (P, 4) and gt_box.shape == (G, 4) and gt_area.shape == (G,)
+    for t in (prop_off, prop_box, gt_off, gt_box, gt_area, item_off):
+        assert t.is_contiguous()
+    dev = prop_box.device
+    assert item_off.numel() >= 1
+    big_p = big_g = 0
+    if n_img > 0 and (check_offsets or max_boxes is None or max_props is None):          # one device-to-host copy
+        dp, dg = prop_off.diff(), gt_off.diff()
+        di_min = item_off.diff().min() if item_off.numel() > 1 else item_off.new_zeros(())
+        v = torch.stack([dp.min(), dg.min(), di_min, prop_off[0], gt_off[0], item_off[0], prop_off[-1], gt_off[-1], dp.max(),
+                         dg.max()]).tolist()
+        if check_offsets and (min(v[:3]) < 0 or any(v[3:6]) or v[6] > P or v[7] > G):
+            raise ValueError("box_proposal_ar: offsets must start at 0, never decrease and end inside their arrays")
+        big_p, big_g = int(v[8]), int(v[9])
+    if max_boxes is None:
+        max_boxes = big_g
+    if max_props is None:
+        max_props = big_p if (not limits or min(limits) <= 0) else min(big_p, max(limits))
+    if overlap is None:
+        overlap = torch.empty(int(item_off[-1].item()), device=dev, dtype=torch.float32)
+    if match_gt is None:
+        match_gt = torch.empty(overlap.numel(), device=dev, dtype=torch.int32)
+    if match_box is None:
+        match_box = torch.empty(overlap.numel(), device=dev, dtype=torch.int32)
+    assert overlap.dtype == torch.float32 and match_gt.dtype == torch.int32 and match_box.dtype == torch.int32
+    assert overlap.dim() == 1 and match_gt.shape == overlap.shape and match_box.shape == overlap.shape
+    assert overlap.is_contiguous() and match_gt.is_contiguous() and match_box.is_contiguous()
+    cnt_yes = torch.empty(max(L, 1), max(A, 1), max(T, 1), device=dev, dtype=torch.int64)
+    status = torch.empty(1, device=dev, dtype=torch.int32)
+    nbytes = lib.sw_box_proposal_ar_workspace_bytes(n_img, int(max_boxes), int(max_props))
+    assert nbytes >= 0, "sw_box_proposal_ar_workspace_bytes"
+    ws, ws_p = _workspace256(nbytes, dev) if nbytes else (None, None)
+    check(lib.sw_box_proposal_ar(n_img, _p(prop_off), _p(prop_box), P, _p(gt_off), _p(gt_box), _p(gt_area), G, A,
+                                 _floats([v for r in area_rng for v in r], max(2 * A, 1)), L,
+                                 (ctypes.c_int32 * max(L, 1))(*limits), T, _floats(thr, max(T, 1)), _p(item_off), item_off.numel(),
+                                 overlap.numel(), _p(overlap), _p(match_gt), _p(match_box), _p(cnt_yes), ws_p, nbytes, int(max_boxes),
+                                 int(max_props), _p(status), _stream()), "sw_box_proposal_ar")
+    return overlap, match_gt, match_box, cnt_yes, status
+
+
 # ================================================================================================ JPEG reader (csrc/jpeg.hip)
 def jpeg_error(code):
     """the host code's reason for a probe / entropy-decode return code"""

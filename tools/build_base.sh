@@ -4,7 +4,7 @@
 #   tools/build_base.sh [REV] [SRC ...]     (SRC: only these sources come from REV, the others from the last regular build)
 set -e
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"; C="$ROOT/sos-wsod_amd/csrc"; REV="${1:-HEAD}"; shift || true
-ALL="gemm conv_direct conv_wgrad_direct roipool elementwise heads detector proposals pseudo_labels evaluation augment proposal_recall conv_col jpeg"       # as in csrc/build.sh
+ALL="gemm conv_direct conv_wgrad_direct roipool elementwise heads detector proposals pseudo_labels evaluation augment proposal_recall proposal_ar conv_col jpeg"       # as in csrc/build.sh
 SRCS="${@:-$ALL}"
 T="$(mktemp -d)"; mkdir -p "$T/inc"
 git -C "$ROOT" show "$REV:sos-wsod_amd/csrc/common.h" > "$T/common.h"
