@@ -1,5 +1,8 @@
 // Shared device helpers for the gfx950 (MI355X / CDNA4) kernels of the OICR+ hot path.
 // wave = 64 lanes everywhere in this tree.
+// In order: bf16 / NHWC / dropout / SGD / batched-launch helpers, element and 16-byte access, wave and workgroup reductions, then the
+// labelled sections: index arithmetic (workgroup scan, sort keys, bitonic sort), float32 box arithmetic (area, IoU, clip, decode),
+// loss arithmetic, LDS-DMA, and the host side of the launches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -174,6 +177,155 @@ __device__ __forceinline__ float block_reduce_max(float v, float* red) {
   float r = (lane < nw) ? red[lane] : -3.402823466e38f;
   r = wave_reduce_max(r);
   return r;
+}
+
+// ---- index arithmetic shared by the kernels that select, sort, compact and match (heads.hip, proposals.hip, evaluation.hip,
+// elementwise.hip)
+// Inclusive scan over the workgroup's blockDim.x threads (Hillis-Steele in LDS, two barriers per step; any blockDim.x <= the
+// length of buf; a kernel that is only ever launched with one block size names it as THREADS, which lets the compiler unroll the
+// steps as it did for the literal bounds the sites used to spell — 0 = read blockDim.x), in thread order, or with REVERSE from the last thread to the first (a suffix scan).  op(earlier, later) need
+// only be associative.  Every thread of the workgroup calls it.  Returns
+//   incl   op over the threads up to and including this one,
+//   prev   the incl of the thread before this one in scan order — the exclusive value, for operators without an inverse;
+//          this thread's own incl at the first thread, which has none before it,
+//   total  the incl of the last thread in scan order.
+// It begins by writing buf and ends in a barrier after its last read: on return buf is free, and a call site needs no barrier of
+// its own for it, neither before the next call on the same buf nor before any other use.  (Fields a caller leaves unread cost
+// nothing: the helper is inlined and their LDS reads go.)
+template <typename T> struct BlockScan { T incl, prev, total; };
+template <int THREADS = 0, bool REVERSE = false, typename T, typename Op>
+__device__ __forceinline__ BlockScan<T> block_scan(T v, T* buf, Op op) {
+  const int n = THREADS ? THREADS : (int)blockDim.x, rank = REVERSE ? n - 1 - (int)threadIdx.x : (int)threadIdx.x;   // this thread's place in scan order
+  auto at = [&](int r) -> T& { return buf[REVERSE ? n - 1 - r : r]; };                      // buf is indexed by thread
+  at(rank) = v;
+  __syncthreads();
+  for (int off = 1; off < n; off <<= 1) {
+    const bool has = rank >= off;
+    const T o = at(has ? rank - off : rank);
+    __syncthreads();
+    if (has) {
+      v = op(o, v);
+      at(rank) = v;
+    }
+    __syncthreads();
+  }
+  BlockScan<T> r;
+  r.incl = v;
+  r.prev = at(rank > 0 ? rank - 1 : rank);
+  r.total = at(n - 1);
+  __syncthreads();
+  return r;
+}
+struct ScanAdd {
+  template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+
+// Order-preserving map of a float onto unsigned bits (ascending unsigned order == ascending float order by bits: -NaN < -inf < ..
+// < -0.0 < +0.0 < .. < +inf < +NaN) and its inverse
+__device__ __forceinline__ unsigned int orderable(float f) {
+  const unsigned int u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float from_orderable(unsigned int o) {
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+// ascending sort of this key == descending score, ascending index (the oracle's tie rule)
+__device__ __forceinline__ unsigned long long make_key(float score, unsigned int idx) {
+  return ((unsigned long long)(~orderable(score)) << 32) | idx;
+}
+// a make_key key taken apart: its index, and its score bit for bit
+__device__ __forceinline__ int key_index(unsigned long long key) { return (int)(unsigned int)(key & 0xFFFFFFFFu); }
+__device__ __forceinline__ float key_score(unsigned long long key) { return from_orderable(~(unsigned int)(key >> 32)); }
+
+// Ascending bitonic sort of N 64-bit keys by one workgroup.  Requires: N a power of two, blockDim.x a multiple of 64, every thread
+// of the workgroup calls it, and the keys are written and a barrier passed before the call.  It ends in a barrier: on return every
+// thread may read any key.  An ascending sort of a fixed multiset of words has one result, whatever the order of the passes.
+// WAVE_LOCAL (keys in LDS only): a pass whose partner distance j is < 128 stays inside one aligned block of 128 keys.  A wave owns
+// such a block (lane = the pair whose lower index has bit j clear) and runs all the remaining passes of the stage on it back to
+// back: the LDS serves one wave's requests in issue order, so those passes need no workgroup barrier — 2048 keys take 14
+// barriers instead of 66 (the mining kernel sorts one score column per image-level class on the step's critical path).
+// (Holding the block in registers and exchanging by __shfl_xor was slower — four ds_bpermute per pass — and so was giving a thread
+// four independent pairs per pass: a pass costs ~0.2 us of issue + LDS round trip either way; in-kernel stamps at R = 2000, G = 2:
+// column sorts 27 us, threshold + keys 2, NMS sort 7, NMS 12, labels 6.)
+// nseg > 1: nseg independent arrays of N keys back to back, all sorted ascending by the same passes (the passes are latency bound,
+// so several score columns sort in the time of one).
+template <bool WAVE_LOCAL>
+__device__ void bitonic_sort(unsigned long long* keys, int N, int nseg = 1) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const int T = N * nseg;
+  for (int k = 2; k <= N; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (WAVE_LOCAL && j < 128) {
+        for (int base = wave * 128; base < T; base += nwaves * 128) {
+          for (int jj = j; jj > 0; jj >>= 1) {
+            const int i = base + (((lane & ~(jj - 1)) << 1) | (lane & (jj - 1))), p = i | jj;
+            if (p < T) {
+              const unsigned long long a = keys[i], b = keys[p];
+              const bool asc = ((i & (N - 1)) & k) == 0;
+              if ((a > b) == asc) { keys[i] = b; keys[p] = a; }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+          }
+        }
+        __syncthreads();
+        break;
+      }
+      for (int i = threadIdx.x; i < T; i += blockDim.x) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const unsigned long long a = keys[i], b = keys[ixj];
+          const bool asc = ((i & (N - 1)) & k) == 0;
+          if ((a > b) == asc) { keys[i] = b; keys[ixj] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+// smallest power of two >= n, at least 64 (a wave): the length a list of n keys is padded to for bitonic_sort, on both sides of a launch
+__host__ __device__ __forceinline__ int next_pow2(int n) { int p = 64; while (p < n) p <<= 1; return p; }
+
+// ---- float32 box arithmetic of the index side (heads.hip, proposals.hip, proposal_ar.hip): boxes as x0 y0 x1 y1, a float4 by value
+// (a caller whose pointer is not known to be 16-byte aligned builds it from four scalar loads); every operation rounds on its own,
+// in the reference's order (the library is built without FMA contraction)
+__device__ __forceinline__ float box_area(float4 b) { return __fmul_rn(b.z - b.x, b.w - b.y); }
+// detectron2 pairwise_iou (structures/boxes.py:322-370), one pair: 0 where inter <= 0.  A NaN width or height of the intersection
+// counts as 0 (fmaxf drops it), so a NaN coordinate gives 0 unless it reaches an area: then the union, and the result, is NaN.
+// area_a / area_b: box_area of a and b (a caller that holds one box against many hoists its area)
+__device__ __forceinline__ float pairwise_iou(float4 a, float area_a, float4 b, float area_b) {
+  const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f);
+  const float h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
+  const float inter = __fmul_rn(w, h);
+  return inter > 0.f ? __fdiv_rn(inter, __fadd_rn(area_a, area_b) - inter) : 0.f;
+}
+__device__ __forceinline__ float pairwise_iou(float4 a, float4 b) { return pairwise_iou(a, box_area(a), b, box_area(b)); }
+// torchvision nms IoU: inter / (a_i + a_j - inter), inter = max(0,dx)*max(0,dy)
+__device__ __forceinline__ float iou_nms(float4 a, float4 b) {
+  const float w = fmaxf(0.f, fminf(a.z, b.z) - fmaxf(a.x, b.x));
+  const float h = fmaxf(0.f, fminf(a.w, b.w) - fmaxf(a.y, b.y));
+  const float inter = __fmul_rn(w, h);
+  return __fdiv_rn(inter, __fadd_rn(box_area(a), box_area(b)) - inter);
+}
+// iou_nms(a, b) > thresh for thresh >= 0, without the division for disjoint boxes: inter == 0 gives 0 / union = 0 (or 0 / 0 = NaN for
+// two empty boxes), never > thresh — most pairs of a 2000-candidate list are disjoint
+__device__ __forceinline__ bool iou_nms_above(float4 a, float4 b, float thresh) {
+  const float w = fminf(a.z, b.z) - fmaxf(a.x, b.x);
+  const float h = fminf(a.w, b.w) - fmaxf(a.y, b.y);
+  if (!(w > 0.f && h > 0.f)) return false;
+  const float inter = __fmul_rn(w, h);
+  return __fdiv_rn(inter, __fadd_rn(box_area(a), box_area(b)) - inter) > thresh;
+}
+// one coordinate clipped to [0, hi] (Boxes.clip); a NaN becomes 0 (fmaxf drops it)
+__device__ __forceinline__ float clip(float v, float hi) { return fminf(fmaxf(v, 0.f), hi); }
+// Box2BoxTransform.apply_deltas (box_regression.py:73-116) against one anchor / proposal box.  dx dy dw dh are the deltas AFTER the
+// caller has divided them by the weights and clamped dw, dh at scale_clamp: the callers differ in that clamp (see there).
+__device__ __forceinline__ float4 decode_box(float4 an, float dx, float dy, float dw, float dh) {
+  const float w = an.z - an.x, h = an.w - an.y;
+  const float cx = an.x + __fmul_rn(0.5f, w), cy = an.y + __fmul_rn(0.5f, h);
+  const float px = __fadd_rn(__fmul_rn(dx, w), cx), py = __fadd_rn(__fmul_rn(dy, h), cy);
+  const float pw = __fmul_rn(expf(dw), w), ph = __fmul_rn(expf(dh), h);
+  return make_float4(px - __fmul_rn(0.5f, pw), py - __fmul_rn(0.5f, ph), px + __fmul_rn(0.5f, pw), py + __fmul_rn(0.5f, ph));
 }
 
 // ---- loss arithmetic shared by the RPN / detector losses (detector.hip) and the refinement / focal losses (heads.hip)

@@ -1348,16 +1348,9 @@ __global__ __launch_bounds__(1024) void threshold_select_kernel(int n, const flo
       for (int a = 0; a < n_allowed; ++a) in = in || (allowed[a] == classes[i]);
       ok = in;
     }
-    s_scan[threadIdx.x] = ok ? 1 : 0;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-      const int add = threadIdx.x >= off ? s_scan[threadIdx.x - off] : 0;
-      __syncthreads();
-      s_scan[threadIdx.x] += add;
-      __syncthreads();
-    }
+    const BlockScan<int> sc = block_scan<1024>(ok ? 1 : 0, s_scan, ScanAdd());
     if (ok) {
-      const int o = s_base + s_scan[threadIdx.x] - 1;
+      const int o = s_base + sc.incl - 1;
       out_boxes[4 * o + 0] = boxes[4 * i + 0]; out_boxes[4 * o + 1] = boxes[4 * i + 1];
       out_boxes[4 * o + 2] = boxes[4 * i + 2]; out_boxes[4 * o + 3] = boxes[4 * i + 3];
       if (out_classes && classes) out_classes[o] = classes[i];
@@ -1365,7 +1358,7 @@ __global__ __launch_bounds__(1024) void threshold_select_kernel(int n, const flo
       if (out_index) out_index[o] = i;
     }
     __syncthreads();
-    if (threadIdx.x == 0) s_base += s_scan[1023];
+    if (threadIdx.x == 0) s_base += sc.total;
     __syncthreads();
   }
   if (threadIdx.x == 0) out_count[0] = s_base;

@@ -127,25 +127,6 @@ struct MaxCount {
   int n;
 };
 
-// inclusive Hillis-Steele scan over the workgroup in thread order; buf[kThreads - 1] holds the total until the next call
-template <typename T, typename Op>
-__device__ T block_scan(T v, T* buf, Op op) {
-  const int tid = threadIdx.x;
-  buf[tid] = v;
-  __syncthreads();
-  for (int off = 1; off < kThreads; off <<= 1) {
-    const bool has = tid >= off;
-    T o = buf[has ? tid - off : tid];
-    __syncthreads();
-    if (has) {
-      v = op(o, v);
-      buf[tid] = v;
-    }
-    __syncthreads();
-  }
-  return v;
-}
-
 // numpy's pairwise_sum of a[s, s + n) for n <= 8192, with a(k) = rterms[last - k] (the terms are stored back to front)
 __device__ double pairwise_leaf(const double* rterms, long long last, long long s, long long n) {
   if (n < 8) {
@@ -244,16 +225,14 @@ __global__ void __launch_bounds__(kThreads) voc_ap_kernel(
       run += f;
       v[k] = run;
     }
-    const unsigned long long incl = block_scan(run, sbuf, [](unsigned long long a, unsigned long long b) { return a + b; });
-    const unsigned long long total = sbuf[kThreads - 1];
-    const unsigned long long before = carry + incl - run;
+    const BlockScan<unsigned long long> sc = block_scan<kThreads>(run, sbuf, ScanAdd());
+    const unsigned long long before = carry + sc.incl - run;
 #pragma unroll
     for (int k = 0; k < kItems; ++k) {
       const long long d = lo + tid * kItems + k;
       if (d < nd) cum[d] = before + v[k];
     }
-    carry += total;
-    __syncthreads();
+    carry += sc.total;
   }
   __syncthreads();                               // cum complete and visible to the workgroup
 
@@ -283,10 +262,9 @@ __global__ void __launch_bounds__(kThreads) voc_ap_kernel(
         run.n += m1[k] != m0[k];
       }
     }
-    const MaxCount incl = block_scan(run, mbuf, [](MaxCount a, MaxCount b) { return MaxCount{np_max(b.m, a.m), a.n + b.n}; });
-    const MaxCount total = mbuf[kThreads - 1];
-    double env = tid > 0 ? np_max(mbuf[tid - 1].m, mcarry.m) : mcarry.m;   // max(mpre[i + 1 ..]) above this thread's items
-    int pos = mcarry.n + incl.n - run.n;                                      // change points at larger i
+    const BlockScan<MaxCount> sc = block_scan<kThreads>(run, mbuf, [](MaxCount a, MaxCount b) { return MaxCount{np_max(b.m, a.m), a.n + b.n}; });
+    double env = tid > 0 ? np_max(sc.prev.m, mcarry.m) : mcarry.m;            // max(mpre[i + 1 ..]) above this thread's items
+    int pos = mcarry.n + sc.incl.n - run.n;                                   // change points at larger i
 #pragma unroll
     for (int k = 0; k < kItems; ++k) {
       const long long r = lo + tid * kItems + k;
@@ -299,9 +277,8 @@ __global__ void __launch_bounds__(kThreads) voc_ap_kernel(
           if (m1[k] >= t11[q] && !(i > 0 && m0[k] >= t11[q])) p11[q] = env;
       }
     }
-    __syncthreads();                             // mbuf is read above; the next tile's scan overwrites it
-    mcarry.m = np_max(total.m, mcarry.m);
-    mcarry.n += total.n;
+    mcarry.m = np_max(sc.total.m, mcarry.m);
+    mcarry.n += sc.total.n;
   }
   __syncthreads();
 
@@ -604,10 +581,9 @@ __global__ void __launch_bounds__(kThreads) coco_accum_kernel(
       if (j < nd) v[k] = flag(j, in[k], idx[k]);
       run += v[k];
     }
-    const u64 incl = block_scan(run, sbuf, [](u64 x, u64 y) { return x + y; });
-    const u64 tile_total = sbuf[kThreads - 1];
-    const u64 before = carry - tile_total;
-    u64 cum = before + incl - run;
+    const BlockScan<u64> sc = block_scan<kThreads>(run, sbuf, ScanAdd());
+    const u64 before = carry - sc.total;
+    u64 cum = before + sc.incl - run;
     double pr[kItems], tmax = -INFINITY;
 #pragma unroll
     for (int k = 0; k < kItems; ++k) {
@@ -616,20 +592,11 @@ __global__ void __launch_bounds__(kThreads) coco_accum_kernel(
       pr[k] = !in[k] ? -INFINITY : n > 0 ? (double)tp / (double)n : 0.0;
       if (pr[k] > tmax) tmax = pr[k];
     }
-    // suffix max over the threads: mbuf[tid] = max of the threads tid .. kThreads - 1
-    __syncthreads();
-    mbuf[tid] = tmax;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {
-      const bool has = tid + off < kThreads;
-      const double o = mbuf[has ? tid + off : tid];
-      __syncthreads();
-      if (has && o > mbuf[tid]) mbuf[tid] = o;
-      __syncthreads();
-    }
-    double env = tid + 1 < kThreads ? mbuf[tid + 1] : -INFINITY;
+    // suffix max over the threads: the scan from the last thread to the first; prev = the max of the threads tid + 1 .. kThreads - 1
+    const BlockScan<double> sm = block_scan<kThreads, true>(tmax, mbuf, [](double later, double mine) { return later > mine ? later : mine; });
+    double env = tid + 1 < kThreads ? sm.prev : -INFINITY;
     if (mcarry > env) env = mcarry;
-    const double tile_max = mbuf[0];
+    const double tile_max = sm.total;
 #pragma unroll
     for (int k = kItems - 1; k >= 0; --k) {
       if (pr[k] > env) env = pr[k];              // the envelope at this position
@@ -648,7 +615,6 @@ __global__ void __launch_bounds__(kThreads) coco_accum_kernel(
       }
       cum -= v[k];
     }
-    __syncthreads();                             // mbuf and sbuf are rewritten by the next tile
     if (tile_max > mcarry) mcarry = tile_max;
     carry = before;
   }

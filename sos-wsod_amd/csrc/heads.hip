@@ -6,6 +6,9 @@
 // They are latency-bound glue in the reference (dozens of tiny kernels + host syncs); here the whole
 // chain is 8 launches with wave64 shuffle reductions, no host round trip, and the K refinement rounds side by side
 // (a round's mining scores depend on the logits only, not on the previous round's labels).
+// Shared with the other index kernels through common.h, one copy each: the workgroup scan (block_scan), the bitonic sort and its
+// score | index keys (bitonic_sort, make_key), and the float32 box arithmetic (pairwise_iou, iou_nms, decode_box, clip).  This file
+// keeps what is its own: det_score and the TTA key on top of orderable, the fminf clamp in front of decode_box.
 #include <float.h>
 #include "common.h"
 #include "soswsod_hip.h"
@@ -369,94 +372,7 @@ __global__ __launch_bounds__(1024) void focal_reduce_kernel(int N, float scale, 
 }
 
 // ------------------------------------------------------------------------------------------- mining + labelling
-__device__ __forceinline__ unsigned int orderable(float f) {
-  const unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float from_orderable(unsigned int o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-// ascending sort of this key == descending score, ascending index (the oracle's tie rule)
-__device__ __forceinline__ unsigned long long make_key(float score, unsigned int idx) {
-  return ((unsigned long long)(~orderable(score)) << 32) | idx;
-}
-// a make_key key taken apart: its index, and its score bit for bit
-__device__ __forceinline__ int key_index(unsigned long long key) { return (int)(unsigned int)(key & 0xFFFFFFFFu); }
-__device__ __forceinline__ float key_score(unsigned long long key) { return from_orderable(~(unsigned int)(key >> 32)); }
-
-// WAVE_LOCAL (keys in LDS): a pass whose partner distance j is < 128 stays inside one aligned block of 128 keys.  A wave owns
-// such a block (lane = the pair whose lower index has bit j clear) and runs all the remaining passes of the stage on it back to
-// back: the LDS serves one wave's requests in issue order, so those passes need no workgroup barrier — 2048 keys take 14
-// barriers instead of 66 (the mining kernel sorts one score column per image-level class on the step's critical path).
-// (Holding the block in registers and exchanging by __shfl_xor was slower — four ds_bpermute per pass — and so was giving a thread
-// four independent pairs per pass: a pass costs ~0.2 us of issue + LDS round trip either way; in-kernel stamps at R = 2000, G = 2:
-// column sorts 27 us, threshold + keys 2, NMS sort 7, NMS 12, labels 6.)
-// nseg > 1: nseg independent arrays of N keys back to back, all sorted ascending by the same passes (the passes are latency bound,
-// so several score columns sort in the time of one).
-template <bool WAVE_LOCAL>
-__device__ void bitonic_sort(unsigned long long* keys, int N, int nseg = 1) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-  const int T = N * nseg;
-  for (int k = 2; k <= N; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (WAVE_LOCAL && j < 128) {
-        for (int base = wave * 128; base < T; base += nwaves * 128) {
-          for (int jj = j; jj > 0; jj >>= 1) {
-            const int i = base + (((lane & ~(jj - 1)) << 1) | (lane & (jj - 1))), p = i | jj;
-            if (p < T) {
-              const unsigned long long a = keys[i], b = keys[p];
-              const bool asc = ((i & (N - 1)) & k) == 0;
-              if ((a > b) == asc) { keys[i] = b; keys[p] = a; }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-          }
-        }
-        __syncthreads();
-        break;
-      }
-      for (int i = threadIdx.x; i < T; i += blockDim.x) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], b = keys[ixj];
-          const bool asc = ((i & (N - 1)) & k) == 0;
-          if ((a > b) == asc) { keys[i] = b; keys[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// smallest power of two >= n, at least 64 (a wave): the length a list of n keys is padded to for bitonic_sort, on both sides of a launch
-__host__ __device__ __forceinline__ int next_pow2(int n) { int p = 64; while (p < n) p <<= 1; return p; }
-
-__device__ __forceinline__ float box_area(const float* b) { return __fmul_rn(b[2] - b[0], b[3] - b[1]); }
-
-// torchvision nms IoU: inter / (a_i + a_j - inter), inter = max(0,dx)*max(0,dy)
-__device__ __forceinline__ float iou_nms(const float* a, const float* b) {
-  const float w = fmaxf(0.f, fminf(a[2], b[2]) - fmaxf(a[0], b[0]));
-  const float h = fmaxf(0.f, fminf(a[3], b[3]) - fmaxf(a[1], b[1]));
-  const float inter = __fmul_rn(w, h);
-  return __fdiv_rn(inter, __fadd_rn(box_area(a), box_area(b)) - inter);
-}
-// iou_nms(a, b) > thresh for thresh >= 0, without the division for disjoint boxes: inter == 0 gives 0 / union = 0 (or 0 / 0 = NaN for
-// two empty boxes), never > thresh — most pairs of a 2000-candidate list are disjoint
-__device__ __forceinline__ bool iou_nms_above(const float* a, const float* b, float thresh) {
-  const float w = fminf(a[2], b[2]) - fmaxf(a[0], b[0]);
-  const float h = fminf(a[3], b[3]) - fmaxf(a[1], b[1]);
-  if (!(w > 0.f && h > 0.f)) return false;
-  const float inter = __fmul_rn(w, h);
-  return __fdiv_rn(inter, __fadd_rn(box_area(a), box_area(b)) - inter) > thresh;
-}
-// detectron2 pairwise_iou (structures/boxes.py:329-361): 0 where inter <= 0
-__device__ __forceinline__ float iou_pair(const float* gtb, const float* pb) {
-  const float w = fmaxf(fminf(gtb[2], pb[2]) - fmaxf(gtb[0], pb[0]), 0.f);
-  const float h = fmaxf(fminf(gtb[3], pb[3]) - fmaxf(gtb[1], pb[1]), 0.f);
-  const float inter = __fmul_rn(w, h);
-  return inter > 0.f ? __fdiv_rn(inter, __fadd_rn(box_area(gtb), box_area(pb)) - inter) : 0.f;
-}
-
+// (sort keys, bitonic_sort, next_pow2 and the box arithmetic — iou_nms, pairwise_iou, decode_box, clip — are common.h's)
 // STAGED (the usual case: the sort keys + 25 bytes per (rank, class) slot fit LDS): the slot lists live in LDS, the NMS sort keys
 // are built straight from the thresholded slots (slot order = masked_select order, so the slot number is the tie-break), and the
 // greedy NMS walks the candidates in SORTED order with their boxes gathered once into that order — the serial part of the kernel
@@ -510,8 +426,8 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
     }
   }
   // the candidate box of proposal `row` for image-level class number g
-  auto cand_box = [&](int row, int g) -> const float* {
-    return (EXT && cand) ? cand + ((long)row * G + g) * 4 : boxes + (long)row * 4;
+  auto cand_box = [&](int row, int g) -> float4 {
+    return *(const float4*)((EXT && cand) ? cand + ((long)row * G + g) * 4 : boxes + (long)row * 4);
   };
   const int NP = next_pow2(R > n_slots ? R : n_slots);
   // sort keys: LDS while NP * 8 B + the suppression bytes fit (R, top_k*G <= 16384: every VOC / COCO recipe with up to 16
@@ -554,17 +470,10 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
   int cnt = 0;
   for (int s = tid * per; s < min(n_slots, (tid + 1) * per); ++s)
     cnt += (s < G || slot_score[s] >= score_thresh) ? 1 : 0;
-  s_scan[tid] = cnt;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int add = tid >= off ? s_scan[tid - off] : 0;
-    __syncthreads();
-    s_scan[tid] += add;
-    __syncthreads();
-  }
-  const int n = s_scan[1023];
+  const BlockScan<int> kept = block_scan<1024>(cnt, s_scan, ScanAdd());
+  const int n = kept.total;
   const int NPN = next_pow2(n);
-  int pos = s_scan[tid] - cnt;
+  int pos = kept.incl - cnt;
   // ---- 3. class-agnostic greedy NMS (get_pgt_mist :576-581; torchvision nms): sort by score desc, position asc
   if (STAGED) {
     for (int s = tid * per; s < min(n_slots, (tid + 1) * per); ++s)
@@ -591,7 +500,7 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
     for (int t = tid; t < n; t += blockDim.x) {
       const int slot = key_index(keys[t]);
       const int row = slot_idx[slot];
-      sbox[t] = *(const float4*)(EXT ? cand_box(row, slot % G) : boxes + (long)row * 4);
+      sbox[t] = EXT ? cand_box(row, slot % G) : *(const float4*)(boxes + (long)row * 4);
       sup[t] = 0;
     }
     __syncthreads();
@@ -615,7 +524,7 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
       const float4 bp = sbox[t];
       for (int u = t + 1 + tid; u < n; u += blockDim.x) {
         const float4 bq = sbox[u];
-        if (!sup[u] && iou_nms((const float*)&bp, (const float*)&bq) > nms_thresh) sup[u] = 1;
+        if (!sup[u] && iou_nms(bp, bq) > nms_thresh) sup[u] = 1;
       }
       __syncthreads();                         // flags final; everybody holds box t in registers
       if (tid == 0) {                          // the kept boxes are the prefix of the sorted list (nk <= t: slots already consumed)
@@ -639,10 +548,10 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
       if (sup[p]) continue;                                               // uniform across the workgroup
       if (tid == 0) { pgt_index[nk] = c_idx[p]; pgt_class[nk] = EXT ? gt_classes[c_cls[p]] : c_cls[p]; pgt_score[nk] = c_score[p]; }
       ++nk;
-      const float* bp = EXT ? cand_box(c_idx[p], c_cls[p]) : boxes + (long)c_idx[p] * 4;
+      const float4 bp = EXT ? cand_box(c_idx[p], c_cls[p]) : *(const float4*)(boxes + (long)c_idx[p] * 4);
       for (int u = t + 1 + tid; u < n; u += blockDim.x) {
         const int q = key_index(keys[u]);
-        if (!sup[q] && iou_nms(bp, EXT ? cand_box(c_idx[q], c_cls[q]) : boxes + (long)c_idx[q] * 4) > nms_thresh) sup[q] = 1;
+        if (!sup[q] && iou_nms(bp, EXT ? cand_box(c_idx[q], c_cls[q]) : *(const float4*)(boxes + (long)c_idx[q] * 4)) > nms_thresh) sup[q] = 1;
       }
       __syncthreads();
     }
@@ -663,20 +572,16 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
   // the j-th kept pseudo box (workspace form: looked up again; STAGED: sbox[j])
   auto kept_box = [&](int j) -> float4 {
     if (STAGED) return sbox[j];
-    return *(const float4*)((EXT && cand) ? cand_box(pgt_index[j], kept_g[j]) : boxes + (long)pgt_index[j] * 4);
+    return (EXT && cand) ? cand_box(pgt_index[j], kept_g[j]) : *(const float4*)(boxes + (long)pgt_index[j] * 4);
   };
   if (EXT && pgt_box)
     for (int j = tid; j < nk; j += blockDim.x) pgt_box[j] = kept_box(j);
   // ---- 4. IoU matching + labels (pairwise_iou, Matcher [iou_bg, iou_fg] -> {0,-1,1}, roi_heads.py:225-257,266-375)
   for (int r = tid; r < R; r += blockDim.x) {
-    const float4 pbv = *(const float4*)(boxes + (long)r * 4);
-    const float* pb = (const float*)&pbv;
+    const float4 pb = *(const float4*)(boxes + (long)r * 4);
     float best = -1.f; int bj = 0;
     for (int j = 0; j < nk; ++j) {
-      float v;
-      if (STAGED) { const float4 gb = sbox[j]; v = iou_pair((const float*)&gb, pb); }
-      else if (EXT) { const float4 gb = kept_box(j); v = iou_pair((const float*)&gb, pb); }
-      else v = iou_pair(boxes + (long)pgt_index[j] * 4, pb);
+      float v = pairwise_iou(kept_box(j), pb);
       if (EXT && !(v == v)) v = 0.f;                                    // a NaN coordinate: where(inter > 0, ., 0) of a NaN inter
       if (v > best) { best = v; bj = j; }                               // first max = lowest pgt index
     }
@@ -695,22 +600,12 @@ __global__ __launch_bounds__(1024) void mine_label_kernel(int R, int ncol, int K
 // ------------------------------------------------------------------------------------------- inference (a23)
 // all_scores[r][j] = mean_k softmax(cls_score_k logits)[j]; all_boxes[r][4c..] = apply_deltas(mean_k deltas_k, proposal)
 // (predict_probs_K / predict_boxes_K fast_rcnn_oicr.py:674-735, Box2BoxTransform.apply_deltas box_regression.py:73-110)
-// Box2BoxTransform.apply_deltas (box_regression.py:73-110) against one proposal box: every multiplication and addition rounds on its
-// own, in the reference's order (the one copy of this arithmetic: predict_kernel and update_boxes_kernel decode with it)
-struct DecodeAnchor {
-  float w, h, cx, cy;
-  __device__ __forceinline__ explicit DecodeAnchor(const float* b) {
-    w = b[2] - b[0]; h = b[3] - b[1];
-    cx = b[0] + 0.5f * w; cy = b[1] + 0.5f * h;
-  }
-  __device__ __forceinline__ float4 apply(const float* d, float wx, float wy, float ww, float wh, float scale_clamp) const {
-    const float dx = __fdiv_rn(d[0], wx), dy = __fdiv_rn(d[1], wy);
-    const float dw = fminf(__fdiv_rn(d[2], ww), scale_clamp), dh = fminf(__fdiv_rn(d[3], wh), scale_clamp);
-    const float px = __fadd_rn(__fmul_rn(dx, w), cx), py = __fadd_rn(__fmul_rn(dy, h), cy);
-    const float pw = __fmul_rn(expf(dw), w), ph = __fmul_rn(expf(dh), h);
-    return make_float4(px - __fmul_rn(0.5f, pw), py - __fmul_rn(0.5f, ph), px + __fmul_rn(0.5f, pw), py + __fmul_rn(0.5f, ph));
-  }
-};
+// The deltas of one box over their weights, dw / dh clamped at scale_clamp, decoded against proposal box `an` (decode_box).  fminf
+// DROPS a NaN dw / dh: the box comes out finite, from the clamp, where the reference's torch.clamp(max=) keeps the NaN (a known
+// deviation; the RPN's decode keeps it).
+__device__ __forceinline__ float4 decode_clamped(float4 an, const float* d, float wx, float wy, float ww, float wh, float scale_clamp) {
+  return decode_box(an, __fdiv_rn(d[0], wx), __fdiv_rn(d[1], wy), fminf(__fdiv_rn(d[2], ww), scale_clamp), fminf(__fdiv_rn(d[3], wh), scale_clamp));
+}
 
 __global__ __launch_bounds__(256) void predict_kernel(int R, int K, int RK, const float* __restrict__ logits, long ld,
                                                       int base_col, int round_stride, const float* __restrict__ boxes,
@@ -731,7 +626,8 @@ __global__ __launch_bounds__(256) void predict_kernel(int R, int K, int RK, cons
     for (int j = 0; j < K1; ++j) S[j] += expf(x[j] - m) / z;
   }
   for (int j = 0; j < K1; ++j) S[j] = __fdiv_rn(S[j], (float)RK);
-  const DecodeAnchor a(boxes + (long)r * 4);
+  const float* b = boxes + (long)r * 4;
+  const float4 an = make_float4(b[0], b[1], b[2], b[3]);
   float* O = all_boxes + (long)r * 4 * K;
   for (int c = 0; c < K; ++c) {
     float d[4];
@@ -740,7 +636,7 @@ __global__ __launch_bounds__(256) void predict_kernel(int R, int K, int RK, cons
       for (int k = 0; k < RK; ++k) acc += L[base_col + k * round_stride + K1 + 4 * c + q];   // sum in branch order (:691-693)
       d[q] = __fdiv_rn(acc, (float)RK);
     }
-    const float4 p = a.apply(d, wx, wy, ww, wh, scale_clamp);
+    const float4 p = decode_clamped(an, d, wx, wy, ww, wh, scale_clamp);
     O[4 * c + 0] = p.x; O[4 * c + 1] = p.y; O[4 * c + 2] = p.z; O[4 * c + 3] = p.w;
   }
 }
@@ -778,10 +674,9 @@ __global__ __launch_bounds__(256) void update_boxes_kernel(int V, int R, int K, 
     }
     d[q] = __fdiv_rn(acc, (float)V);
   }
-  *o = DecodeAnchor(boxes + (long)r * 4).apply(d, wx, wy, ww, wh, scale_clamp);
+  const float* b = boxes + (long)r * 4;
+  *o = decode_clamped(make_float4(b[0], b[1], b[2], b[3]), d, wx, wy, ww, wh, scale_clamp);
 }
-
-__device__ __forceinline__ float clipf(float v, float hi) { return fminf(fmaxf(v, 0.f), hi); }
 
 // The detection keys rank by score VALUE as the reference's sort does: -0.0 and +0.0 are one score (an RPN logit can be either) and the
 // position decides between them.  make_key ranks by bits (+0.0 above -0.0), so a zero goes into a detection key as +0.0 — and comes out of
@@ -793,14 +688,14 @@ __device__ __forceinline__ float det_score(float s) { return s == 0.f ? 0.f : s;
 // proposal `row`'s class-c box clipped to the image, and a box moved by its class's offset as torchvision batched_nms forms it
 __device__ __forceinline__ float4 det_box(const float* __restrict__ boxes, long row, int K, int c, float imw, float imh) {
   const float* b = boxes + row * 4 * K + 4 * c;
-  return make_float4(clipf(b[0], imw), clipf(b[1], imh), clipf(b[2], imw), clipf(b[3], imh));
+  return make_float4(clip(b[0], imw), clip(b[1], imh), clip(b[2], imw), clip(b[3], imh));
 }
 __device__ __forceinline__ float4 offset_box(float4 b, float off) {
   return make_float4(__fadd_rn(b.x, off), __fadd_rn(b.y, off), __fadd_rn(b.z, off), __fadd_rn(b.w, off));
 }
 // IoU(a, b) > thresh; pos_thresh = (thresh >= 0) is the caller's, worked out once per kernel
 __device__ __forceinline__ bool nms_over(float4 a, float4 b, float thresh, bool pos_thresh) {
-  return pos_thresh ? iou_nms_above((const float*)&a, (const float*)&b, thresh) : iou_nms((const float*)&a, (const float*)&b) > thresh;
+  return pos_thresh ? iou_nms_above(a, b, thresh) : iou_nms(a, b) > thresh;
 }
 // lane k's box to every lane (k wave-uniform): v_readlane, no LDS access
 __device__ __forceinline__ float4 lane_box(float4 v, int k) {
@@ -984,7 +879,7 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(int R, int K, float
       const int q = key_index(keys[u]);
       if (sup[q]) continue;
       const float4 b = offset_box(det_box(boxes, q, K, c, imw, imh), off);
-      if (iou_nms((const float*)&a, (const float*)&b) > nms_thresh) sup[q] = 1;
+      if (iou_nms(a, b) > nms_thresh) sup[q] = 1;
     }
     __syncthreads();
   }
@@ -1166,7 +1061,7 @@ __device__ __forceinline__ TtaRow tta_row(int i, int T, int K, const float* __re
   x0 = __fmul_rn(__fmul_rn(x0, t[2]), t[4]); x1 = __fmul_rn(__fmul_rn(x1, t[2]), t[4]);
   y0 = __fmul_rn(__fmul_rn(y0, t[3]), t[5]); y1 = __fmul_rn(__fmul_rn(y1, t[3]), t[5]);
   const bool fin = fin_in && isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1);
-  r.b[0] = clipf(x0, imw); r.b[1] = clipf(y0, imh); r.b[2] = clipf(x1, imw); r.b[3] = clipf(y1, imh);
+  r.b[0] = clip(x0, imw); r.b[1] = clip(y0, imh); r.b[2] = clip(x1, imw); r.b[3] = clip(y1, imh);
   r.keep = fin && r.score > 1e-8f && r.cls >= 0 && r.cls < K;
   return r;
 }

@@ -78,27 +78,16 @@ __host__ __device__ inline long long slot_bytes(long long boxes, long long props
   return (24 * boxes + 4 * used_words(props) + 15) / 16 * 16;
 }
 
-// boxes.py:322-368 in float32: p a proposal, g a ground-truth box of area ga
-__device__ __forceinline__ float iou_of(const float4 p, const float4 g, const float ga) {
-  const float pa = (p.z - p.x) * (p.w - p.y);
-  const float tw = fminf(p.z, g.z) - fmaxf(p.x, g.x);
-  const float th = fminf(p.w, g.w) - fmaxf(p.y, g.y);
-  const float w = tw > 0.f ? tw : 0.f;
-  const float h = th > 0.f ? th : 0.f;
-  const float inter = w * h;
-  return inter > 0.f ? inter / (pa + ga - inter) : 0.f;
-}
-
 // box k's best unused proposal among the first np (every lane returns it)
 __device__ __forceinline__ Cand scan_box(const float4* prop, int np, const float4* gbox, const uint32_t* used, int k, int lane) {
   const float4 g = gbox[k];
-  const float ga = (g.z - g.x) * (g.w - g.y);
+  const float ga = box_area(g);
   Cand best = {0.f, k, -1};
   uint32_t uw = 0;
   for (int p = lane, i = 0; p < np; p += 64, ++i) {
     if ((i & 31) == 0) uw = used[(i >> 5) * 64 + lane];
     if ((uw >> (i & 31)) & 1u) continue;
-    const Cand c = {iou_of(prop[p], g, ga), k, p};
+    const Cand c = {pairwise_iou(prop[p], box_area(prop[p]), g, ga), k, p};     // boxes.py:322-368 in float32, g's area hoisted
     if (replaces(best, c)) best = c;
   }
   return wave_best(best);

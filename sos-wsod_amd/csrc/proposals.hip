@@ -12,6 +12,9 @@
 // argsort(random keys, stable)[:num] of the label sampler (key = 24-bit hash of (seed, position in the candidate list)).
 // Random keys: u = splitmix64(seed + position) >> 40, the closed form of the oracle's generator (oracle/detgen.py), so that the
 // fixtures' sampled sets are reproduced bit for bit; the product draws `seed` per candidate list from its own counter.
+// Shared with the other index kernels through common.h, one copy each: the workgroup scan (block_scan), the LDS bitonic sort
+// (bitonic_sort), the float's monotone bit map (orderable) and the float32 box arithmetic (pairwise_iou, decode_box, clip).  This
+// file keeps what is its own: desc_key's rules for -0.0, NaN and KEY_NONE, the NaN-keeping clamp in front of decode_box.
 #include <float.h>
 #include <stdlib.h>
 #include "common.h"
@@ -31,8 +34,7 @@ __device__ __forceinline__ unsigned desc_key(float v) {
   unsigned b = __float_as_uint(v);
   if (b == 0x80000000u) b = 0u;                      // -0.0 ties with +0.0, as under torch.sort
   if ((b & 0x7FFFFFFFu) > 0x7F800000u) return 0u;    // NaN sorts first in a descending torch.sort (and is then refused / filtered)
-  const unsigned mono = (b & 0x80000000u) ? ~b : (b | 0x80000000u);    // ascending float order
-  const unsigned k = ~mono;
+  const unsigned k = ~orderable(__uint_as_float(b));                   // orderable: ascending float order
   return k == KEY_NONE ? KEY_NONE - 1 : k;
 }
 
@@ -182,18 +184,9 @@ __global__ void sel_scan_kernel(SegTab t, SelState* __restrict__ st, unsigned* _
 // block-wide exclusive scan of 4 flags per thread (CHUNK = 1024 = 256 threads x 4 consecutive elements)
 __device__ __forceinline__ void block_scan4(const unsigned f[4], unsigned out[4], unsigned* sh /*[256]*/) {
   const unsigned mine = f[0] + f[1] + f[2] + f[3];
-  sh[threadIdx.x] = mine;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const unsigned v = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0u;
-    __syncthreads();
-    sh[threadIdx.x] += v;
-    __syncthreads();
-  }
-  unsigned run = sh[threadIdx.x] - mine;
+  unsigned run = block_scan<256>(mine, sh, ScanAdd()).incl - mine;
 #pragma unroll
   for (int j = 0; j < 4; ++j) { out[j] = run; run += f[j]; }
-  __syncthreads();
 }
 
 // the selected elements in INDEX order: sel_idx[seg * sel_stride + pos] = index inside the segment; mark[mark_off + i] = mark_val
@@ -258,15 +251,7 @@ int sel_run(const SegTab& t, char* ws, const unsigned* keys, const int* k_dev, i
 }
 
 // ---------------------------------------------------------------------------------------------------- boxes
-// structures/boxes.py:337-370 pairwise_iou, one pair, every operation rounded to f32 as torch evaluates it
-__device__ __forceinline__ float iou_pair(const float4 a, const float4 b) {
-  const float a1 = __fmul_rn(__fsub_rn(a.z, a.x), __fsub_rn(a.w, a.y));
-  const float a2 = __fmul_rn(__fsub_rn(b.z, b.x), __fsub_rn(b.w, b.y));
-  const float w = fmaxf(__fsub_rn(fminf(a.z, b.z), fmaxf(a.x, b.x)), 0.f);
-  const float h = fmaxf(__fsub_rn(fminf(a.w, b.w), fmaxf(a.y, b.y)), 0.f);
-  const float inter = __fmul_rn(w, h);
-  return inter > 0.f ? __fdiv_rn(inter, __fsub_rn(__fadd_rn(a1, a2), inter)) : 0.f;
-}
+// (pairwise_iou, decode_box and clip are common.h's)
 
 // ---------------------------------------------------------------------------------------------------- RPN proposal selection
 struct RpnLevels {
@@ -305,18 +290,7 @@ __global__ __launch_bounds__(1024) void rpn_sort_pack_kernel(int CAP, RpnLevels 
     sk[i] = v;
   }
   __syncthreads();
-  for (int k2 = 2; k2 <= CAP; k2 <<= 1)
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < CAP; i += blockDim.x) {
-        const int p = i ^ j;
-        if (p > i) {
-          const unsigned long long a = sk[i], b = sk[p];
-          const bool up = (i & k2) == 0;
-          if ((a > b) == up) { sk[i] = b; sk[p] = a; }
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_sort<true>(sk, CAP);
   // rows of this level inside the image's candidate block: levels in order, pre_topk slots each
   const float H = (float)img_hw[2 * img], W = (float)img_hw[2 * img + 1];
   const float ninf = -__uint_as_float(0x7F800000u);
@@ -332,20 +306,16 @@ __global__ __launch_bounds__(1024) void rpn_sort_pack_kernel(int CAP, RpnLevels 
     const float* d = lv.deltas[l] + irow * 4;
     const float* an = lv.anchors[l] + (long)a * 4;
     const float logit = lv.logits[l][irow];
-    // apply_deltas: widths / heights / centres of the anchor, deltas / weights, clamp dw, dh
-    const float aw = __fsub_rn(an[2], an[0]), ah = __fsub_rn(an[3], an[1]);
-    const float cx = __fadd_rn(an[0], __fmul_rn(0.5f, aw)), cy = __fadd_rn(an[1], __fmul_rn(0.5f, ah));
-    const float dx = __fdiv_rn(d[0], w0), dy = __fdiv_rn(d[1], w1);
+    // apply_deltas: deltas / weights, clamp dw, dh.  The ternary KEEPS a NaN dw / dh as torch.clamp(max=) does (fminf, the heads'
+    // clamp, drops it): the box comes out NaN and clears finite[img]
     float dw = __fdiv_rn(d[2], w2), dh = __fdiv_rn(d[3], w3);
-    dw = dw > scale_clamp ? scale_clamp : dw; dh = dh > scale_clamp ? scale_clamp : dh;      // torch.clamp(max=): NaN stays NaN (fminf drops it)
-    const float pcx = __fadd_rn(__fmul_rn(dx, aw), cx), pcy = __fadd_rn(__fmul_rn(dy, ah), cy);
-    const float pw = __fmul_rn(expf(dw), aw), ph = __fmul_rn(expf(dh), ah);
-    const float x1 = __fsub_rn(pcx, __fmul_rn(0.5f, pw)), y1 = __fsub_rn(pcy, __fmul_rn(0.5f, ph));
-    const float x2 = __fadd_rn(pcx, __fmul_rn(0.5f, pw)), y2 = __fadd_rn(pcy, __fmul_rn(0.5f, ph));
+    dw = dw > scale_clamp ? scale_clamp : dw; dh = dh > scale_clamp ? scale_clamp : dh;
+    const float4 p = decode_box(make_float4(an[0], an[1], an[2], an[3]), __fdiv_rn(d[0], w0), __fdiv_rn(d[1], w1), dw, dh);
+    const float x1 = p.x, y1 = p.y, x2 = p.z, y2 = p.w;
     const bool f4 = (x1 - x1 == 0.f) && (y1 - y1 == 0.f) && (x2 - x2 == 0.f) && (y2 - y2 == 0.f) && (logit - logit == 0.f);
     fin = fin && f4;
-    const float cw = __fsub_rn(fminf(fmaxf(x2, 0.f), W), fminf(fmaxf(x1, 0.f), W));
-    const float ch = __fsub_rn(fminf(fmaxf(y2, 0.f), H), fminf(fmaxf(y1, 0.f), H));
+    const float cw = __fsub_rn(clip(x2, W), clip(x1, W));
+    const float ch = __fsub_rn(clip(y2, H), clip(y1, H));
     sc[l] = (f4 && cw > 0.f && ch > 0.f) ? logit : ninf;
     for (int c = 0; c < L; ++c) { bx[4 * c] = x1; bx[4 * c + 1] = y1; bx[4 * c + 2] = x2; bx[4 * c + 3] = y2; }
   }
@@ -373,7 +343,7 @@ __global__ __launch_bounds__(256) void anchor_best_kernel(LabelArgs g, unsigned*
   for (int gi = 0; gi < G; ++gi) {
     const float4 b = gt[gi];
     float m = 0.f;
-    for (long a = (long)blockIdx.x * blockDim.x + threadIdx.x; a < g.A; a += (long)gridDim.x * blockDim.x) m = fmaxf(m, iou_pair(b, an[a]));
+    for (long a = (long)blockIdx.x * blockDim.x + threadIdx.x; a < g.A; a += (long)gridDim.x * blockDim.x) m = fmaxf(m, pairwise_iou(b, an[a]));
     m = wave_reduce_max(m);
     if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(&best[g.g_off[img] + gi], __float_as_uint(m));
   }
@@ -397,7 +367,7 @@ __global__ __launch_bounds__(256) void anchor_label_kernel(LabelArgs g, const un
     const float4 box = an[a];
     float mv = -1.f; int mi = 0; bool low = false;
     for (int gi = 0; gi < G; ++gi) {
-      const float v = iou_pair(gt[gi], box);
+      const float v = pairwise_iou(gt[gi], box);
       if (v > mv) { mv = v; mi = gi; }
       if (__float_as_uint(v) == best[g.g_off[img] + gi]) low = true;       // == the gt's best IoU (0 included: matcher.py:121-126)
     }
@@ -500,7 +470,7 @@ __global__ __launch_bounds__(1024) void roi_sample_kernel(RoiSampleArgs ra, cons
     if (i < n) {
       const float4 b = box_of(i);
       float mv = -1.f;
-      for (int gi = 0; gi < G; ++gi) { const float v = iou_pair(gb[gi], b); if (v > mv) { mv = v; mi = gi; } }
+      for (int gi = 0; gi < G; ++gi) { const float v = pairwise_iou(gb[gi], b); if (v > mv) { mv = v; mi = gi; } }
       cls = (G > 0 && mv >= thr) ? gc[mi] : K;
     }
     s_cls[i] = (short)cls; s_m[i] = (short)mi;
@@ -513,39 +483,19 @@ __global__ __launch_bounds__(1024) void roi_sample_kernel(RoiSampleArgs ra, cons
     const int cls = i < CAP ? (int)s_cls[i] : -2;
     for (int w = 0; w < 2; ++w) {
       const unsigned f = (w == 0) ? (cls >= 0 && cls != K) : (cls == K);
-      sh[threadIdx.x] = f;
-      __syncthreads();
-      for (int o = 1; o < 1024; o <<= 1) {
-        unsigned v = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += v;
-        __syncthreads();
-      }
-      const unsigned incl = sh[threadIdx.x], total = sh[1023];
-      __syncthreads();
+      const BlockScan<unsigned> sc = block_scan<1024>(f, sh, ScanAdd());
       if (f && i < CAP) {
-        const unsigned pos = (w == 0 ? base_p : base_n) + incl - 1;
+        const unsigned pos = (w == 0 ? base_p : base_n) + sc.incl - 1;
         const unsigned key = hash_key24(ra.seeds[2 * img + w], pos);
         // sort key: list (0 = foreground first), random key, position; payload row
         sk[i] = ((unsigned long long)w << 63) | ((unsigned long long)key << 36) | ((unsigned long long)(pos & 0xFFFFFu) << 16) | (unsigned)i;
       }
-      if (w == 0) base_p += (int)total; else base_n += (int)total;
+      if (w == 0) base_p += (int)sc.total; else base_n += (int)sc.total;
     }
     if (i < CAP && !((cls >= 0 && cls != K) || cls == K)) sk[i] = ~0ull;
   }
   __syncthreads();
-  for (int k2 = 2; k2 <= CAP; k2 <<= 1)
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < CAP; i += blockDim.x) {
-        const int p = i ^ j;
-        if (p > i) {
-          const unsigned long long a = sk[i], b = sk[p];
-          const bool up = (i & k2) == 0;
-          if ((a > b) == up) { sk[i] = b; sk[p] = a; }
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_sort<true>(sk, CAP);
   const int n_pos = base_p, n_neg = base_n;
   const int num_pos = min(n_pos, max_pos), num_neg = min(n_neg, batch - num_pos);
   if (threadIdx.x == 0) out_cnt[img] = num_pos + num_neg;
@@ -639,19 +589,10 @@ __global__ __launch_bounds__(1024) void roi_levels_kernel(LevelArgs g, int R, co
     }
     for (int l = 0; l < 4; ++l) {
       const unsigned f = lv == l ? 1u : 0u;
-      sh[threadIdx.x] = f;
+      const BlockScan<unsigned> sc = block_scan<1024>(f, sh, ScanAdd());
+      if (f) sel[(long)l * R + s_base[l] + sc.incl - 1] = r;
       __syncthreads();
-      for (int o = 1; o < 1024; o <<= 1) {
-        const unsigned v = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += v;
-        __syncthreads();
-      }
-      const unsigned incl = sh[threadIdx.x], tot = sh[1023];
-      __syncthreads();
-      if (f) sel[(long)l * R + s_base[l] + incl - 1] = r;
-      __syncthreads();
-      if (threadIdx.x == 0) s_base[l] += (int)tot;
+      if (threadIdx.x == 0) s_base[l] += (int)sc.total;
       __syncthreads();
     }
   }

@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, staging, wgrad
+from .ops import _splitmix64
 from .registry import META_ARCH_REGISTRY
 from .structures import Boxes, Instances
 
@@ -1071,14 +1072,6 @@ class _SplitRowsFn(torch.autograd.Function):
             r0 += n * H * W
         ops.copy_multi(pairs)
         return full, None
-
-
-def _splitmix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
-    z = x
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
-    return z ^ (z >> 31)
 
 
 class Sampler:

@@ -14,6 +14,14 @@ def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _splitmix64(x):
+    """sw_splitmix64 of csrc/common.h on a Python int: the host derives its seeds with the generator the kernels draw from"""
+    x = (x + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return x ^ (x >> 31)
+
+
 def _floats(vals, n):
     """HOST float[n] argument (configuration constants passed by value into a launch)"""
     return (ctypes.c_float * n)(*[float(v) for v in vals])

@@ -32,6 +32,7 @@ from .events import get_event_storage, has_event_storage
 from .fast_rcnn_oicr import OICROutputLayers
 from .fast_rcnn_wsddn import WSDDNOutputLayers
 from .inference import SCALE_CLAMP
+from .ops import _splitmix64
 from .poolers import ROIPooler
 from .registry import ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY
 from .structures import ShapeSpec
@@ -84,13 +85,6 @@ def loss_names(refine_K):
     for k in range(refine_K):
         names += [f"loss_cls_r{k}", f"loss_box_reg_r{k}"]
     return names
-
-
-def _splitmix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
-    return x ^ (x >> 31)
 
 
 def _current_rank():

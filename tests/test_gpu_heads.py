@@ -191,6 +191,23 @@ def test_predict_against_float64(ops, c):
     assert bool(_untouched(sc[R]).all() and _untouched(bx[R]).all())
 
 
+def test_predict_with_nan_size_deltas_gives_the_clamped_box(ops):
+    """the heads' clamp of dw and of dh is fminf, which drops a NaN: the box is the one deltas above scale_clamp decode to, finite,
+    where the reference's torch.clamp(max=) would keep the NaN (known, left as it is)"""
+    K = 1
+    boxes = torch.tensor([[10.0, 10.0, 30.0, 50.0]] * 2, device="cuda")
+    lg = torch.zeros(2, 5 * K + 1, device="cuda")
+    lg[0, K + 1 + 2:K + 1 + 4] = float("nan")                                               # dw and dh: one fminf each
+    lg[1, K + 1 + 2:K + 1 + 4] = 1e3                                                        # far above scale_clamp * weight
+    sc, bx = _sent(2, K + 1), _sent(2, 4 * K)
+    ops.oicr_predict(lg, 2, K, 1, 0, 5 * K + 1, boxes, H.REG_WEIGHTS, H.SCALE_CLAMP, sc, bx)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(bx).all()), bx.tolist()
+    assert torch.equal(bx[0], bx[1]), bx.tolist()
+    assert float(bx[0, 2] - bx[0, 0]) > 1000.0 and float(bx[0, 3] - bx[0, 1]) > 2000.0       # exp(scale_clamp) = 62.5 times 20 x 40
+    assert float(bx[0, 0] + bx[0, 2]) == 40.0 and float(bx[0, 1] + bx[0, 3]) == 60.0         # the centre stays
+
+
 def test_predict_of_no_rows_is_a_no_op(ops):
     K = 20
     sc, bx = _sent(3, K + 1), _sent(3, 4 * K)

@@ -78,7 +78,7 @@ def test_update_boxes_two_heads_and_column_stride(ops):
 
 
 # ------------------------------------------------------------------------------------------------ sw_oicr_mine_label
-def _mine(ops, scores, boxes, gt, K, cand=None, cand_from=0, seed_rule=0, ext=True, top_p=0.10):
+def _mine(ops, scores, boxes, gt, K, cand=None, cand_from=0, seed_rule=0, ext=True, top_p=0.10, iou_bg=0.5):
     """one launch over scores [NR][R][ncol]; -> dict of host arrays per round, after checking sentinels and a second, bit-equal launch"""
     scores = np.asarray(scores, np.float32)
     NR, R, _ = scores.shape
@@ -95,7 +95,7 @@ def _mine(ops, scores, boxes, gt, K, cand=None, cand_from=0, seed_rule=0, ext=Tr
         if ext:
             kw = dict(cand_boxes=None if cand is None else _cu(np.asarray(cand, np.float32)), cand_from=cand_from, seed_rule=seed_rule,
                       lab_box=b["lab_b"][4:4 + NR * R * 4], pgt_box=b["pb"])
-        ops.oicr_mine_label(_cu(scores), _cu(np.asarray(gt, np.int32)), _cu(boxes), K, top_k, 0.05, 0.01, 0.5, 0.6, b["lab_c"],
+        ops.oicr_mine_label(_cu(scores), _cu(np.asarray(gt, np.int32)), _cu(boxes), K, top_k, 0.05, 0.01, iou_bg, 0.6, b["lab_c"],
                             b["lab_w"], b["lab_i"], b["cnt"], b["pi"], b["pc"], b["ps"], ws, **kw)
         torch.cuda.synchronize()
         runs.append({k: v.cpu() for k, v in b.items()})
@@ -156,6 +156,65 @@ def test_mining_edge_cases_against_the_restatement(ops, name):
     cand = None if c["cand"] is None else c["cand"][None]
     got = _mine(ops, c["scores"][None], c["boxes"], c["gt"], c["K"], cand, 0, c["seed_rule"])[0]
     _same(got, p, l, name)
+
+
+def test_mining_pairwise_iou_edge_pairs(ops):
+    """pairwise_iou at its edges through the labels, with iou_bg = 0 so that an IoU of exactly 0 (ignore, -1) and a NaN or negative one
+    (background) part ways; expected from the oracle's pairwise_iou and matcher at thresholds (0, 0.6).  One seed (row 0, class 3):
+    a zero-area seed against itself and its twin must give 0, not 0 / 0; a box sharing only an edge gives exactly 0; a proposal with
+    a NaN coordinate counts as 0 in the extended kernel (the plain one leaves the NaN, which never wins)"""
+    K, gt = 20, np.array([3], np.int64)
+    flat, seed = [30, 30, 30, 40], [10, 10, 20, 20]
+    runs = {"zero_area": (False, [flat, flat, [30, 30, 40, 40], [100, 100, 110, 110]]),
+            "edge": (False, [seed, [20, 10, 30, 20], [12, 10, 22, 20], [100, 100, 110, 110]]),
+            "nan": (True, [seed, [np.nan, 10, 20, 20], [10, 10, 20, np.nan], [20, 10, 30, 20]])}
+    for name, (ext, bx) in runs.items():
+        boxes = np.array(bx, np.float32)
+        scores = np.full((1, len(boxes), K + 1), 0.01, np.float32)
+        scores[0, 0, 3] = 0.9
+        got = _mine(ops, scores, boxes, gt, K, ext=ext, iou_bg=0.0)[0]
+        assert got["pgt_index"].tolist() == [0], name
+        m, lab = M.O.matcher(M.O.pairwise_iou(boxes[:1], boxes), thresholds=(0.0, 0.6))
+        want = np.where(lab == 1, 3, np.where(lab == 0, K, -1))
+        assert np.array_equal(got["lab_class"], want), f"{name}: labels {got['lab_class'].tolist()}, the oracle's {want.tolist()}"
+        assert want.tolist() == {"zero_area": [-1, -1, -1, -1], "edge": [3, -1, 3, -1], "nan": [3, -1, -1, -1]}[name]
+
+
+def test_mining_ranks_signed_zeros_and_nan_scores_by_their_bits(ops):
+    """make_key orders a score column by the bits of the monotone map, not by value: +0.0 ranks above -0.0 (a value order would tie and
+    take the lower row), every negative score below both, and a +NaN above everything.  Only the seed (rank 0) passes the score
+    threshold here, so the list is the top of the column"""
+    K, R, gt = 20, 24, np.array([3], np.int64)
+    gx, gy = np.meshgrid(np.arange(6), np.arange(4))
+    boxes = np.stack([gx.ravel() * 40.0, gy.ravel() * 40.0, gx.ravel() * 40.0 + 30.0, gy.ravel() * 40.0 + 30.0], 1).astype(np.float32)
+    scores = np.zeros((1, R, K + 1), np.float32)
+    scores[0, :, 3] = -np.arange(1, R + 1, dtype=np.float32)               # every other row negative, row 23 the most
+    scores[0, 2, 3], scores[0, 5, 3] = -0.0, 0.0
+    got = _mine(ops, scores, boxes, gt, K, ext=False)[0]
+    assert got["pgt_index"].tolist() == [5] and _bits(got["pgt_score"]).tolist() == _bits([0.0]).tolist()
+    scores[0, 5, 3] = -0.5                                                  # without the +0.0 the -0.0 leads, bit for bit
+    got = _mine(ops, scores, boxes, gt, K, ext=False)[0]
+    assert got["pgt_index"].tolist() == [2] and _bits(got["pgt_score"]).tolist() == _bits([-0.0]).tolist()
+    scores[0, 7, 3] = np.nan
+    got = _mine(ops, scores, boxes, gt, K, ext=False)[0]
+    assert got["pgt_index"].tolist() == [7] and np.isnan(got["pgt_score"]).all()
+
+
+def test_update_boxes_with_nan_size_deltas_gives_the_clamped_box(ops):
+    """sw_oicr_update_boxes averages the views' deltas and clamps dw, dh with fminf, which drops a NaN: the box is the one deltas above
+    scale_clamp decode to, finite, where the reference's torch.clamp(max=) would keep the NaN"""
+    V, R, K, G = 2, 2, 1, 1
+    lg = np.zeros((V * R, 4), np.float32)
+    lg[0, 2:] = np.nan                                                     # row 0, view 0: the mean of (NaN, 0) is NaN
+    lg[1, 2:] = 1e3; lg[3, 2:] = 1e3                                       # row 1: far above scale_clamp * weight in both views
+    boxes = np.array([[10, 10, 30, 50]] * 2, np.float32)
+    out = _sent(R, G, 4)
+    ops.oicr_update_boxes(_cu(lg), V, R, K, 1, 0, 0, _cu(boxes), _cu(np.zeros(G, np.int32)), _cu(np.ones(V, np.int32)), M.WEIGHTS,
+                          M.SCALE_CLAMP, out)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(out).all()), out.tolist()
+    assert torch.equal(out[0], out[1]), out.tolist()
+    assert float(out[0, 0, 2] - out[0, 0, 0]) > 1000.0 and float(out[0, 0, 3] - out[0, 0, 1]) > 2000.0
 
 
 def test_mining_workspace_form_with_candidate_boxes(ops):

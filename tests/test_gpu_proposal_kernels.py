@@ -147,6 +147,23 @@ def test_decode_against_float64(ops, weights):
     assert worst <= e["bar"]
 
 
+def test_decode_keeps_nan_size_deltas(ops):
+    """the RPN's clamps of dw and of dh keep a NaN as torch.clamp(max=) does (the heads' fminf drops it): a NaN dw makes x0 and x2 of
+    that box NaN, a NaN dh y0 and y2, the score is -inf and finite[img] is cleared; the other image is untouched by it"""
+    an = _t(np.array([[10, 10, 30, 50], [100, 100, 120, 140]], np.float32))
+    dl = np.zeros((2, 2, 4), np.float32)
+    dl[0, 0, 2] = np.nan                                                                # dw of anchor 0, dh of anchor 1: one clamp each
+    dl[0, 1, 3] = np.nan
+    img_hw = torch.tensor([[300, 400]] * 2, dtype=torch.int32).cuda()
+    sc, bx, fin = ops.rpn_select_pack([_t(np.array([[2.0, 1.0]] * 2, np.float32))], [_t(dl)], [an], 2, R.W1, R.SCALE_CLAMP, img_hw)
+    torch.cuda.synchronize()
+    sc, bx, fin = sc.cpu().numpy(), bx.cpu().numpy(), fin.cpu().numpy()
+    assert (fin != 0).tolist() == [False, True]
+    assert np.isnan(bx[0, 0, [0, 2]]).all() and bx[0, 0, [1, 3]].tolist() == [10.0, 50.0] and np.isneginf(sc[0, 0]).all()
+    assert np.isnan(bx[0, 1, [1, 3]]).all() and bx[0, 1, [0, 2]].tolist() == [100.0, 120.0] and np.isneginf(sc[0, 1]).all()
+    assert bx[1].tolist() == [[10.0, 10.0, 30.0, 50.0], [100.0, 100.0, 120.0, 140.0]] and sc[1, :, 0].tolist() == [2.0, 1.0]
+
+
 # ------------------------------------------------------------------------------------------------ 3. anchor labels
 @pytest.mark.parametrize("case", R.LABEL_CASES, ids=[c[0] for c in R.LABEL_CASES])
 def test_rpn_label_anchors_against_the_oracle(ops, case):
@@ -167,6 +184,27 @@ def test_rpn_label_anchors_against_the_oracle(ops, case):
         by_m = {m: int(labels[0][pos[j]]) for j, m in enumerate(R.SPECIAL_M)}
         assert by_m == {70: 1, 30: -1, 100: 1, 71: 1, 69: -1, 31: -1, 29: 0, 1: 0}, by_m   # IoU == 0.7 -> 1, == 0.3 -> -1 and not 0
         assert np.array_equal(matched[0][pos[len(R.SPECIAL_M)]], R.SPLIT_GT[0])            # two equally good boxes: the first wins
+
+
+def test_rpn_label_anchors_pairwise_iou_edge_pairs(ops):
+    """pairwise_iou at its edges, nothing sampled away, against the oracle's matcher: a box that shares only an edge with the
+    ground-truth box (inter == 0: IoU exactly 0), a zero-area box against itself (0, not 0 / 0 = NaN: as the image's only
+    ground-truth box its best IoU is 0, so every anchor with IoU 0 is a low-quality positive, the twin included), and an anchor with
+    a NaN coordinate.  There the oracle's intersection is NaN and its where(inter > 0, ., 0) gives 0; the kernel's fminf / fmaxf drop
+    the NaN, its intersection is positive and pairwise_iou returns inter / NaN = NaN, not 0: the labels agree because a NaN never
+    wins `v > best` and never equals a ground-truth box's best IoU"""
+    gt = np.array([10, 10, 20, 20], np.float32)
+    flat = np.array([30, 30, 30, 40], np.float32)                                       # zero width
+    an = np.array([[10, 10, 20, 20], [20, 10, 30, 20], [10, 20, 20, 30], [12, 10, 22, 20], flat, [40, 40, 50, 50],
+                   [np.nan, 10, 20, 20], [10, 10, 20, np.nan]], np.float32)
+    for name, gtb in (("edge", gt[None]), ("flat_twin", flat[None]), ("both", np.stack([gt, flat]))):
+        want = R.matcher_labels(an, gtb)
+        labels, matched = ops.rpn_label_anchors(_t(an), _t(gtb), [len(gtb)], [1, 2], 64, 64)
+        torch.cuda.synchronize()
+        got = labels.cpu().numpy().astype(np.int64)[0]
+        assert np.array_equal(got, want), f"{name}: labels {got.tolist()}, the oracle's matcher {want.tolist()}"
+    assert R.matcher_labels(an, gt[None]).tolist()[:3] == [1, 0, 0]                    # the edge neighbours are background, not ignored
+    assert R.matcher_labels(an, flat[None])[4] == 1                                     # the twin of the zero-area box: IoU 0 == its best
 
 
 # ------------------------------------------------------------------------------------------------ 4. ROI sampling
